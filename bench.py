@@ -1,18 +1,25 @@
 #!/usr/bin/env python3
 """Headline benchmark of the tiny-diffusion DDPM hot path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]          (N > 1: starts its own N ranks)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]   (N > 1: starts its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one full training step of the unconditional MNIST 28x28 UNet in fp32 on a
 per-GPU minibatch of 256 synthetic MNIST-shaped images (BASELINE.json configs[1];
 weak scaling for N > 1): t ~ U, q_sample, UNet forward (train-mode BatchNorm), MSE,
 backward of every parameter, gradient all-reduce (N > 1), Adam.  Rank 0 prints ONE
-JSON line.  `value` = images/s of the whole job; `roofline` = fp32-MFMA fraction of
-the 3x3 convolution kernels (>= 99.9 % of the FLOPs) timed live with HIP events;
-`cpu_baseline` = the CPU oracle (a port of the reference path, checked against the
-reference's own outputs) timed on this host; `sample` = wall-clock of the reference's
-1000-step reverse loop (graph-replayed) at n = 16 and n = 64.
+JSON line.  `value` = images/s of the whole job, `ms_per_step` = one timed step.
+
+A plain run sets up, warms up, times the K steps and prints the line; nothing else.
+--dump-outputs DIR then writes what the last timed step produced (see dump_outputs).
+--full adds everything else, outside the timed region: the first-step parity check
+against the CPU oracle (`parity_check`), for N > 1 the replica check and the step
+without the gradient exchange (`weak_scaling`), and - unless --no-extras - `roofline`
+= fp32-MFMA fraction of the 3x3 convolution kernels (>= 99.9 % of the FLOPs) timed
+live with HIP events; `cpu_baseline` = the CPU oracle (a port of the reference path,
+checked against the reference's own outputs) timed on this host; `sample` = wall-clock
+of the reference's 1000-step reverse loop (graph-replayed) at n = 16 and n = 64; the
+HBM-bound kernels, the bf16 mode and the LAION / latent legs.
 """
 from __future__ import annotations
 
@@ -793,17 +800,57 @@ def timed_steps(ts, x0, warmup: int, steps: int, barrier):
     return time.perf_counter() - t0, loss
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(out_dir: str, arrays: dict) -> dict:
+    """Each entry as <out_dir>/<name>.npy in float32 (float64 stays float64); at most DUMP_LIMIT_BYTES in all.
+    Returns {name: shape}."""
+    import numpy as np
+
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = t.numpy() if t.dtype == torch.float64 else t.float().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench: outputs of {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte dump limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in host.items()}
+
+
+def dump_outputs(out_dir: str, model, ts, loss) -> dict:
+    """What a caller of TrainStep.step holds after the last timed step: the returned loss, and the model it
+    updated in place - every parameter (the flat fp32 buffer the parameters are views of, 11.18 M floats, in
+    TrainStep's order) and the BatchNorm running statistics (floating-point buffers in named_buffers() order)."""
+    bufs = [b.detach().reshape(-1).float() for _, b in model.named_buffers() if b.is_floating_point()]
+    return write_outputs(out_dir, {"loss": loss.reshape(-1), "params": ts.flat_param,
+                                   "bn_running_stats": torch.cat(bufs)})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline / cpu baseline / sampling legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write the last step's loss, parameters and BatchNorm running statistics "
+                         "as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity check, the replica check / single-rank step (N > 1) and, unless "
+                         "--no-extras, every other leg (roofline, probes, HBM kernels, CPU baseline, sampling, bf16, "
+                         "LAION, latent)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip roofline / cpu baseline / sampling legs")
     ap.add_argument("--roofline-only", action="store_true",
                     help="run only the per-launch conv timing leg (for rocprofv3 cross-checks)")
     ap.add_argument("--train-only", action="store_true",
                     help="run only the timed training steps (for rocprofv3 traces of the real step)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench: --steps must be >= 1 and --warmup >= 0")
+    extras = args.full and not args.no_extras and not args.train_only
     if args.roofline_only:
         torch.cuda.set_device(0)
         print(json.dumps({"roofline": roofline_block(PER_GPU_BATCH)}))
@@ -847,7 +894,7 @@ def main():
             torch.distributed.barrier()
 
     parity = None
-    if rank == 0 and not args.train_only:
+    if rank == 0 and args.full and not args.train_only:
         note("first-step parity check against the CPU oracle (B=256 forward on the host) ...")
         parity = first_step_parity(model, fp, x0, 1234)   # untimed; the other ranks wait at the barrier
         note(f"parity ok: {parity}")
@@ -856,11 +903,14 @@ def main():
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = tt.item()
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, model, ts, loss)
+        note(f"outputs of the last step in {args.dump_outputs}: {dumped}")
     loss_v = loss.item()
     if not (loss_v == loss_v) or loss_v > 1e3:
         raise SystemExit(f"training diverged in the benchmark: loss {loss_v}")
     single = None
-    if world > 1:
+    if world > 1 and args.full:
         # outside the timed region: replicas must still hold identical parameters
         probe = torch.stack([ts.flat_param.double().sum(), ts.flat_param.double().pow(2).sum()])
         lo, hi = probe.clone(), probe.clone()
@@ -881,7 +931,7 @@ def main():
         del ts1, m1
 
     multi = None
-    if world > 1 and not args.no_extras and not args.train_only:
+    if world > 1 and extras:
         # BASELINE's metric also names the 1000-step sample latency at every N.  Sampling does not shard (SURVEY.md
         # 8(e): replicas only): every rank runs its OWN chains at n = 16 and n = 64 with no collective in the path,
         # all ranks at once; the line reports the MAX over ranks (what the slowest replica's user waits for).  The
@@ -925,7 +975,7 @@ def main():
                 "efficiency": round(value / world / single, 4),
                 "note": "single_rank = the same step with the gradient all-reduce disabled, timed on all "
                         f"{world} GPUs at once after the main region (mean over ranks); backend " + backend}
-        if not args.no_extras and not args.train_only and world == 1:
+        if extras and world == 1:
             note(f"train: {value:.0f} images/s, {ms_per_step:.3f} ms/step; peak probes ...")
             probes = peak_probes()
             note(f"probes {probes}; conv roofline leg ...")

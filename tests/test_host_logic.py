@@ -169,6 +169,25 @@ def test_bench_self_launch_command(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_write_outputs(tmp_path):
+    """bench.py --dump-outputs: every array as <name>.npy, float32 unless it is float64, and refused beyond 64 MB."""
+    import sys
+
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    shapes = bench.write_outputs(str(tmp_path / "out"), {"a": torch.arange(6, dtype=torch.float16).reshape(2, 3),
+                                                         "b": torch.ones(4, dtype=torch.float64)})
+    assert shapes == {"a": [2, 3], "b": [4]}
+    a, b = np.load(tmp_path / "out" / "a.npy"), np.load(tmp_path / "out" / "b.npy")
+    assert a.dtype == np.float32 and a.tolist() == [[0, 1, 2], [3, 4, 5]] and b.dtype == np.float64
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "big"), {"x": torch.zeros((64 << 20) // 4 + 1)})
+    assert not (tmp_path / "big").exists()
+
+
 def test_conv_descriptor_bound():
     """32-bit buffer offsets with 0x80000000 as the zero-padding sentinel: shapes whose activation
     tensors reach 2 GiB are refused (TDX_E_SHAPE) instead of silently reading real memory for padding

@@ -9,6 +9,7 @@ tag=${1:-r04}
 mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
 run() { echo "[evidence] $*" >&2; "$@"; }
+bench_raw=$(mktemp -d)   # raw rocprofv3 output of the full benchmark (`bench.py --full`): only its conversions are kept
 # which sources the profiled library was built from: the converters stamp it into profiles/<tag>_*.json and bench.py
 # reports a committed profile as a measurement of the running build only when the hashes agree
 python3 -c "from tiny_diffusion_amd import _build; print(_build.source_hash())" > gpurun_out/${tag}_src_sha256.txt
@@ -17,7 +18,7 @@ run rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/${tag}_pmc_f --
 run rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/${tag}_pmc_w -- python3 bench.py --roofline-only > /dev/null 2> gpurun_out/${tag}_pmc_w.err && echo pmc_w ok &&
 run rocprofv3 --pmc MfmaUtil --output-format csv -d gpurun_out/${tag}_pmc_mfma -- python3 bench.py --roofline-only > /dev/null 2> gpurun_out/${tag}_pmc_mfma.err && echo pmc_mfma ok &&
 run rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${tag}_train -- python3 bench.py --train-only --steps 30 --warmup 5 > gpurun_out/${tag}_train.json 2> gpurun_out/${tag}_train.err && echo train ok &&
-run rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${tag}_bench -- python3 bench.py --steps 20 --warmup 5 > gpurun_out/${tag}_bench_under_rocprof.json 2> gpurun_out/${tag}_bench.err && echo bench ok
+run rocprofv3 --kernel-trace --stats --output-format csv -d $bench_raw/trace -- python3 bench.py --full --steps 20 --warmup 5 > $bench_raw/line.json && echo bench ok
 rc=$?
 # the bf16 mode: kernel stats + one step's timeline of the MNIST leg, every GEMM launch in isolation, L2 counters
 rc16=0
@@ -45,9 +46,9 @@ if [ $rc -eq 0 ]; then
   fi
   keep "$(first "gpurun_out/${tag}_roof/*/*kernel_stats.csv")" $out/${tag}_roofline_leg_kernel_stats.csv || rc=1
   keep "$(first "gpurun_out/${tag}_train/*/*kernel_stats.csv")" $out/${tag}_train_only_kernel_stats.csv || rc=1
-  keep "$(first "gpurun_out/${tag}_bench/*/*kernel_stats.csv")" $out/${tag}_bench_default_kernel_stats.csv || rc=1
+  keep "$(first "$bench_raw/trace/*/*kernel_stats.csv")" $out/${tag}_bench_default_kernel_stats.csv || rc=1
   keep gpurun_out/${tag}_roof.json $out/${tag}_roofline_leg.json || rc=1
-  keep gpurun_out/${tag}_bench_under_rocprof.json $out/${tag}_bench_default_under_rocprof.json || rc=1
+  keep $bench_raw/line.json $out/${tag}_bench_default_under_rocprof.json || rc=1
   keep $sha $out/ || rc=1
   if [ $rc16 -eq 0 ]; then
     bf=$(first "gpurun_out/${tag}_bf16/*/*kernel_trace.csv")
@@ -91,6 +92,7 @@ if [ $rc -eq 0 ]; then
 fi
 # the raw rocprofv3 output directories are large (per-dispatch traces of two 1000-step chains): only the conversions travel back
 rm -rf gpurun_out/${tag}_bf16 gpurun_out/${tag}_roof gpurun_out/${tag}_pmc_f gpurun_out/${tag}_pmc_w gpurun_out/${tag}_pmc_mfma gpurun_out/${tag}_train gpurun_out/${tag}_bench
+rm -rf $bench_raw
 du -sh gpurun_out/${tag}_* 2>/dev/null
 [ $rc -eq 0 ] && rc=$rc16
 exit $rc
