@@ -206,6 +206,9 @@ int tdx_conv3x3_fwd_wino_infer(const float* in, const float* u, const float* bia
 /* 1 when a training step of the UNets at batch B runs this layer's forward (role 0) / input gradient (role 1) on the
  * Winograd kernel (tuning knobs "wino", "wino_min_wgs"), 0: on the direct kernels - what bench.py's roofline leg times. */
 int tdx_conv3x3_train_algo(int B, int H, int W, int cin, int cout, int role);
+/* 1 when a sampling (INFER-mode) forward of B samples runs this layer on tdx_conv3x3_fwd_wino_infer (tuning knobs
+ * "wino_infer", "wino_infer_min_units", "infer_ring"), 0: on the direct kernels (split-K tdx_conv3x3_fwd_splitk). */
+int tdx_conv3x3_infer_algo(int B, int H, int W, int cin, int cout);
 /* Weight gradient by F(3x3, 2x2) (the transposition of the forward's identity; both operands transformed on the fly):
  * dw_slabs = [tdx_conv3x3_wgrad_wino_splits(...)][cout][9][cin], the slab format of tdx_conv3x3_wgrad - sum with
  * tdx_conv3x3_wgrad_reduce.  Raw NHWC input and dy; cin % 64 == 0, cout % 64 == 0; any H, W. */

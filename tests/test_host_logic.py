@@ -290,3 +290,59 @@ def test_plan_lru_evicts_but_never_destroys_a_referenced_plan(monkeypatch):
     del held
     gc.collect()
     assert 16 in destroyed
+
+
+def _div_rcp(n, d):
+    """conv3x3_wino.hip::div_rcp in numpy float32: q = (int)((float)n * r) with r = 1.0f / d (host division), then one
+    fix-up step of the remainder."""
+    import numpy as np
+
+    r = np.float32(1.0) / np.float32(d)
+    q = np.trunc(n.astype(np.float32) * r).astype(np.int64)
+    m = n - q * d
+    lo, hi = m < 0, m >= d
+    q = q - lo + hi
+    m = m + d * lo - d * hi
+    return q, m
+
+
+def test_winograd_tile_division_in_fp32():
+    """The forward Winograd kernel divides tile indices n < 2^24 by th * tw and by tw with one fp32 multiplication by
+    the reciprocal and ONE fix-up step: correct only while the estimate is off by at most one.  tdx_conv3x3_wino_ok
+    admits launches of fewer than 2^24 - 64 tiles on that claim.  Every n in [0, 2^24) for every divisor of the maps of
+    both UNets (MNIST 28x28, LAION 32x32 / 64x64) and 1, then seeded random divisors up to 2^23 with n near their
+    multiples and near 2^24."""
+    import numpy as np
+
+    from tiny_diffusion_amd import unet as UN
+
+    divisors = {1}
+    for arch, sides in ((UN.ARCH_MNIST, (28,)), (UN.ARCH_LAION, (32, 64))):
+        for h in sides:
+            maps = []
+            for _ in arch.enc:
+                maps.append(h)
+                h = -(-h // 2) if arch.ceil_pool else h // 2
+            maps.append(h)                # bottleneck
+            for _ in arch.dec:
+                h *= 2
+                maps.append(h)
+            for H in maps:
+                tw = (H + 1) // 2
+                divisors |= {tw, tw * tw}
+    assert {1, 16, 4, 196} <= divisors   # 7x7: 4 x 4 tiles per image; 28x28: 14 x 14
+    n = np.arange(1 << 24, dtype=np.int64)
+    for d in sorted(divisors):
+        q, m = _div_rcp(n, d)
+        bad = np.nonzero((q != n // d) | (m != n % d))[0]
+        assert bad.size == 0, (d, bad[:5])
+    rng = np.random.default_rng(24)
+    divs = np.concatenate([rng.integers(2, 1 << 23, 400), rng.integers(2, 4096, 400), [(1 << 23) - 1, 1 << 23, 3, 7, 255]])
+    top = (1 << 24) - 1 - np.arange(4096, dtype=np.int64)
+    for d in divs.tolist():
+        k = rng.integers(0, (1 << 24) // d, 256, dtype=np.int64)
+        near = (k[:, None] * d + np.arange(-2, 3)[None, :]).ravel()
+        cand = np.concatenate([near, top, (((1 << 24) - 1) // d) * d + np.arange(-2, 3)])
+        cand = cand[(cand >= 0) & (cand < (1 << 24))]
+        q, m = _div_rcp(cand, d)
+        assert np.array_equal(q, cand // d) and np.array_equal(m, cand % d), (d, cand[q != cand // d][:5])

@@ -83,6 +83,7 @@ _SIGS = {
     "tdx_conv3x3_fwd_wino_infer": (C.c_int, [_ptr, _ptr, _ptr, _ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ptr, _ptr,
                                              _ptr, C.c_size_t, _ptr]),
     "tdx_conv3x3_train_algo": (C.c_int, [C.c_int] * 6),
+    "tdx_conv3x3_infer_algo": (C.c_int, [C.c_int] * 5),
     "tdx_conv3x3_wgrad_wino_splits": (C.c_int, [C.c_int] * 5),
     "tdx_conv3x3_wgrad_wino": (C.c_int, [_ptr, _ptr, _ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ptr]),
     "tdx_conv3x3_wino_stat_tiles": (C.c_int, [C.c_int] * 3),

@@ -966,7 +966,7 @@ extern "C" int tdx_tune_set(const char* key, int value) {
   if (!strcmp(key, "wino_infer_red")) { g_wino_infer_red = value >= 0 ? value : 3; return 0; }
   if (!strcmp(key, "wino_wgrad")) { g_tdx_wino_wgrad = value != 0; return 0; }
   if (!strcmp(key, "wino_wgrad_min_tiles")) { g_tdx_wino_wgrad_min_tiles = value > 0 ? value : 1024; return 0; }
-  if (!strcmp(key, "wino_wgrad_target")) { g_tdx_wino_wgrad_target = value > 0 ? value : 1024; return 0; }
+  if (!strcmp(key, "wino_wgrad_target")) { g_tdx_wino_wgrad_target = value > 0 ? value : 512; return 0; }
   if (!strcmp(key, "wino_min_wgs")) { g_tdx_wino_min_wgs = value > 0 ? value : 1; return 0; }
   if (!strcmp(key, "infer_ring")) { g_tdx_infer_ring = value != 0; return 0; }
   if (!strcmp(key, "infer_stages")) { g_infer_stages = value == 3 ? 3 : 4; return 0; }

@@ -537,6 +537,16 @@ extern "C" int tdx_conv3x3_train_algo(int B, int H, int W, int cin, int cout, in
   return blocks * ((role == 0 ? cout : cin) / 64) >= g_tdx_wino_min_wgs ? 1 : 0;
 }
 
+// 1 when an INFER-mode (sampling) forward of n = B samples runs this layer on the Winograd kernel with split K
+// (tdx_conv3x3_fwd_wino_infer), 0: on the direct kernels.  Winograd where the launch is big enough to pay for its fixed
+// costs (one workgroup per CU, ring fill, output transform, partials): measured per layer at n = 16 / 32 / 64
+// (profiles/r04_infer_layers_wino.txt) it wins wherever workgroups x stages >= ~800 and loses up to 6 us per layer
+// below (the 64-channel and 4x4 layers at n = 16).  The plan must also hold the Winograd pack (decide_wino).
+extern "C" int tdx_conv3x3_infer_algo(int B, int H, int W, int cin, int cout) {
+  if (!g_tdx_wino_infer || g_tdx_infer_ring || !tdx_conv3x3_wino_ok(B, H, W, cin, cout)) return 0;
+  return (int64_t)tdx_conv3x3_wino_stat_tiles(B, H, W) * (cout / 64) * (cin / 8) >= g_tdx_wino_infer_min_units ? 1 : 0;
+}
+
 static void decide_wino(tdx_unet* u, int B, bool training_modes) {
   for (int i = 0; i < 13; ++i) {
     u->wino_f[i] = u->wino_d[i] = u->wino_w[i] = false;
@@ -844,11 +854,9 @@ static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const
     if (infer) {
       const float* iss = u->infer_ss + u->iss_off[i];
       // small-batch sampling is latency-bound: split K over more workgroups where the tile
-      // grid would not fill the chip; the (unused in INFER mode) gradient buffers are the scratch
-      // Winograd where the launch is big enough to pay for its fixed costs (one workgroup per CU, ring fill, output
-      // transform, partials): measured per layer at n = 16 / 32 / 64 (profiles/r04_infer_layers_wino.txt) it wins wherever
-      // workgroups x stages >= ~800 and loses up to 6 us per layer below (the 64-channel and 4x4 layers at n = 16)
-      if (u->wino_f[i] && (int64_t)tdx_conv3x3_wino_stat_tiles(B, d.hw, d.hw) * (d.cout / 64) * (d.cin / 8) >= g_tdx_wino_infer_min_units)
+      // grid would not fill the chip; the (unused in INFER mode) gradient buffers are the scratch.
+      // Winograd where the launch is big enough to pay for its fixed costs (tdx_conv3x3_infer_algo)
+      if (u->wino_f[i] && tdx_conv3x3_infer_algo(B, d.hw, d.hw, d.cin, d.cout))
         return tdx_conv3x3_fwd_wino_infer_ex(in, u->upack + u->uf_off[i], bias, Y, B, d.hw, d.hw, d.cin, d.cout, iss,
                                              iss + d.cout, ws + L.G1, 2 * L.gbuf, stream, defer, pool);
       if (u->wf_tiled)
