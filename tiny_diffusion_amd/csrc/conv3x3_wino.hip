@@ -563,25 +563,39 @@ extern "C" int tdx_conv3x3_fwd_wino(const float* in, const float* u, const float
 //     dW = G^T [ (A e A^T) .* (B^T d B) ] G        e: the tile's 2x2 of dy,  A = (A^T of the forward)^T,  B^T, G as above
 //
 // 16 multiplications per (tile, co, ci) instead of 36, summed over the tiles: sixteen GEMMs M_p[co][ci] = sum_tiles E_p[tile][co]
-// V_p[tile][ci] whose K dimension is the TILES.  Both operands are transformed on the fly, per lane for its channel
-// (l31 is the output channel of the A operand and the input channel of the B operand) and four tiles per K-stage of
-// eight: the lane reads its channel of the tile's raw 4 dy pixels and 16 input pixels from [tile][pixel][channel] LDS
-// images (ds_read_b32, conflict-free: consecutive lanes = consecutive channels), computes E' = A' e A'^T (12 adds; A' is
-// A with the sign of its last row dropped - the signs s_xi s_nu come back in the output transform) and V = B^T d B (32
-// adds), and issues one MFMA per position with them - the operand trick along the tiles: MFMA j of a stage contracts
-// tile j (lanes 0-31) and tile 4+j (lanes 32-63).  A stage is 4 tile-iterations of 16 MFMAs; the operands of the NEXT
-// tile are read and transformed in the shadow of the current tile's MFMAs, so only the very first tile of a workgroup has
-// nothing to hide behind.  Three LDS stages of 40 KB (8 tiles x (16 + 4) pixels x 64 channels); the pieces of stage
-// s+2 are requested in tile-iteration 3 of stage s and tile-iteration 0 of stage s+1, two iterations before the single
-// barrier per stage that makes stage s+1 visible.  Per-tile addresses and validity masks (image borders, odd maps, the
-// ragged end of the chunk) come from a table the workgroup builds once in LDS.  Output: the direct kernel's slabs
-// [split][Cout][9][Cin] (G^T . G applied in the epilogue), summed by the shared fixed-order reduction.
+// V_p[tile][ci] whose K dimension is the TILES.  Both operands are transformed on the fly, per lane for its channels
+// (lane l31 gives the A operand of output channel 2 l31 + c and the B operand of one input channel) and four tiles per
+// K-stage of eight: the lane reads its channels of the tile's raw 4 dy pixels and input pixels from [tile][pixel][channel]
+// LDS images (conflict-free: consecutive lanes = consecutive channels), computes E' = A' e A'^T (A' is A with the sign
+// of its last row dropped - the signs s_xi s_nu come back in the output transform) and V = B^T d B, and issues one MFMA
+// per (position, output-channel parity c) with them - the operand trick along the tiles: MFMA j of a stage contracts
+// tile j (lanes 0-31) and tile 4+j (lanes 32-63).  The waves split the TRANSFORM ROWS: wave (h, wn) owns the positions
+// xi = 2h, 2h+1 (all four nu) of all 64 output channels (the even and the odd 32) and input-channel half wn, so that no
+// two waves compute the same transform: per tile a lane builds two rows of B^T d (from patch rows h..h+2: 8 adds) and
+// their columns (8), and two rows of E' for output channels 2 l31 and 2 l31 + 1 (6 adds each) - 28 scalar adds for 16
+// MFMAs where a split by output channel (every wave all 16 positions) needs 44: the fp32 MFMA shares the vector pipe,
+// and each add beside it costs ~7 cycles.  Every accumulator sums the same products in the same order
+// as in that split, from operands built by the same expressions: the result is bit-identical to it.  A stage is 4
+// tile-iterations of 16 MFMAs; the operands of the NEXT tile are read and transformed in the shadow of the current
+// tile's MFMAs, so only the very first tile of a workgroup has nothing to hide behind.  Three LDS stages of 40 KB (8
+// tiles x (16 + 4) pixels x 64 channels); the pieces of stage s+2 are requested in tile-iterations 2 and 3 of stage s,
+// behind the single barrier per stage that makes stage s+1 visible.  The DMA addressing is scalar: a wave's two tiles
+// of a stage are wave-uniform, so their base offsets ride in soffset and the validity of a piece's pixels in a 64-bit
+// lane mask built by the scalar unit; one v_cndmask per piece puts the out-of-range voffset on the lanes of invalid
+// pixels (zero padding: image borders, odd maps, the ragged end of the chunk).  The table the workgroup builds once in
+// LDS holds one word per tile: its first output pixel and the validity of its patch rows and columns.  Epilogue:
+// G^T . G mixes all four xi rows, held by two waves - each wave hands the rows of the OTHER channel parity to its
+// partner through LDS (the ring is free by then) and finalises its own.  Output: the direct kernel's slabs
+// [split][Cout][9][Cin], summed by the shared fixed-order reduction.
 constexpr int GT8 = 8;                    // tiles per K-stage
 constexpr int XS_F = GT8 * 16 * 64;       // floats of a stage's input patches  [tile][16 px][64 ci]
 constexpr int ES_F = GT8 * 4 * 64;        // floats of a stage's dy tiles       [tile][4 px][64 co]
 constexpr int WST_F = XS_F + ES_F;        // 10240 floats = 40 KB
 constexpr int WNST = 3;
-constexpr int WG_MAX_CHUNK = 1024;        // tiles per workgroup at most (table: 16 B per tile)
+constexpr int WG_MAX_CHUNK = 1024;        // tiles per workgroup at most (table: 4 B per tile)
+constexpr int WG_XCH_F = 4 * 8 * 16 * 64; // floats of the epilogue exchange: per wave 8 accumulators x 64 lanes (32 KB)
+constexpr size_t WG_LDS = 131072;         // bytes: the ring + the largest table, or the exchange
+static_assert((size_t)WNST * WST_F * 4 + (size_t)WG_MAX_CHUNK * 4 <= WG_LDS && (size_t)WG_XCH_F * 4 <= WG_LDS, "LDS");
 
 struct WinoWgArgs {
   const float* in;
@@ -592,20 +606,34 @@ struct WinoWgArgs {
   unsigned long long* stamps;  // diagnostics (tools/gpu_wino_phases.py --wgrad), null in every product launch
 };
 
+#if defined(__HIP_DEVICE_COMPILE__)
+// bit q of m (wave-uniform) -> lanes 16q .. 16q+15: the DMA lanes of pixel column q (patch) or output pixel q (dy)
+__device__ __forceinline__ unsigned long long wg_lanes16(unsigned m) {
+  const unsigned lo = ((m & 1u) ? 0x0000ffffu : 0u) | ((m & 2u) ? 0xffff0000u : 0u);
+  const unsigned hi = ((m & 4u) ? 0x0000ffffu : 0u) | ((m & 8u) ? 0xffff0000u : 0u);
+  return (unsigned long long)hi << 32 | lo;
+}
+// per lane: mask bit of the lane ? x : y - one VALU, the mask read from an SGPR pair
+__device__ __forceinline__ unsigned wg_sel(unsigned long long mask, unsigned x, unsigned y) {
+  unsigned r;
+  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(y), "v"(x), "s"(mask));
+  return r;
+}
+#endif
+
 __global__ void __launch_bounds__(256)
 conv3x3_wgrad_wino_kernel(WinoWgArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  typedef int i32x4 __attribute__((ext_vector_type(4)));
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  i32x4* tab = reinterpret_cast<i32x4*>(smem + WNST * WST_F);
+  unsigned* tab = reinterpret_cast<unsigned*>(smem + WNST * WST_F);
   const unsigned long long t_entry = a.stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;   // diagnostics only
   unsigned long long t_table = 0, t_first = 0, t_loop = 0, c_loop = 0;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, half = lane >> 5;
-  const int wm = wave >> 1, wn = wave & 1;
+  const int wn = wave & 1;
   const int ntile = a.tilesCo * a.tilesCi;
   const int split = blockIdx.x / ntile, tl = blockIdx.x - split * ntile;
   const int tile_co = tl / a.tilesCi, tile_ci = tl - tile_co * a.tilesCi;
@@ -616,26 +644,21 @@ conv3x3_wgrad_wino_kernel(WinoWgArgs a) {
   const int tpi = a.th * a.tw;
   const int neg = (a.W + 1) * a.Cin;   // the input descriptor starts (W+1) pixels before the tensor: patch row / column -1
 
-  // ---- the tile table: {byte offset of patch pixel (0,0) from the descriptor base, byte offset of output pixel (0,0),
-  // validity of the 16 patch pixels, validity of the 4 output pixels}
+  // ---- the tile table: per tile {index of its output pixel (0,0) (< 2^23) | validity of the 4 patch columns (bits 4-7)
+  // and rows (bits 0-3)}; the output pixels are patch rows / columns 1 and 2, a tile past the chunk's end is all invalid
   for (int i = tid; i < ns * GT8; i += 256) {
     const int T = T_lo + i;
-    i32x4 e = {0, 0, 0, 0};
+    unsigned e = 0;
     if (T < T_hi) {
       const int b = T / tpi, rem = T - b * tpi;
       const int ty = rem / a.tw, tx = rem - ty * a.tw;
-      e[0] = (((b * a.H + 2 * ty - 1) * a.W + 2 * tx - 1) * a.Cin + neg) * 4;
-      e[1] = (((b * a.H + 2 * ty) * a.W + 2 * tx) * a.Cout) * 4;
-      int m16 = 0, m4 = 0;
+      unsigned rows = 0, cols = 0;
 #pragma unroll
-      for (int p = 0; p < 16; ++p) {
-        const int ih = 2 * ty - 1 + (p >> 2), iw = 2 * tx - 1 + (p & 3);
-        if ((unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W) m16 |= 1 << p;
+      for (int p = 0; p < 4; ++p) {
+        if ((unsigned)(2 * ty - 1 + p) < (unsigned)a.H) rows |= 1u << p;
+        if ((unsigned)(2 * tx - 1 + p) < (unsigned)a.W) cols |= 1u << p;
       }
-#pragma unroll
-      for (int p = 0; p < 4; ++p)
-        if (2 * ty + (p >> 1) < a.H && 2 * tx + (p & 1) < a.W) m4 |= 1 << p;
-      e[2] = m16; e[3] = m4;
+      e = (unsigned)((b * a.H + 2 * ty) * a.W + 2 * tx) << 8 | cols << 4 | rows;
     }
     tab[i] = e;
   }
@@ -645,184 +668,232 @@ conv3x3_wgrad_wino_kernel(WinoWgArgs a) {
   const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in) - neg, 0,
                                                          (int)(((int64_t)a.M * a.Cin + 2 * neg) * 4), 0x00020000);
   const auto rsrc_dy = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dy), 0, (int)((int64_t)a.M * a.Cout * 4), 0x00020000);
-  constexpr unsigned OOB = 0x80000000u;
-  // DMA lane: pixel-row q = lane / 16 of the piece (patch column / output pixel), channels 4 (lane % 16) .. +3
+  // DMA lane: pixel column q = lane / 16 of the piece (patch column / output pixel), channels 4 (lane % 16) .. +3;
+  // the patch row and the tile are in soffset
   const int q = lane >> 4, c16 = lane & 15;
-  unsigned x_lane[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) x_lane[r] = (unsigned)(((r * a.W + q) * a.Cin + ci0 + c16 * 4) * 4);
+  const unsigned x_lane = (unsigned)((q * a.Cin + ci0 + c16 * 4) * 4);
   const unsigned dy_lane = (unsigned)((((q >> 1) * a.W + (q & 1)) * a.Cout + co0 + c16 * 4) * 4);
+  const unsigned row_bytes = (unsigned)(a.W * a.Cin * 4), cin4 = (unsigned)a.Cin * 4u, cout4 = (unsigned)a.Cout * 4u;
+  unsigned oob = 0x80000000u;   // the out-of-range voffset, in a VGPR of its own (the v_cndmask operand)
+  asm volatile("" : "+v"(oob));
 
-  // piece k (0..9) of stage s into buffer buf: this wave's two tiles 2*wave, 2*wave+1 - four patch rows each (k < 8), then their dy tiles
-  auto issue_piece = [&](int k, int s, int buf) {
-    const int sc = s < ns ? s : ns - 1;   // (past the end: a redundant copy of the last stage, never read)
+  // the wave-uniform DMA state of this wave's two tiles 2*wave, 2*wave+1 of a stage, from their table entries
+  struct Pair { unsigned xb[2], rows[2], db[2]; unsigned long long cm[2], dm[2]; };
+  // (patch pixel (0,0) of the tile is (W+1) pixels before its output pixel (0,0): the input descriptor's base)
+  auto pair_of = [&](uint2 e) {
+    Pair P;
+    const unsigned w[2] = {(unsigned)__builtin_amdgcn_readfirstlane(e.x), (unsigned)__builtin_amdgcn_readfirstlane(e.y)};
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const unsigned pix = w[t] >> 8, rows = w[t] & 15u, cols = (w[t] >> 4) & 15u;
+      const unsigned r12 = (rows >> 1) & 3u, c12 = (cols >> 1) & 3u;   // output rows / columns 0, 1
+      P.xb[t] = pix * cin4;
+      P.rows[t] = rows;
+      P.cm[t] = wg_lanes16(cols);
+      P.db[t] = pix * cout4;
+      P.dm[t] = wg_lanes16(((r12 & 1u) ? c12 : 0u) | ((r12 & 2u) ? c12 << 2 : 0u));   // output pixel q = 2 row + column
+    }
+    return P;
+  };
+  auto entries = [&](int s) {   // (past the end: a redundant copy of the last stage, never read)
+    const int sc = s < ns ? s : ns - 1;
+    return *reinterpret_cast<const uint2*>(tab + sc * GT8 + 2 * wave);
+  };
+  // piece k (0..9) of a stage into buffer buf: tile 2*wave + (k >> 2), patch row k & 3 (k < 8), then the two dy tiles
+  auto issue_piece = [&](int k, const Pair& P, int buf) {
     float* Xb = smem + buf * WST_F;
     float* Eb = Xb + XS_F;
     if (k < 8) {
-      const int t = 2 * wave + (k >> 2), r = k & 3;
-      const i32x4 e = tab[sc * GT8 + t];
-      const bool ok = (e[2] >> (r * 4 + q)) & 1;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_in, (lds_ptr_t)(Xb + (t * 16 + r * 4) * 64), 16,
-                                               ok ? (unsigned)e[0] + x_lane[r] : OOB, 0, 0, 0);
+      const int t = k >> 2, r = k & 3;
+      const unsigned long long m = (P.rows[t] >> r) & 1u ? P.cm[t] : 0ull;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_in, (lds_ptr_t)(Xb + ((2 * wave + t) * 16 + r * 4) * 64), 16,
+                                               wg_sel(m, x_lane, oob), P.xb[t] + r * row_bytes, 0, 0);
     } else {
-      const int t = 2 * wave + (k - 8);
-      const i32x4 e = tab[sc * GT8 + t];
-      const bool ok = (e[3] >> q) & 1;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_dy, (lds_ptr_t)(Eb + t * 4 * 64), 16, ok ? (unsigned)e[1] + dy_lane : OOB, 0, 0, 0);
+      const int t = k - 8;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_dy, (lds_ptr_t)(Eb + (2 * wave + t) * 4 * 64), 16,
+                                               wg_sel(P.dm[t], dy_lane, oob), P.db[t], 0, 0);
     }
   };
 
-  // the same with the table entries of this wave's two tiles already in registers
-  auto issue_piece_e = [&](int k, const i32x4& e0, const i32x4& e1, int buf) {
-    float* Xb = smem + buf * WST_F;
-    float* Eb = Xb + XS_F;
-    if (k < 8) {
-      const int t = 2 * wave + (k >> 2), r = k & 3;
-      const i32x4& e = (k >> 2) ? e1 : e0;
-      const bool ok = (e[2] >> (r * 4 + q)) & 1;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_in, (lds_ptr_t)(Xb + (t * 16 + r * 4) * 64), 16,
-                                               ok ? (unsigned)e[0] + x_lane[r] : OOB, 0, 0, 0);
-    } else {
-      const int t = 2 * wave + (k - 8);
-      const i32x4& e = (k - 8) ? e1 : e0;
-      const bool ok = (e[3] >> q) & 1;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_dy, (lds_ptr_t)(Eb + t * 4 * 64), 16, ok ? (unsigned)e[1] + dy_lane : OOB, 0, 0, 0);
-    }
-  };
+  const int x_rd = wn * 32 + l31;
+  // The body for wave row pair H (wave = 2 H + wn): the transforms differ between the two (rows 0/1 of B^T d are
+  // d0 - d2, d1 + d2; rows 2/3 are d2 - d1, d1 - d3), so each has its own copy of the loop.
+  auto body = [&](auto Hc) {
+    constexpr int H = decltype(Hc)::value;
+    f32x16 acc[16];   // [c][xi - 2H][nu]: output channels 2 m + c (m the accumulator row)
+#pragma unroll
+    for (int p = 0; p < 16; ++p)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
 
-  f32x16 acc[16];
+    // operands of one tile for this lane: E'[c][xi - 2H][nu] (output channels 2 l31, 2 l31 + 1), V[xi - 2H][nu] (its
+    // input channel)
+    float Ec[16], Vc[8], En[16], Vn[8];
+    float dr[12], er[8], ern[8];   // raw values of the tile being prepared: patch rows H .. H+2, dy of both channels
+    // LDS byte addresses of this lane's raw values of tile half*4 in buffer 0 (patch row H, channel x_rd; dy channels
+    // 2 l31, +1): a buffer is one add away, a tile and a pixel are immediate offsets of the ds_read
+    typedef __attribute__((address_space(3))) const float lds_f;
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const unsigned lds0 = (unsigned)(size_t)(lds_f*)smem;
+    const unsigned rx_lane = lds0 + (unsigned)((half * 4 * 16 * 64 + 4 * H * 64 + x_rd) * 4);
+    const unsigned re_lane = lds0 + (unsigned)((XS_F + half * 4 * 4 * 64) * 4 + l31 * 8);
+    auto read_raw = [&](unsigned rx, unsigned re, int j, float (&E)[8]) {   // tile half*4 + j
 #pragma unroll
-  for (int p = 0; p < 16; ++p)
+      for (int p = 0; p < 12; ++p) dr[p] = *(lds_f*)(size_t)(rx + j * 16 * 64 * 4 + p * 256);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
-
-  // operands of one tile for this lane: E'[16] (its output channel), V[16] (its input channel)
-  float Ec[16], Vc[16], En[16], Vn[16];
-  float dr[16], er[4];   // raw values of the tile being prepared
-  const int x_rd = wn * 32 + l31, e_rd = wm * 32 + l31;
-  auto read_raw = [&](int buf, int j) {   // tile half*4 + j of the stage in buffer buf
-    const float* Xb = smem + buf * WST_F + (half * 4 + j) * 16 * 64 + x_rd;
-    const float* Eb = smem + buf * WST_F + XS_F + (half * 4 + j) * 4 * 64 + e_rd;
-#pragma unroll
-    for (int p = 0; p < 16; ++p) dr[p] = Xb[p * 64];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) er[p] = Eb[p * 64];
-  };
-  float tt[16], aa[4];
-  auto xop = [&](int k, float (&V)[16], float (&E)[16]) {   // k-th of the 44 scalar adds that turn (dr, er) into (V, E')
-    if (k < 16) {          // rows of B^T d
-      const int c = k & 3, w = k >> 2;
-      if (w == 0) tt[c] = s_sub(dr[c], dr[8 + c]);
-      else if (w == 1) tt[4 + c] = s_add(dr[4 + c], dr[8 + c]);
-      else if (w == 2) tt[8 + c] = s_sub(dr[8 + c], dr[4 + c]);
-      else tt[12 + c] = s_sub(dr[4 + c], dr[12 + c]);
-    } else if (k < 32) {   // columns: V = (B^T d) B
-      const int r = (k - 16) >> 2, w = (k - 16) & 3;
-      if (w == 0) V[4 * r] = s_sub(tt[4 * r], tt[4 * r + 2]);
-      else if (w == 1) V[4 * r + 1] = s_add(tt[4 * r + 1], tt[4 * r + 2]);
-      else if (w == 2) V[4 * r + 2] = s_sub(tt[4 * r + 2], tt[4 * r + 1]);
-      else V[4 * r + 3] = s_sub(tt[4 * r + 1], tt[4 * r + 3]);
-    } else if (k < 36) {   // rows of A' e: (e0j, e0j + e1j, e0j - e1j, e1j), j = 0, 1; er = (e00, e01, e10, e11)
-      const int j = (k - 32) & 1, w = (k - 32) >> 1;
-      if (w == 0) aa[j] = s_add(er[j], er[2 + j]);        // row 1
-      else aa[2 + j] = s_sub(er[j], er[2 + j]);           // row 2
-    } else {               // columns: E'[xi] = (a_xi0, a_xi0 + a_xi1, a_xi0 - a_xi1, a_xi1)
-      const int xi = (k - 36) >> 1, w = (k - 36) & 1;
-      const float a0 = xi == 0 ? er[0] : xi == 1 ? aa[0] : xi == 2 ? aa[2] : er[2];
-      const float a1 = xi == 0 ? er[1] : xi == 1 ? aa[1] : xi == 2 ? aa[3] : er[3];
-      if (w == 0) { E[4 * xi] = a0; E[4 * xi + 3] = a1; E[4 * xi + 1] = s_add(a0, a1); }
-      else E[4 * xi + 2] = s_sub(a0, a1);
-    }
-  };
-
-  // ---- main loop.  The raw values of tile j+2 are read at position 8 of tile-iteration j (the patch registers are free from
-  // position 7 on), nine MFMAs before their first use - the stamps put 150-200 cycles of LDS wait per tile-iteration on the
-  // reads issued at its top (tools/gpu_wino_phases.py --wgrad: 2.78 us per stage against 1.72 us of MFMA issue).  The one
-  // barrier per stage moves to the top of tile-iteration 2 (the reads of that iteration are the first into stage s+1),
-  // and stage s+2 is requested behind it, in tile-iterations 2 and 3, with its table entries read once.
-#pragma unroll
-  for (int k = 0; k < 10; ++k) issue_piece(k, 0, 0);
-#pragma unroll
-  for (int k = 0; k < 10; ++k) issue_piece(k, 1, 1);
-  asm volatile("s_waitcnt vmcnt(10)\n\ts_barrier" ::: "memory");
-  read_raw(0, 0);
-#pragma unroll
-  for (int k = 0; k < 44; ++k) xop(k, Vc, Ec);
-  read_raw(0, 1);
-  if (a.stamps) { t_first = __builtin_amdgcn_s_memrealtime(); c_loop = __builtin_amdgcn_s_memtime(); }
-  float ern[4];
-  int b0 = 0;   // buffer of stage s
-  for (int s = 0; s < ns; ++s) {
-    int b1 = b0 + 1; b1 = b1 == WNST ? 0 : b1;
-    int b2 = b1 + 1; b2 = b2 == WNST ? 0 : b2;
-    i32x4 e0 = {0, 0, 0, 0}, e1 = {0, 0, 0, 0};
-    auto tile_iter = [&](auto Jc) {
-      constexpr int J = decltype(Jc)::value;
-      if (J == 2) {
-        // stage s+1 has landed (requested a stage ago) and every wave has finished reading stage s-1, whose buffer the
-        // requests of stage s+2 overwrite
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        const int sc = s + 2 < ns ? s + 2 : ns - 1;
-        e0 = tab[sc * GT8 + 2 * wave]; e1 = tab[sc * GT8 + 2 * wave + 1];
+      for (int p = 0; p < 4; ++p) {
+        const f32x2 v = *(const __attribute__((address_space(3))) f32x2*)(size_t)(re + j * 4 * 64 * 4 + p * 256);
+        E[p] = v[0]; E[4 + p] = v[1];
       }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int p = 0; p < 16; ++p) {
-        acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ec[p], Vc[p], acc[p], 0, 0, 0);
-        if (p & 1) {   // six of the 44 adds behind every second MFMA (three behind every one: 3.5 % slower)
-#pragma unroll
-          for (int k = 0; k < 6; ++k)
-            if ((p >> 1) * 6 + k < 44) xop((p >> 1) * 6 + k, Vn, En);
-        }
-        if (p == 8) {   // raw values of tile J + 2
-          const float* Xb = smem + (J < 2 ? b0 : b1) * WST_F + (half * 4 + ((J + 2) & 3)) * 16 * 64 + x_rd;
-          const float* Eb = smem + (J < 2 ? b0 : b1) * WST_F + XS_F + (half * 4 + ((J + 2) & 3)) * 4 * 64 + e_rd;
-#pragma unroll
-          for (int i = 0; i < 16; ++i) dr[i] = Xb[i * 64];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) ern[i] = Eb[i * 64];
-        }
-        if ((J == 2 || J == 3) && p % 3 == 1 && p / 3 < 5) issue_piece_e(J == 2 ? p / 3 : 5 + p / 3, e0, e1, b2);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int p = 0; p < 16; ++p) { Ec[p] = En[p]; Vc[p] = Vn[p]; }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) er[i] = ern[i];
     };
-    tile_iter(std::integral_constant<int, 0>{});
-    tile_iter(std::integral_constant<int, 1>{});
-    tile_iter(std::integral_constant<int, 2>{});
-    tile_iter(std::integral_constant<int, 3>{});
-    b0 = b1;
-  }
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    float tt[8], aa[4];
+    auto xop = [&](int k, float (&V)[8], float (&E)[16]) {   // k-th of the 28 scalar adds that turn (dr, er) into (V, E')
+      if (k < 8) {          // the two rows of B^T d
+        const int c = k & 3, w = k >> 2;
+        if (H == 0) {
+          if (w == 0) tt[c] = s_sub(dr[c], dr[8 + c]);               // d0 - d2
+          else tt[4 + c] = s_add(dr[4 + c], dr[8 + c]);              // d1 + d2
+        } else {
+          if (w == 0) tt[c] = s_sub(dr[4 + c], dr[c]);               // d2 - d1
+          else tt[4 + c] = s_sub(dr[c], dr[8 + c]);                  // d1 - d3
+        }
+      } else if (k < 16) {  // columns: V = (B^T d) B
+        const int r = (k - 8) >> 2, w = (k - 8) & 3;
+        if (w == 0) V[4 * r] = s_sub(tt[4 * r], tt[4 * r + 2]);
+        else if (w == 1) V[4 * r + 1] = s_add(tt[4 * r + 1], tt[4 * r + 2]);
+        else if (w == 2) V[4 * r + 2] = s_sub(tt[4 * r + 2], tt[4 * r + 1]);
+        else V[4 * r + 3] = s_sub(tt[4 * r + 1], tt[4 * r + 3]);
+      } else {              // E' of output channel c2: er = (e00, e01, e10, e11); rows of A' e (e0j, e0j + e1j, e0j - e1j, e1j)
+        const int c2 = (k - 16) / 6, w = (k - 16) % 6;
+        const float* e = er + 4 * c2;
+        float* a2 = aa + 2 * c2;
+        if (w < 2) a2[w] = H == 0 ? s_add(e[w], e[2 + w]) : s_sub(e[w], e[2 + w]);   // row 1 / row 2
+        else {             // columns: E'[xi] = (a_xi0, a_xi0 + a_xi1, a_xi0 - a_xi1, a_xi1)
+          const int x = (w - 2) >> 1;   // xi - 2H
+          const float a0 = (H == 0) == (x == 0) ? e[2 * H] : a2[0];
+          const float a1 = (H == 0) == (x == 0) ? e[2 * H + 1] : a2[1];
+          float* o = E + 8 * c2 + 4 * x;
+          if ((w & 1) == 0) { o[0] = a0; o[3] = a1; o[1] = s_add(a0, a1); }
+          else o[2] = s_sub(a0, a1);
+        }
+      }
+    };
 
-  if (a.stamps) { t_loop = __builtin_amdgcn_s_memrealtime(); c_loop = __builtin_amdgcn_s_memtime() - c_loop; }
+    // ---- main loop.  The raw values of tile j+2 are read at position 8 of tile-iteration j (the patch registers are free
+    // by then), eight MFMAs before their first use.  The one barrier per stage sits at the top of tile-iteration 2 (the
+    // reads of that iteration are the first into stage s+1), and stage s+2 is requested behind it, in tile-iterations 2
+    // and 3, with its table entries read once.
+    {
+      const Pair P0 = pair_of(entries(0));
+#pragma unroll
+      for (int k = 0; k < 10; ++k) issue_piece(k, P0, 0);
+      const Pair P1 = pair_of(entries(1));
+#pragma unroll
+      for (int k = 0; k < 10; ++k) issue_piece(k, P1, 1);
+    }
+    asm volatile("s_waitcnt vmcnt(10)\n\ts_barrier" ::: "memory");
+    read_raw(rx_lane, re_lane, 0, er);
+#pragma unroll
+    for (int k = 0; k < 28; ++k) xop(k, Vc, Ec);
+    read_raw(rx_lane, re_lane, 1, er);
+    if (a.stamps) { t_first = __builtin_amdgcn_s_memrealtime(); c_loop = __builtin_amdgcn_s_memtime(); }
+    unsigned rx0 = rx_lane, re0 = re_lane;   // the addresses in the buffers of stages s and s+1 (rx1, re1)
+    int b0 = 0;   // buffer of stage s
+    for (int s = 0; s < ns; ++s) {
+      int b1 = b0 + 1; b1 = b1 == WNST ? 0 : b1;
+      int b2 = b1 + 1; b2 = b2 == WNST ? 0 : b2;
+      unsigned rx1 = rx_lane + (unsigned)(b1 * WST_F * 4), re1 = re_lane + (unsigned)(b1 * WST_F * 4);
+      asm volatile("" : "+v"(rx1), "+v"(re1));
+      uint2 e2 = {0u, 0u};
+      Pair P;
+      auto tile_iter = [&](auto Jc) {
+        constexpr int J = decltype(Jc)::value;
+        if (J == 2) {
+          // stage s+1 has landed (requested a stage ago) and every wave has finished reading stage s-1, whose buffer the
+          // requests of stage s+2 overwrite
+          asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+          e2 = entries(s + 2);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int p = 0; p < 16; ++p) {   // MFMA p: output channels 2 m + (p >> 3), position 2H + (p >> 2 & 1), nu = p & 3
+          acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ec[p], Vc[p & 7], acc[p], 0, 0, 0);
+          if (p & 1) {   // four of the 28 adds behind every second MFMA
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if ((p >> 1) * 4 + k < 28) xop((p >> 1) * 4 + k, Vn, En);
+          }
+          if (p == 8) read_raw(J < 2 ? rx0 : rx1, J < 2 ? re0 : re1, (J + 2) & 3, ern);   // raw values of tile J + 2
+          if (J == 2 && p == 1) P = pair_of(e2);
+          if ((J == 2 || J == 3) && p % 3 == 1 && p / 3 < 5) issue_piece(J == 2 ? p / 3 : 5 + p / 3, P, b2);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int p = 0; p < 16; ++p) Ec[p] = En[p];
+#pragma unroll
+        for (int p = 0; p < 8; ++p) { Vc[p] = Vn[p]; er[p] = ern[p]; }
+      };
+      tile_iter(std::integral_constant<int, 0>{});
+      tile_iter(std::integral_constant<int, 1>{});
+      tile_iter(std::integral_constant<int, 2>{});
+      tile_iter(std::integral_constant<int, 3>{});
+      b0 = b1; rx0 = rx1; re0 = re1;
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the ring is free
 
-  // ---- epilogue: dW = G^T (s_xi s_nu M') G per (co, ci), to this split's slab [Cout][9][Cin]
-  float* slab = a.slabs + (size_t)split * a.Cout * 9 * a.Cin;
-  const int ci = ci0 + wn * 32 + l31;
+    if (a.stamps) { t_loop = __builtin_amdgcn_s_memrealtime(); c_loop = __builtin_amdgcn_s_memtime() - c_loop; }
+
+    // ---- epilogue: this wave finalises output channels 2 m + H; the partner (1 - H, wn) holds its rows xi = 2 (1-H), +1.
+    // Exchange: [receiving wave][accumulator][register quad][lane][4] (16-byte lane runs: conflict-free)
+    {
+      f32x4* xo = reinterpret_cast<f32x4*>(smem) + ((1 - H) * 2 + wn) * 2048 + lane;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int co = co0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-    float R[3][4];
+      for (int p = 0; p < 8; ++p)
 #pragma unroll
-    for (int nu = 0; nu < 4; ++nu) {
-      const float sg = nu == 3 ? -1.f : 1.f;
-      const float m0 = sg * acc[0 + nu][r], m1 = sg * acc[4 + nu][r], m2 = sg * acc[8 + nu][r], m3 = -sg * acc[12 + nu][r];
-      R[0][nu] = m0 + 0.5f * (m1 + m2);
-      R[1][nu] = 0.5f * (m1 - m2);
-      R[2][nu] = 0.5f * (m1 + m2) + m3;
+        for (int r4 = 0; r4 < 4; ++r4) {
+          const f32x16& v = acc[8 * (1 - H) + p];
+          xo[(p * 4 + r4) * 64] = f32x4{v[4 * r4], v[4 * r4 + 1], v[4 * r4 + 2], v[4 * r4 + 3]};
+        }
     }
+    __syncthreads();
+    // dW = G^T (s_xi s_nu M') G per (co, ci), to this split's slab [Cout][9][Cin]
+    float* slab = a.slabs + (size_t)split * a.Cout * 9 * a.Cin;
+    const int ci = ci0 + wn * 32 + l31;
+    const f32x4* xin = reinterpret_cast<const f32x4*>(smem) + wave * 2048 + lane;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      float* dst = slab + ((size_t)co * 9 + 3 * k) * a.Cin + ci;
-      dst[0] = R[k][0] + 0.5f * (R[k][1] + R[k][2]);
-      dst[a.Cin] = 0.5f * (R[k][1] - R[k][2]);
-      dst[2 * a.Cin] = 0.5f * (R[k][1] + R[k][2]) + R[k][3];
+    for (int r4 = 0; r4 < 4; ++r4) {
+      f32x4 pv[8];
+#pragma unroll
+      for (int p = 0; p < 8; ++p) pv[p] = xin[(p * 4 + r4) * 64];
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const int r = 4 * r4 + rr;
+        const int co = co0 + 2 * ((r & 3) + 8 * (r >> 2) + 4 * half) + H;
+        auto M = [&](int x, int nu) {   // accumulator of position (x, nu), output channel co
+          return (x >> 1) == H ? acc[8 * H + 4 * (x & 1) + nu][r] : pv[4 * (x & 1) + nu][rr];
+        };
+        float R[3][4];
+#pragma unroll
+        for (int nu = 0; nu < 4; ++nu) {
+          const float sg = nu == 3 ? -1.f : 1.f;
+          const float m0 = sg * M(0, nu), m1 = sg * M(1, nu), m2 = sg * M(2, nu), m3 = -sg * M(3, nu);
+          R[0][nu] = m0 + 0.5f * (m1 + m2);
+          R[1][nu] = 0.5f * (m1 - m2);
+          R[2][nu] = 0.5f * (m1 + m2) + m3;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          float* dst = slab + ((size_t)co * 9 + 3 * k) * a.Cin + ci;
+          dst[0] = R[k][0] + 0.5f * (R[k][1] + R[k][2]);
+          dst[a.Cin] = 0.5f * (R[k][1] - R[k][2]);
+          dst[2 * a.Cin] = 0.5f * (R[k][1] + R[k][2]) + R[k][3];
+        }
+      }
     }
-  }
+  };
+  if (wave >> 1) body(std::integral_constant<int, 1>{});
+  else body(std::integral_constant<int, 0>{});
+
   if (a.stamps && tid == 0) {   // 10-ns ticks: entry, table built, first tile prepared, loop end, epilogue end; loop cycles; ids
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     unsigned long long* o = a.stamps + 8 * (size_t)blockIdx.x;
@@ -869,19 +940,17 @@ extern "C" int tdx_conv3x3_wgrad_wino(const float* in, const float* dy, float* d
   a.M = (int)M;
   a.tilesCo = cout / 64; a.tilesCi = cin / 64;
   const int splits = wino_wgrad_plan(a.NT, cin, cout, &a.chunk);
-  const size_t lds = (size_t)WNST * WST_F * sizeof(float) + (size_t)a.chunk * 16;
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wgrad_wino_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)((size_t)WNST * WST_F * sizeof(float) + (size_t)WG_MAX_CHUNK * 16));
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS);
     if (e != hipSuccess) return (int)e;
     attr_set = true;
   }
   a.stamps = g_tdx_probe_stamp == 3 && g_tdx_diag_buffer && (size_t)splits * a.tilesCo * a.tilesCi * 64 <= g_tdx_diag_bytes
                  ? reinterpret_cast<unsigned long long*>(g_tdx_diag_buffer) : nullptr;   // diagnostic knob conv_stamp = 3
   const dim3 grid(splits * a.tilesCo * a.tilesCi);
-  conv3x3_wgrad_wino_kernel<<<grid, 256, lds, to_stream(stream)>>>(a);
+  conv3x3_wgrad_wino_kernel<<<grid, 256, WG_LDS, to_stream(stream)>>>(a);
   TDX_CHECK_LAUNCH();
   return 0;
 }
