@@ -204,7 +204,10 @@ int tdx_conv3x3_fwd_wino_infer(const float* in, const float* u, const float* bia
                                int cin, int cout, const float* out_scale, const float* out_shift, float* scratch,
                                size_t scratch_floats, tdx_stream_t stream);
 /* 1 when a training step of the UNets at batch B runs this layer's forward (role 0) / input gradient (role 1) on the
- * Winograd kernel (tuning knobs "wino", "wino_min_wgs"), 0: on the direct kernels - what bench.py's roofline leg times. */
+ * Winograd kernel (tuning knobs "wino", "wino_min_wgs"), 0: on the direct kernels - what bench.py's roofline leg times.
+ * Those launches run the main loop whose waves split the transform rows (knob "wino_rows", default 1; 0: the loop whose
+ * waves split the output channels; "wino_rows_min_stages": only launches of at least that many 8-channel K-stages take
+ * the row split) - bit-identical results either way. */
 int tdx_conv3x3_train_algo(int B, int H, int W, int cin, int cout, int role);
 /* 1 when a sampling (INFER-mode) forward of B samples runs this layer on tdx_conv3x3_fwd_wino_infer (tuning knobs
  * "wino_infer", "wino_infer_min_units", "infer_ring"), 0: on the direct kernels (split-K tdx_conv3x3_fwd_splitk). */

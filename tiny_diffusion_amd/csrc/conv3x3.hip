@@ -968,6 +968,8 @@ extern "C" int tdx_tune_set(const char* key, int value) {
   if (!strcmp(key, "wino_wgrad_min_tiles")) { g_tdx_wino_wgrad_min_tiles = value > 0 ? value : 1024; return 0; }
   if (!strcmp(key, "wino_wgrad_target")) { g_tdx_wino_wgrad_target = value > 0 ? value : 512; return 0; }
   if (!strcmp(key, "wino_min_wgs")) { g_tdx_wino_min_wgs = value > 0 ? value : 1; return 0; }
+  if (!strcmp(key, "wino_rows")) { g_tdx_wino_rows = value != 0; return 0; }
+  if (!strcmp(key, "wino_rows_min_stages")) { g_tdx_wino_rows_min_stages = value > 0 ? value : 16; return 0; }
   if (!strcmp(key, "infer_ring")) { g_tdx_infer_ring = value != 0; return 0; }
   if (!strcmp(key, "infer_stages")) { g_infer_stages = value == 3 ? 3 : 4; return 0; }
   if (!strcmp(key, "infer_splits")) { g_infer_splits = value > 0 ? value : 0; return 0; }

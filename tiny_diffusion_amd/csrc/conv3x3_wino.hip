@@ -14,12 +14,13 @@
 // Everything is fused into one kernel - a transformed-input tensor in HBM would be 4x the input, and this path is
 // worth nothing if it becomes HBM-bound:
 //   * a workgroup owns 64 consecutive tiles (256 output pixels) x 64 output channels; four waves, each 32 tiles x 32
-//     channels x ALL 16 positions = sixteen 32x32 accumulators = 256 accumulator registers per lane (one wave per SIMD);
+//     channels x ALL 16 positions (the inference launches; the training launches split the waves by transform row
+//     instead, see the kernel) = sixteen 32x32 accumulators = 256 accumulator registers per lane (one wave per SIMD);
 //   * per stage of 8 input channels the raw 4x4 patches of the 64 tiles and the 16 x 64 x 8 transformed weights go
 //     global -> LDS by DMA (32 KB + 32 KB, double-buffered), in exactly the order the fragment reads want them
 //     ([pixel | position][tile | channel][k-half][4 floats]: every ds_read_b128 of a wave is one contiguous KiB);
-//   * each lane transforms the patch of ITS tile in registers (B^T d B on four channels at a time: 32 packed adds for
-//     64 MFMAs) - the transformed input never exists in memory;
+//   * each lane transforms the patch of ITS tile in registers (B^T d B on four channels at a time: 128 scalar adds per
+//     64 MFMAs, 64 in the row split) - the transformed input never exists in memory;
 //   * the weights are transformed once per step by the pack kernel (U = G g G^T, tile-major so that a stage is one
 //     contiguous 32 KB piece), for the forward and - flipped and transposed - for the input gradient;
 //   * the epilogue applies A^T . A to the sixteen accumulators of a (tile, channel) - lane-local - then bias and the
@@ -67,9 +68,14 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // and a wave instruction four whole 256-byte rows: 16 buffer stores per lane instead of 64 scalar ones, and no integer
 // division per accumulator row - measured with the workgroup stamps (tools/gpu_wino_phases.py), the scalar form cost
 // 8-9 us of a 31-50 us workgroup.
-template <int EPI>
+// XH >= 0 (the row split): this wave holds channel half wn = XH of positions 8 XH .. 8 XH + 7 in acc; the other eight
+// positions' registers 4 j .. 4 j + 3 are at xin[(p * 4 + j) * 64] (p = position - 8 (1 - XH)) in LDS, read four
+// registers at a time when the row loop needs them - held in registers all at once, they spill - and the output image,
+// which overlaps them, is written once every wave has read its own.
+template <int EPI, int XH = -1>
 __device__ __forceinline__ void wino_epilogue(const WinoArgs& a, float* out, const float* bias, f32x16 (&acc)[16], float* smem,
-                                              int tblk, int n0, int wm, int wn, int l31, int half, int tid) {
+                                              int tblk, int n0, int wm, int wn, int l31, int half, int tid,
+                                              const f32x4* xin = nullptr) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const unsigned* tab = reinterpret_cast<const unsigned*>(smem + TAB_OFF);
   const int cl = wn * 32 + l31, col = n0 + cl;
@@ -80,13 +86,19 @@ __device__ __forceinline__ void wino_epilogue(const WinoArgs& a, float* out, con
   float* ot = smem;   // [256 pixels = 64 tiles x 4][OLD]
   // the transformed outputs replace the accumulators of positions 0, 1, 4, 5 (Y00, Y01, Y10, Y11), so that the centred
   // second pass of the statistics can read them again
+  f32x4 pv[8];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
+    if (XH >= 0 && (r & 3) == 0) {
+#pragma unroll
+      for (int p = 0; p < 8; ++p) pv[p] = xin[(p * 4 + (r >> 2)) * 64];
+    }
+    auto M = [&](int p) { return XH >= 0 && (p >> 3) != XH ? pv[p & 7][r & 3] : acc[p][r]; };
     float s0[4], s1[4];
 #pragma unroll
     for (int nu = 0; nu < 4; ++nu) {
-      s0[nu] = acc[0 + nu][r] + acc[4 + nu][r] + acc[8 + nu][r];
-      s1[nu] = acc[4 + nu][r] - acc[8 + nu][r] - acc[12 + nu][r];
+      s0[nu] = M(0 + nu) + M(4 + nu) + M(8 + nu);
+      s1[nu] = M(4 + nu) - M(8 + nu) - M(12 + nu);
     }
     float y[4] = {s0[0] + s0[1] + s0[2], s0[1] - s0[2] - s0[3], s1[0] + s1[1] + s1[2], s1[1] - s1[2] - s1[3]};
     const int tl = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
@@ -96,7 +108,7 @@ __device__ __forceinline__ void wino_epilogue(const WinoArgs& a, float* out, con
       float val = y[q] + bv;
       if (EPI == EPI_BNRELU) val = fmaxf(fmaf(val, osc, osh), 0.f);
       const bool ok = (m >> q) & 1u;
-      ot[(tl * 4 + q) * OLD + cl] = val;
+      if (XH < 0) ot[(tl * 4 + q) * OLD + cl] = val;
       csum += ok ? val : 0.f;
       cnt += ok ? 1.f : 0.f;
       y[q] = ok ? val : 0.f;
@@ -106,6 +118,15 @@ __device__ __forceinline__ void wino_epilogue(const WinoArgs& a, float* out, con
     acc[3][r] = (m & 2u) ? 1.f : 0.f;
     acc[6][r] = (m & 4u) ? 1.f : 0.f;
     acc[7][r] = (m & 8u) ? 1.f : 0.f;
+  }
+  if (XH >= 0) {   // (the image of the stores only: a pixel that is not valid - y = 0 here - is never stored)
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int tl = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+      ot[(tl * 4 + 0) * OLD + cl] = acc[0][r]; ot[(tl * 4 + 1) * OLD + cl] = acc[1][r];
+      ot[(tl * 4 + 2) * OLD + cl] = acc[4][r]; ot[(tl * 4 + 3) * OLD + cl] = acc[5][r];
+    }
   }
   __syncthreads();
   {
@@ -182,10 +203,13 @@ __device__ __forceinline__ int div_rcp(int n, int d, float r, int* rem) {
   return q;
 }
 
-template <int EPI, bool SPLITK>
+// ROWS (training launches, knob wino_rows): the waves split the TRANSFORM ROWS instead of the output channels - see the
+// main loop below.
+template <int EPI, bool SPLITK, bool ROWS>
 __global__ void __launch_bounds__(256)
 conv3x3_wino_kernel(WinoArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  static_assert(!ROWS || (!SPLITK && EPI != EPI_BNRELU), "the row split serves the training launches only");
   typedef __attribute__((address_space(3))) void* lds_ptr_t;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const unsigned long long t_entry = a.stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;   // diagnostics only
@@ -193,7 +217,8 @@ conv3x3_wino_kernel(WinoArgs a) {
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, half = lane >> 5;
-  const int wm = wave >> 1, wn = wave & 1;
+  // tile group wm (tiles 32 wm .. 32 wm + 31); channel half wn (channel split) or transform rows 2 wn, 2 wn + 1 (ROWS)
+  const int wm = ROWS ? wave & 1 : wave >> 1, wn = ROWS ? wave >> 1 : wave & 1;
   // workgroup id -> (tile block, channel block): the channel blocks of one tile block (same input patches) get ids that
   // differ by multiples of 8 inside a group of 8 * tilesN consecutive ids: same XCD, same L2 (as conv3x3.hip)
   const int xb = blockIdx.x / (8 * a.tilesN), xr = blockIdx.x % (8 * a.tilesN);
@@ -276,113 +301,246 @@ conv3x3_wino_kernel(WinoArgs a) {
 #pragma unroll
   for (int i = 0; i < 16; ++i) piece(i, 0, 0);
   unsigned long long t_issued = 0, t_landed = 0, t_loop = 0, c_loop = 0;
-  f32x4 d[16], v[16], t1[4], t2[4], t3[4];
-  // f32x4 operation q (0..23) of the transform behind its first row: rows 1, 2, 3 of t (q % 8 < 4) and of V (q % 8 >= 4)
-  auto xop = [&](int q) {
-    const int r = q >> 3, k = q & 7, c = k & 3;
-    if (k < 4) {
-      if (r == 0) t1[c] = add4(d[4 + c], d[8 + c]);
-      else if (r == 1) t2[c] = sub4(d[8 + c], d[4 + c]);
-      else t3[c] = sub4(d[4 + c], d[12 + c]);
-    } else {
-      f32x4(&t)[4] = r == 0 ? t1 : r == 1 ? t2 : t3;
-      f32x4& o = v[4 * (r + 1) + c];
-      if (c == 0) o = sub4(t[0], t[2]);
-      else if (c == 1) o = add4(t[1], t[2]);
-      else if (c == 2) o = sub4(t[2], t[1]);
-      else o = sub4(t[1], t[3]);
-    }
-  };
-  {
-    // ---- the stage boundary of the LDS ring sits at position 12 of the MFMA stage.  With the boundary at the barrier
-    // the workgroup stamps (tools/gpu_wino_phases.py) put a stage at 2.35-2.7 us against 1.73 us of MFMA issue: after the
-    // barrier every wave - alone on its SIMD - read eighteen fragments and transformed a row before its first MFMA, and the
-    // last DMA piece of the next stage was requested 256 cycles before the barrier that waited for it.  Here the weight fragments of
-    // positions 12-15 are in registers by position 11, so the ONE barrier per stage stands between MFMAs (12,0) and
-    // (12,1): behind it the next stage's patch rows and first two weight fragments are read and its first transform row
-    // computed in the shadow of positions 12-15, and the buffer just released takes the weights (pieces 0-7) of stage
-    // s+2 at once; its patches (pieces 8-15) follow at positions 0-7 of stage s+1 - four positions before the barrier
-    // that needs them.
+  if constexpr (ROWS) {
+    // ---- the row split.  Wave (h, wm) = wave 2 h + wm owns tiles 32 wm .. 32 wm + 31, the positions xi = 2h, 2h+1 (all
+    // four nu) and ALL 64 output channels as two 32-wide column blocks: still sixteen 32x32 accumulators, acc[2 pp + c]
+    // for local position pp = 4 (xi - 2h) + nu and channel half c.  A lane builds only rows 2h, 2h+1 of B^T d from its
+    // patch rows h .. h+2 (12 of the 16 pixel reads) and their columns: 64 scalar adds per 64 MFMAs where the channel
+    // split builds all four rows in both waves of a tile group (128).  Every V value feeds two MFMAs (one per channel
+    // half), and a stage still reads 16 weight fragments: group g = 2 pp + c of the wave's 16 MFMA groups takes the one
+    // at position 8h + pp, channel half c - 256 floats after group g-1's, so the wave's fragments are one contiguous 8 KB.
+    // Same operand expressions, lane -> (tile, k) map and k order as the channel split: every accumulator sums the
+    // same products in the same order, and the result is bit-identical to it.  The stage keeps that loop's shape - one
+    // barrier, at group 12, between MFMAs (12,0) and (12,1); behind it the next stage's patch rows are read and its row
+    // 2h transformed in the shadow of groups 12-15 - with the fillers re-placed for the new counts: row 2h+1 of the
+    // stage (8 f32x4 operations) in groups 0-3, two per gap, ready for its first use in group 8.
+    // Epilogue: A^T . A mixes all four xi rows.  Wave (h, wm) keeps channel half h and hands its 8 accumulators of half
+    // 1-h to wave (1-h, wm) through the free ring (32 KB per wave, 128 KB = the two stages: the tile table stays); the
+    // shared epilogue then does what wave (wm, wn = h) of the channel split did, with the same arithmetic, reading the
+    // received rows from LDS as it goes (XH).
+    static_assert(4 * 8 * 16 * 64 == 2 * STAGE, "the exchange fills the ring");
 #pragma unroll
     for (int i = 0; i < 8; ++i) piece(i, 1, 1);
     if (a.stamps) t_issued = __builtin_amdgcn_s_memrealtime();
     asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // stage 0 has landed (loads return in order)
     if (a.stamps) { t_landed = __builtin_amdgcn_s_memrealtime(); c_loop = __builtin_amdgcn_s_memtime(); }
-    f32x4 bq[5], nbq[2];
-    {
-      const float* Ab = smem + wm * 256 + l31 * 8 + half * 4;
-      const float* Bb = smem + A_ST + wn * 256 + l31 * 8 + half * 4;
+    auto body = [&](auto Hc) {
+      constexpr int H = decltype(Hc)::value;
+      // d: patch rows H .. H+2 (local rows 0-2) x 4 pixels; v: V rows 2H (0-3) and 2H+1 (4-7); t: one row of B^T d
+      f32x4 d[12], v[8], t[4], bq[5], nbq[2];
+      const int lofs = wm * 256 + l31 * 8 + half * 4;
+      // column c of row 2H + x of B^T d, by the channel split's expressions: d0 - d2, d1 + d2 | d2 - d1, d1 - d3
+      auto trow = [&](int x, int c) {
+        if (H == 0) t[c] = x == 0 ? sub4(d[c], d[8 + c]) : add4(d[4 + c], d[8 + c]);
+        else t[c] = x == 0 ? sub4(d[4 + c], d[c]) : sub4(d[c], d[8 + c]);
+      };
+      auto vcol = [&](int x, int c) {   // V[2H + x][c] = ((B^T d) B)[.][c]
+        f32x4& o = v[4 * x + c];
+        if (c == 0) o = sub4(t[0], t[2]);
+        else if (c == 1) o = add4(t[1], t[2]);
+        else if (c == 2) o = sub4(t[2], t[1]);
+        else o = sub4(t[1], t[3]);
+      };
+      // the local rows that row 2H reads first (0 and 2 | 0 and 1), then the remaining one
+      constexpr int RA = 0, RB = H == 0 ? 2 : 1, RC = H == 0 ? 1 : 2;
+      {
+        const float* Ab = smem + 4 * H * 512 + lofs;
+        const float* Bb = smem + A_ST + 8 * H * 512 + l31 * 8 + half * 4;
 #pragma unroll
-      for (int c = 0; c < 4; ++c) { d[c] = *reinterpret_cast<const f32x4*>(Ab + c * 512); d[8 + c] = *reinterpret_cast<const f32x4*>(Ab + (8 + c) * 512); }
-      nbq[0] = *reinterpret_cast<const f32x4*>(Bb);
-      nbq[1] = *reinterpret_cast<const f32x4*>(Bb + 512);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) { d[4 + c] = *reinterpret_cast<const f32x4*>(Ab + (4 + c) * 512); d[12 + c] = *reinterpret_cast<const f32x4*>(Ab + (12 + c) * 512); }
-      f32x4 t0[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) t0[c] = sub4(d[c], d[8 + c]);
-      v[0] = sub4(t0[0], t0[2]); v[1] = add4(t0[1], t0[2]); v[2] = sub4(t0[2], t0[1]); v[3] = sub4(t0[1], t0[3]);
-    }
-    auto stage = [&](auto first_c, int s) {
-      constexpr bool FIRST = decltype(first_c)::value;
-      const int cb = s & 1;
-      const float* Bb = smem + cb * STAGE + A_ST + wn * 256 + l31 * 8 + half * 4;
-      const float* An = smem + (cb ^ 1) * STAGE + wm * 256 + l31 * 8 + half * 4;     // the next stage's
-      const float* Bn = smem + (cb ^ 1) * STAGE + A_ST + wn * 256 + l31 * 8 + half * 4;
-      bq[0] = nbq[0]; bq[1] = nbq[1];
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int p = 0; p < 16; ++p) {
-        const int cur = p % 5;
-        if (FIRST) acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[p][0], bq[cur][0], zero16, 0, 0, 0);
-        else acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[p][0], bq[cur][0], acc[p], 0, 0, 0);
-        if (p < 8) piece(8 + p, cb ^ 1, s + 1);
-        if (p == 10) bq[4] = *reinterpret_cast<const f32x4*>(Bb + 14 * 512);
-        if (p == 11) bq[0] = *reinterpret_cast<const f32x4*>(Bb + 15 * 512);
-        if (p == 12) {
-          // stage s+1 has landed and every wave is done reading the buffer of stage s
-          asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#pragma unroll
-          for (int c = 0; c < 4; ++c) { d[c] = *reinterpret_cast<const f32x4*>(An + c * 512); d[8 + c] = *reinterpret_cast<const f32x4*>(An + (8 + c) * 512); }
+        for (int c = 0; c < 4; ++c) {
+          d[4 * RA + c] = *reinterpret_cast<const f32x4*>(Ab + (4 * RA + c) * 512);
+          d[4 * RB + c] = *reinterpret_cast<const f32x4*>(Ab + (4 * RB + c) * 512);
         }
-        if (p == 13) {
+        nbq[0] = *reinterpret_cast<const f32x4*>(Bb);
+        nbq[1] = *reinterpret_cast<const f32x4*>(Bb + 256);
 #pragma unroll
-          for (int c = 0; c < 4; ++c) d[4 + c] = *reinterpret_cast<const f32x4*>(An + (4 + c) * 512);
-        }
-        if (p == 14) {
+        for (int c = 0; c < 4; ++c) d[4 * RC + c] = *reinterpret_cast<const f32x4*>(Ab + (4 * RC + c) * 512);
 #pragma unroll
-          for (int c = 0; c < 4; ++c) t1[c] = sub4(d[c], d[8 + c]);    // (t1 is free: the row-0 temporaries of the next stage)
-        }
-        if (p == 15) { v[2] = sub4(t1[2], t1[1]); v[3] = sub4(t1[1], t1[3]); }
-        __builtin_amdgcn_sched_barrier(0);
-        acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[p][1], bq[cur][1], acc[p], 0, 0, 0);
-        if (p < 12) { xop(2 * p); xop(2 * p + 1); }   // (both in one gap: 2.5 % faster than one per gap)
-        else piece(2 * (p - 12), cb, s + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[p][2], bq[cur][2], acc[p], 0, 0, 0);
-        if (p < 12) bq[(p + 2) % 5] = *reinterpret_cast<const f32x4*>(Bb + (p + 2) * 512);
-        if (p == 12) { nbq[0] = *reinterpret_cast<const f32x4*>(Bn); nbq[1] = *reinterpret_cast<const f32x4*>(Bn + 512); }
-        if (p == 13) {
+        for (int c = 0; c < 4; ++c) trow(0, c);
 #pragma unroll
-          for (int c = 0; c < 4; ++c) d[12 + c] = *reinterpret_cast<const f32x4*>(An + (12 + c) * 512);
+        for (int c = 0; c < 4; ++c) vcol(0, c);
+      }
+      auto stage = [&](auto first_c, int s) {
+        constexpr bool FIRST = decltype(first_c)::value;
+        const int cb = s & 1;
+        const float* Bb = smem + cb * STAGE + A_ST + 8 * H * 512 + l31 * 8 + half * 4;   // fragment of group g: Bb + 256 g
+        const float* An = smem + (cb ^ 1) * STAGE + 4 * H * 512 + lofs;                 // the next stage's
+        const float* Bn = smem + (cb ^ 1) * STAGE + A_ST + 8 * H * 512 + l31 * 8 + half * 4;
+        bq[0] = nbq[0]; bq[1] = nbq[1];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+          const int cur = g % 5, pp = g >> 1, ai = 8 * (g & 1) + pp;
+          if (FIRST) acc[ai] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[pp][0], bq[cur][0], zero16, 0, 0, 0);
+          else acc[ai] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[pp][0], bq[cur][0], acc[ai], 0, 0, 0);
+          if (g < 8) piece(8 + g, cb ^ 1, s + 1);
+          if (g == 10) bq[4] = *reinterpret_cast<const f32x4*>(Bb + 14 * 256);
+          if (g == 11) bq[0] = *reinterpret_cast<const f32x4*>(Bb + 15 * 256);
+          if (g == 12) {
+            // stage s+1 has landed and every wave is done reading the buffer of stage s
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              d[4 * RA + c] = *reinterpret_cast<const f32x4*>(An + (4 * RA + c) * 512);
+              d[4 * RB + c] = *reinterpret_cast<const f32x4*>(An + (4 * RB + c) * 512);
+            }
+          }
+          if (g == 13) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) d[4 * RC + c] = *reinterpret_cast<const f32x4*>(An + (4 * RC + c) * 512);
+          }
+          if (g == 14) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) trow(0, c);    // row 2H of the next stage (t is free: row 2H+1 is done)
+          }
+          if (g == 15) { vcol(0, 2); vcol(0, 3); }
+          __builtin_amdgcn_sched_barrier(0);
+          acc[ai] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[pp][1], bq[cur][1], acc[ai], 0, 0, 0);
+          if (g < 2) { trow(1, 2 * g); trow(1, 2 * g + 1); }          // row 2H+1 of this stage
+          else if (g < 4) { vcol(1, 2 * g - 4); vcol(1, 2 * g - 3); }
+          else if (g >= 12) piece(2 * (g - 12), cb, s + 2);
+          __builtin_amdgcn_sched_barrier(0);
+          acc[ai] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[pp][2], bq[cur][2], acc[ai], 0, 0, 0);
+          if (g < 12) bq[(g + 2) % 5] = *reinterpret_cast<const f32x4*>(Bb + (g + 2) * 256);
+          if (g == 12) { nbq[0] = *reinterpret_cast<const f32x4*>(Bn); nbq[1] = *reinterpret_cast<const f32x4*>(Bn + 256); }
+          if (g == 14) { vcol(0, 0); vcol(0, 1); }
+          if (g == 15) piece(7, cb, s + 2);
+          __builtin_amdgcn_sched_barrier(0);
+          acc[ai] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[pp][3], bq[cur][3], acc[ai], 0, 0, 0);
+          if (g >= 12 && g < 15) piece(2 * (g - 12) + 1, cb, s + 2);
+          __builtin_amdgcn_sched_barrier(0);
         }
-        if (p == 14) { v[0] = sub4(t1[0], t1[2]); v[1] = add4(t1[1], t1[2]); }
-        if (p == 15) piece(7, cb, s + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[p][3], bq[cur][3], acc[p], 0, 0, 0);
-        if (p >= 12 && p < 15) piece(2 * (p - 12) + 1, cb, s + 2);
-        __builtin_amdgcn_sched_barrier(0);
+      };
+      stage(std::true_type{}, 0);
+      for (int s = 1; s < ns; ++s) stage(std::false_type{}, s);
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the requests past the end; the ring is free
+      if (a.stamps) { t_loop = __builtin_amdgcn_s_memrealtime(); c_loop = __builtin_amdgcn_s_memtime() - c_loop; }
+      // exchange: [receiving wave][accumulator][register quad][lane][4] (16-byte lane runs: conflict-free)
+      {
+        f32x4* xo = reinterpret_cast<f32x4*>(smem) + (2 * (1 - H) + wm) * 2048 + lane;
+#pragma unroll
+        for (int pp = 0; pp < 8; ++pp)
+#pragma unroll
+          for (int r4 = 0; r4 < 4; ++r4) {
+            const f32x16& x = acc[8 * (1 - H) + pp];
+            xo[(pp * 4 + r4) * 64] = f32x4{x[4 * r4], x[4 * r4 + 1], x[4 * r4 + 2], x[4 * r4 + 3]};
+          }
+      }
+      __syncthreads();
+      wino_epilogue<EPI, H>(a, a.out, a.bias, acc, smem, tblk, n0, wm, H, l31, half, tid,
+                            reinterpret_cast<const f32x4*>(smem) + wave * 2048 + lane);
+    };
+    if (wn) body(std::integral_constant<int, 1>{});
+    else body(std::integral_constant<int, 0>{});
+  } else {
+    f32x4 d[16], v[16], t1[4], t2[4], t3[4];
+    // f32x4 operation q (0..23) of the transform behind its first row: rows 1, 2, 3 of t (q % 8 < 4) and of V (q % 8 >= 4)
+    auto xop = [&](int q) {
+      const int r = q >> 3, k = q & 7, c = k & 3;
+      if (k < 4) {
+        if (r == 0) t1[c] = add4(d[4 + c], d[8 + c]);
+        else if (r == 1) t2[c] = sub4(d[8 + c], d[4 + c]);
+        else t3[c] = sub4(d[4 + c], d[12 + c]);
+      } else {
+        f32x4(&t)[4] = r == 0 ? t1 : r == 1 ? t2 : t3;
+        f32x4& o = v[4 * (r + 1) + c];
+        if (c == 0) o = sub4(t[0], t[2]);
+        else if (c == 1) o = add4(t[1], t[2]);
+        else if (c == 2) o = sub4(t[2], t[1]);
+        else o = sub4(t[1], t[3]);
       }
     };
-    if (PEEL) stage(std::true_type{}, 0);
-    for (int s = PEEL ? 1 : 0; s < ns; ++s) stage(std::false_type{}, s);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the requests past the end; every wave out of the loop
+    {
+      // ---- the stage boundary of the LDS ring sits at position 12 of the MFMA stage.  With the boundary at the barrier
+      // the workgroup stamps (tools/gpu_wino_phases.py) put a stage at 2.35-2.7 us against 1.73 us of MFMA issue: after the
+      // barrier every wave - alone on its SIMD - read eighteen fragments and transformed a row before its first MFMA, and the
+      // last DMA piece of the next stage was requested 256 cycles before the barrier that waited for it.  Here the weight fragments of
+      // positions 12-15 are in registers by position 11, so the ONE barrier per stage stands between MFMAs (12,0) and
+      // (12,1): behind it the next stage's patch rows and first two weight fragments are read and its first transform row
+      // computed in the shadow of positions 12-15, and the buffer just released takes the weights (pieces 0-7) of stage
+      // s+2 at once; its patches (pieces 8-15) follow at positions 0-7 of stage s+1 - four positions before the barrier
+      // that needs them.
+#pragma unroll
+      for (int i = 0; i < 8; ++i) piece(i, 1, 1);
+      if (a.stamps) t_issued = __builtin_amdgcn_s_memrealtime();
+      asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // stage 0 has landed (loads return in order)
+      if (a.stamps) { t_landed = __builtin_amdgcn_s_memrealtime(); c_loop = __builtin_amdgcn_s_memtime(); }
+      f32x4 bq[5], nbq[2];
+      {
+        const float* Ab = smem + wm * 256 + l31 * 8 + half * 4;
+        const float* Bb = smem + A_ST + wn * 256 + l31 * 8 + half * 4;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { d[c] = *reinterpret_cast<const f32x4*>(Ab + c * 512); d[8 + c] = *reinterpret_cast<const f32x4*>(Ab + (8 + c) * 512); }
+        nbq[0] = *reinterpret_cast<const f32x4*>(Bb);
+        nbq[1] = *reinterpret_cast<const f32x4*>(Bb + 512);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { d[4 + c] = *reinterpret_cast<const f32x4*>(Ab + (4 + c) * 512); d[12 + c] = *reinterpret_cast<const f32x4*>(Ab + (12 + c) * 512); }
+        f32x4 t0[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) t0[c] = sub4(d[c], d[8 + c]);
+        v[0] = sub4(t0[0], t0[2]); v[1] = add4(t0[1], t0[2]); v[2] = sub4(t0[2], t0[1]); v[3] = sub4(t0[1], t0[3]);
+      }
+      auto stage = [&](auto first_c, int s) {
+        constexpr bool FIRST = decltype(first_c)::value;
+        const int cb = s & 1;
+        const float* Bb = smem + cb * STAGE + A_ST + wn * 256 + l31 * 8 + half * 4;
+        const float* An = smem + (cb ^ 1) * STAGE + wm * 256 + l31 * 8 + half * 4;     // the next stage's
+        const float* Bn = smem + (cb ^ 1) * STAGE + A_ST + wn * 256 + l31 * 8 + half * 4;
+        bq[0] = nbq[0]; bq[1] = nbq[1];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int p = 0; p < 16; ++p) {
+          const int cur = p % 5;
+          if (FIRST) acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[p][0], bq[cur][0], zero16, 0, 0, 0);
+          else acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[p][0], bq[cur][0], acc[p], 0, 0, 0);
+          if (p < 8) piece(8 + p, cb ^ 1, s + 1);
+          if (p == 10) bq[4] = *reinterpret_cast<const f32x4*>(Bb + 14 * 512);
+          if (p == 11) bq[0] = *reinterpret_cast<const f32x4*>(Bb + 15 * 512);
+          if (p == 12) {
+            // stage s+1 has landed and every wave is done reading the buffer of stage s
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#pragma unroll
+            for (int c = 0; c < 4; ++c) { d[c] = *reinterpret_cast<const f32x4*>(An + c * 512); d[8 + c] = *reinterpret_cast<const f32x4*>(An + (8 + c) * 512); }
+          }
+          if (p == 13) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) d[4 + c] = *reinterpret_cast<const f32x4*>(An + (4 + c) * 512);
+          }
+          if (p == 14) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) t1[c] = sub4(d[c], d[8 + c]);    // (t1 is free: the row-0 temporaries of the next stage)
+          }
+          if (p == 15) { v[2] = sub4(t1[2], t1[1]); v[3] = sub4(t1[1], t1[3]); }
+          __builtin_amdgcn_sched_barrier(0);
+          acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[p][1], bq[cur][1], acc[p], 0, 0, 0);
+          if (p < 12) { xop(2 * p); xop(2 * p + 1); }   // (both in one gap: 2.5 % faster than one per gap)
+          else piece(2 * (p - 12), cb, s + 2);
+          __builtin_amdgcn_sched_barrier(0);
+          acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[p][2], bq[cur][2], acc[p], 0, 0, 0);
+          if (p < 12) bq[(p + 2) % 5] = *reinterpret_cast<const f32x4*>(Bb + (p + 2) * 512);
+          if (p == 12) { nbq[0] = *reinterpret_cast<const f32x4*>(Bn); nbq[1] = *reinterpret_cast<const f32x4*>(Bn + 512); }
+          if (p == 13) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) d[12 + c] = *reinterpret_cast<const f32x4*>(An + (12 + c) * 512);
+          }
+          if (p == 14) { v[0] = sub4(t1[0], t1[2]); v[1] = add4(t1[1], t1[2]); }
+          if (p == 15) piece(7, cb, s + 2);
+          __builtin_amdgcn_sched_barrier(0);
+          acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[p][3], bq[cur][3], acc[p], 0, 0, 0);
+          if (p >= 12 && p < 15) piece(2 * (p - 12) + 1, cb, s + 2);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
+      if (PEEL) stage(std::true_type{}, 0);
+      for (int s = PEEL ? 1 : 0; s < ns; ++s) stage(std::false_type{}, s);
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the requests past the end; every wave out of the loop
+    }
+    if (a.stamps) { t_loop = __builtin_amdgcn_s_memrealtime(); c_loop = __builtin_amdgcn_s_memtime() - c_loop; }
+    if (SPLITK)   // raw partials: bias and epilogue are the split-K reduction's
+      wino_epilogue<EPI_PLAIN>(a, a.out + (size_t)blockIdx.y * (size_t)a.M * a.Cout, nullptr, acc, smem, tblk, n0, wm, wn, l31, half, tid);
+    else
+      wino_epilogue<EPI>(a, a.out, a.bias, acc, smem, tblk, n0, wm, wn, l31, half, tid);
   }
-  if (a.stamps) { t_loop = __builtin_amdgcn_s_memrealtime(); c_loop = __builtin_amdgcn_s_memtime() - c_loop; }
-  if (SPLITK)   // raw partials: bias and epilogue are the split-K reduction's
-    wino_epilogue<EPI_PLAIN>(a, a.out + (size_t)blockIdx.y * (size_t)a.M * a.Cout, nullptr, acc, smem, tblk, n0, wm, wn, l31, half, tid);
-  else
-    wino_epilogue<EPI>(a, a.out, a.bias, acc, smem, tblk, n0, wm, wn, l31, half, tid);
   if (a.stamps && tid == 0) {   // 10-ns ticks: entry, first stage requested, landed, loop end, epilogue end; loop cycles; ids
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the epilogue's stores have left the wave
     unsigned long long* o = a.stamps + 8 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
@@ -500,6 +658,10 @@ extern "C" int tdx_pack_conv3x3_wino(const float* w_oihw, float* u_fwd, float* u
   return tdx_pack_conv3x3_wino_pad(w_oihw, u_fwd, u_dgrad, cout, cin, cin, stream);
 }
 
+int g_tdx_wino_rows = 1;              // knob "wino_rows": training launches on the row-split main loop (0: the channel split)
+int g_tdx_wino_rows_min_stages = 16;  // knob "wino_rows_min_stages": ... of at least this many K-stages (the 8-stage input gradients lost
+                                      // more to the exchange than their loop saved: profiles/r06_wino_phases.txt)
+
 // splits > 1: K (input channels) cut into `splits` ranges of `per` stages, raw partials to out[split][M][cout]
 // (flags, bias, scale / shift then belong to the caller's reduction)
 int tdx_conv3x3_wino_launch(const float* in, const float* u, const float* bias, float* out, int B, int H, int W,
@@ -527,9 +689,9 @@ int tdx_conv3x3_wino_launch(const float* in, const float* u, const float* bias, 
                  ? reinterpret_cast<unsigned long long*>(g_tdx_diag_buffer) : nullptr;   // diagnostic knob conv_stamp = 3
   const size_t lds = (size_t)2 * STAGE * sizeof(float) + WT * 2 * sizeof(unsigned);   // two stages + the tile table
   hipStream_t st = to_stream(stream);
-#define TDX_WINO_LAUNCH(EPI_, SPL_)                                                                              \
+#define TDX_WINO_LAUNCH(EPI_, SPL_, ROWS_)                                                                       \
   do {                                                                                                           \
-    auto kern = conv3x3_wino_kernel<EPI_, SPL_>;                                                                 \
+    auto kern = conv3x3_wino_kernel<EPI_, SPL_, ROWS_>;                                                          \
     static bool attr_set = false;                                                                                \
     if (!attr_set) {                                                                                             \
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                    \
@@ -539,10 +701,14 @@ int tdx_conv3x3_wino_launch(const float* in, const float* u, const float* bias, 
     }                                                                                                            \
     kern<<<grid, 256, lds, st>>>(a);                                                                             \
   } while (0)
-  if (splits > 1) TDX_WINO_LAUNCH(EPI_PLAIN, true);
-  else if (flags & TDX_CONV_OUT_BNRELU) TDX_WINO_LAUNCH(EPI_BNRELU, false);
-  else if (flags & TDX_CONV_OUT_STATS) TDX_WINO_LAUNCH(EPI_STATS, false);
-  else TDX_WINO_LAUNCH(EPI_PLAIN, false);
+  const bool rows = g_tdx_wino_rows && cin / WK >= g_tdx_wino_rows_min_stages;   // the training launches' loop
+  if (splits > 1) TDX_WINO_LAUNCH(EPI_PLAIN, true, false);
+  else if (flags & TDX_CONV_OUT_BNRELU) TDX_WINO_LAUNCH(EPI_BNRELU, false, false);
+  else if (flags & TDX_CONV_OUT_STATS) {
+    if (rows) TDX_WINO_LAUNCH(EPI_STATS, false, true);
+    else TDX_WINO_LAUNCH(EPI_STATS, false, false);
+  } else if (rows) TDX_WINO_LAUNCH(EPI_PLAIN, false, true);
+  else TDX_WINO_LAUNCH(EPI_PLAIN, false, false);
 #undef TDX_WINO_LAUNCH
   TDX_CHECK_LAUNCH();
   return 0;

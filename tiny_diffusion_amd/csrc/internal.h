@@ -79,6 +79,7 @@ extern "C" int tdx_conv3x3_wino_stat_tiles(int B, int H, int W);
 extern "C" int tdx_conv3x3_wino_stat_tile_rows(int B, int H, int W);
 extern int g_tdx_wino, g_tdx_wino_min_wgs;   // knobs "wino" / "wino_min_wgs" (unet.hip)
 extern int g_tdx_wino_wgrad, g_tdx_wino_wgrad_min_tiles, g_tdx_wino_wgrad_target;
+extern int g_tdx_wino_rows, g_tdx_wino_rows_min_stages;   // knobs "wino_rows" / "wino_rows_min_stages" (conv3x3_wino.hip)
 extern "C" int tdx_conv3x3_wgrad_wino_splits(int B, int H, int W, int cin, int cout);
 extern "C" int tdx_conv3x3_wgrad_wino(const float* in, const float* dy, float* dw_slabs, int B, int H, int W, int cin, int cout,
                                       tdx_stream_t stream);

@@ -18,8 +18,10 @@ sys.path.insert(0, ROOT)
 from tiny_diffusion_amd import _build  # noqa: E402
 
 KERNELS = [("conv3x3_wgrad_wino_kernel", "_Z25conv3x3_wgrad_wino_kernel10WinoWgArgs"),
-           ("conv3x3_wino_kernel<1,false> (forward, statistics)", "_Z19conv3x3_wino_kernelILi1ELb0EEv8WinoArgs"),
-           ("conv3x3_wino_kernel<0,false> (input gradient)", "_Z19conv3x3_wino_kernelILi0ELb0EEv8WinoArgs")]
+           ("conv3x3_wino_kernel<1,false,false> (forward, stats)", "_Z19conv3x3_wino_kernelILi1ELb0ELb0EEv8WinoArgs"),
+           ("conv3x3_wino_kernel<0,false,false> (input gradient)", "_Z19conv3x3_wino_kernelILi0ELb0ELb0EEv8WinoArgs"),
+           ("conv3x3_wino_kernel<1,false,true> (fwd, row split)", "_Z19conv3x3_wino_kernelILi1ELb0ELb1EEv8WinoArgs"),
+           ("conv3x3_wino_kernel<0,false,true> (dgrad, row split)", "_Z19conv3x3_wino_kernelILi0ELb0ELb1EEv8WinoArgs")]
 CLASSES = ["mfma", "v_add/sub_f32", "other VALU", "accvgpr mov", "SALU", "ds", "buffer", "scratch", "waitcnt/barrier"]
 
 
@@ -91,30 +93,52 @@ def resources(asm, sym):
             "scratch": get(r"; ScratchSize:\s+(\d+)", blk), "lds_static": get(r"\.group_segment_fixed_size:\s+(\d+)", meta)}
 
 
-def main():
-    src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(_build.CSRC, "conv3x3_wino.hip")
+def compile_asm(src):
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "wino.s")
         cmd = [_build._hipcc(), *_build.HIPCC_FLAGS, "--cuda-device-only", "-S", "-I", _build.CSRC, src, "-o", out]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode:
-            sys.exit(f"hipcc failed:\n{r.stderr}")
-        asm = open(out).read()
+            raise RuntimeError(f"hipcc failed:\n{r.stderr}")
+        return open(out).read()
+
+
+def run(src=None):
+    """{kernel name: None (not in the object) or {"lines", the CLASSES per 64 MFMAs, "valu" (non-MFMA VALU per 64
+    MFMAs), "res": {"vgpr", "agpr", "scratch", "lds_static"} as strings}}"""
+    asm = compile_asm(src or os.path.join(_build.CSRC, "conv3x3_wino.hip"))
+    rows = {}
+    for name, sym in KERNELS:
+        if f"\n{sym}:" not in asm:
+            rows[name] = None
+            continue
+        loop = innermost_loop(function_body(asm, sym))
+        n = census(loop)
+        k = 64.0 / n["mfma"] if n["mfma"] else 1.0
+        row = {c: n[c] * k for c in CLASSES}
+        row["valu"] = (n["v_add/sub_f32"] + n["other VALU"]) * k
+        row["lines"] = len(loop)
+        row["res"] = resources(asm, sym)
+        rows[name] = row
+    return rows
+
+
+def main():
+    src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(_build.CSRC, "conv3x3_wino.hip")
+    try:
+        rows = run(src)
+    except RuntimeError as e:
+        sys.exit(str(e))
     print(f"# {os.path.relpath(src, ROOT)}  ({' '.join(_build.HIPCC_FLAGS)})")
     print("# innermost loop, one iteration scaled to 64 MFMAs (one K-stage)")
     print(f"{'kernel':52s} {'lines':>5s} " + " ".join(f"{c:>14s}" for c in CLASSES) + "  VGPR AGPR scratch")
-    for name, sym in KERNELS:
-        if f"\n{sym}:" not in asm:
+    for name, row in rows.items():
+        if row is None:
             print(f"{name:52s} (not found)")
             continue
-        body = function_body(asm, sym)
-        loop = innermost_loop(body)
-        n = census(loop)
-        k = 64.0 / n["mfma"] if n["mfma"] else 1.0
-        res = resources(asm, sym)
-        print(f"{name:52s} {len(loop):5d} " + " ".join(f"{n[c] * k:14.0f}" for c in CLASSES)
-              + f"  {res['vgpr']:>4s} {res['agpr']:>4s} {res['scratch']:>7s}")
-        print(f"{'':52s} {'':5s}   non-MFMA VALU per 64 MFMAs (add/sub + other): {(n['v_add/sub_f32'] + n['other VALU']) * k:.0f}")
+        print(f"{name:52s} {row['lines']:5d} " + " ".join(f"{row[c]:14.0f}" for c in CLASSES)
+              + f"  {row['res']['vgpr']:>4s} {row['res']['agpr']:>4s} {row['res']['scratch']:>7s}")
+        print(f"{'':52s} {'':5s}   non-MFMA VALU per 64 MFMAs (add/sub + other): {row['valu']:.0f}")
 
 
 if __name__ == "__main__":
