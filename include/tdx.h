@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define TDX_VERSION 400 /* 0.4.0: additions: tdx_pack_conv3x3_tiled, tdx_conv3x3_fwd_infer, tdx_conv3x3_infer_scratch_floats (the inference convolution of the reverse process), tdx_linear_{fwd,bwd}_prec; tdx_unet_set_precision accepts TDX_PREC_BF16 for the latent MLP.  0.3.0: tdx_diag_set_buffer takes the buffer size (incompatible); additions: tdx_timestep_embedding_f32, tdx_initial_conv_input_grad, tdx_unet_request_input_grad; time_dim of any width */
+#define TDX_VERSION 400 /* 0.4.0: additions: tdx_step_begin_sched, tdx_p_sample_step_sched{,_philox}, tdx_unet_prepare_sampling_sched, tdx_unet_eval_step_sched (timestep schedules: DDIM sampling); tdx_pack_conv3x3_tiled, tdx_conv3x3_fwd_infer, tdx_conv3x3_infer_scratch_floats (the inference convolution of the reverse process), tdx_linear_{fwd,bwd}_prec; tdx_unet_set_precision accepts TDX_PREC_BF16 for the latent MLP.  0.3.0: tdx_diag_set_buffer takes the buffer size (incompatible); additions: tdx_timestep_embedding_f32, tdx_initial_conv_input_grad, tdx_unet_request_input_grad; time_dim of any width */
 
 #define TDX_E_BADARG (-1)   /* null pointer, size <= 0, batch > plan capacity ... */
 #define TDX_E_SHAPE (-2)    /* shape the kernel family does not cover */
@@ -80,6 +80,21 @@ int tdx_p_sample_step_philox(float* x_out, const float* x, const float* eps,
 /* Device-side step counter for graph-captured sampling loops: t = *counter; *t_idx = t;
  * t_vec[0..n) = t; *counter = t - 1.  (diffusion.py:259-260 rebuilds t on the host per step.) */
 int tdx_step_begin(int64_t* counter, int32_t* t_idx, int64_t* t_vec, int n, tdx_stream_t stream);
+
+/* Timestep schedules (DDIM, schedule.py ddim_schedule): a reverse chain of S steps k = S-1 .. 0 that runs the
+ * network at the timesteps tau[k] (device int64, strictly ascending, < T).  The step index k takes the place of t:
+ * it is the row of the (S,3) coefficient table coef = (c1, c2, sigma) of x' = c1 (x - c2 eps) + sigma z, the noise
+ * term is skipped at k == 0, and in-kernel Philox noise is keyed by (element, tau[k], seed) - so the identity
+ * schedule tau = 0..T-1 with the table of tdx_p_sample_step reproduces that update bit for bit.
+ * tdx_step_begin_sched: k = *counter; *t_idx = k; t_vec[0..n) = tau[k]; *counter = k - 1. */
+int tdx_step_begin_sched(int64_t* counter, const int64_t* tau, int32_t* t_idx, int64_t* t_vec, int n,
+                         tdx_stream_t stream);
+/* The update at step k = *k_idx (z == NULL: no noise term). */
+int tdx_p_sample_step_sched(float* x_out, const float* x, const float* eps, const float* z, const float* coef,
+                            const int64_t* tau, const int32_t* k_idx, int64_t n, tdx_stream_t stream);
+int tdx_p_sample_step_sched_philox(float* x_out, const float* x, const float* eps, const float* coef,
+                                   const int64_t* tau, const int32_t* k_idx, int64_t n, uint64_t seed,
+                                   tdx_stream_t stream);
 
 /* Caller side of the path: minibatch gather from a device-resident uint8
  * dataset fused with ToTensor + Normalize((mean,),(std,)) of diffusion.py:202-204:
@@ -568,6 +583,19 @@ int tdx_unet_eval_step(tdx_unet* u, const void* const* params, void* const* buff
  * Any later tdx_unet_pack invalidates the tables (eval steps then take the direct path). */
 int tdx_unet_prepare_sampling(tdx_unet* u, const void* const* params, const void* cond, int batch, int T,
                               tdx_stream_t stream);
+
+/* The same two entries for a timestep schedule of S steps (tau: device int64 [S], see tdx_step_begin_sched):
+ * prepare builds S table rows at the timesteps tau[0..S) (rebuilt on every call), and the scheduled eval step
+ * runs eps_theta(x, tau[k]) and the update of coefficient row k (coef: (S,3)); the counter holds k.  A table built
+ * for one schedule (or for none) serves only eval steps with the same tau pointer and S: otherwise the step takes
+ * the direct path. */
+int tdx_unet_prepare_sampling_sched(tdx_unet* u, const void* const* params, const void* cond, int batch,
+                                    const int64_t* tau, int S, tdx_stream_t stream);
+int tdx_unet_eval_step_sched(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
+                             const void* cond, const float* z, const float* coef, const int64_t* tau, int S,
+                             int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
+                             void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed,
+                             tdx_stream_t stream);
 
 /* Testing aid: offset (in floats) and element count of a named intermediate inside the
  * workspace after a forward: "x0", "Y0".."Y12", "ss0".."ss12", "e1p", "cat1", "d1a", ... */

@@ -126,6 +126,9 @@ _SIGS = {
                                       C.c_int, C.c_int, _ptr]),
     "tdx_adam_step_dev": (C.c_int, [_ptr, _ptr, _ptr, _ptr, C.c_int64, _ptr, C.c_float, C.c_float, C.c_float, _ptr]),
     "tdx_step_begin": (C.c_int, [_ptr, _ptr, _ptr, C.c_int, _ptr]),
+    "tdx_step_begin_sched": (C.c_int, [_ptr, _ptr, _ptr, _ptr, C.c_int, _ptr]),
+    "tdx_p_sample_step_sched": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int64, _ptr]),
+    "tdx_p_sample_step_sched_philox": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int64, C.c_uint64, _ptr]),
     "tdx_linear_fwd": (C.c_int, [_ptr, C.c_int, _ptr, _ptr, _ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ptr]),
     "tdx_linear_bwd": (C.c_int, [_ptr, C.c_int, _ptr, C.c_int, _ptr, _ptr, C.c_int, _ptr, _ptr, C.c_int, C.c_int,
                                  C.c_int, _ptr]),
@@ -171,9 +174,12 @@ _SIGS = {
     "tdx_unet_backward_sync_mark": (C.c_int, [_ptr, C.c_int]),
     "tdx_unet_request_input_grad": (C.c_int, [_ptr, _ptr]),
     "tdx_unet_prepare_sampling": (C.c_int, [_ptr, _ptr, _ptr, C.c_int, C.c_int, _ptr]),
+    "tdx_unet_prepare_sampling_sched": (C.c_int, [_ptr, _ptr, _ptr, C.c_int, _ptr, C.c_int, _ptr]),
     "tdx_initial_conv_input_grad": (C.c_int, [_ptr, _ptr, _ptr] + [C.c_int] * 5 + [_ptr]),
     "tdx_unet_eval_step": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int64,
                                      _ptr, C.c_size_t, C.c_int, C.c_uint64, _ptr]),
+    "tdx_unet_eval_step_sched": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, _ptr, _ptr, _ptr,
+                                           _ptr, C.c_int64, _ptr, C.c_size_t, C.c_int, C.c_uint64, _ptr]),
     "tdx_timestep_embedding": (C.c_int, [_ptr, _ptr, C.c_int, C.c_int, _ptr]),
     "tdx_timestep_embedding_f32": (C.c_int, [_ptr, _ptr, C.c_int, C.c_int, _ptr]),
     "tdx_time_mlp_fwd": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, _ptr]),

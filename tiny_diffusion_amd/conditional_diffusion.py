@@ -6,10 +6,10 @@ from __future__ import annotations
 
 import torch
 
-from .schedule import ForwardProcess, sample_loop
+from .schedule import ForwardProcess, ddim_sample_loop, sample_loop
 from .unet import NoiseModelBase, TIME_DIM
 
-__all__ = ["NoiseModel", "ForwardProcess", "sample"]
+__all__ = ["NoiseModel", "ForwardProcess", "sample", "ddim_sample"]
 
 
 class NoiseModel(NoiseModelBase):
@@ -26,8 +26,22 @@ class NoiseModel(NoiseModelBase):
 @torch.no_grad()
 def sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples=16, y=None, **kw):
     """conditional_diffusion.py:354-386, including its argument errors."""
+    _check_labels(y, n_samples)
+    return sample_loop(noise_model, diffusion, device, n_samples, y, **kw)
+
+
+@torch.no_grad()
+def ddim_sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples=16, y=None, steps=50, eta=0.0,
+                timesteps=None, **kw):
+    """DDIM sampling (Song et al. 2021): ``sample()``'s contract and argument errors over ``steps`` timesteps (or
+    the explicit list ``timesteps``) with stochasticity ``eta`` (schedule.ddim_schedule)."""
+    _check_labels(y, n_samples)
+    return ddim_sample_loop(noise_model, diffusion, device, n_samples, y, steps=steps, eta=eta, timesteps=timesteps,
+                            **kw)
+
+
+def _check_labels(y, n_samples):
     if y is None:
         raise ValueError("Class labels 'y' must be provided for conditional generation.")
     if y.shape[0] != n_samples:
         raise ValueError("y must have shape (n_samples,)")
-    return sample_loop(noise_model, diffusion, device, n_samples, y, **kw)

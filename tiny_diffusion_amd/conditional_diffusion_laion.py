@@ -12,10 +12,10 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .schedule import ForwardProcess as _ForwardProcess, sample_loop
+from .schedule import ForwardProcess as _ForwardProcess, ddim_sample_loop, sample_loop
 from .unet import ARCH_LAION, NoiseModelBase
 
-__all__ = ["NoiseModel", "ForwardProcess", "get_timestep_embedding", "sample", "postprocess_images"]
+__all__ = ["NoiseModel", "ForwardProcess", "get_timestep_embedding", "sample", "ddim_sample", "postprocess_images"]
 
 TIME_DIM = ARCH_LAION.time_dim
 
@@ -73,6 +73,23 @@ def sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, text_embe
         raise ValueError("Text embeddings must be provided for conditional generation.")
     n_samples = text_embeds.shape[0]
     x = sample_loop(noise_model, diffusion, device, n_samples, text_embeds, **kw)
+    return _decode(x, vae, scaling_factor)
+
+
+@torch.no_grad()
+def ddim_sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, text_embeds=None, vae=None,
+                scaling_factor=1.0, steps=50, eta=0.0, timesteps=None, **kw):
+    """DDIM sampling (Song et al. 2021): ``sample()``'s contract, argument errors and decode over ``steps`` timesteps
+    (or the explicit list ``timesteps``) with stochasticity ``eta`` (schedule.ddim_schedule)."""
+    if text_embeds is None:
+        raise ValueError("Text embeddings must be provided for conditional generation.")
+    n_samples = text_embeds.shape[0]
+    x = ddim_sample_loop(noise_model, diffusion, device, n_samples, text_embeds, steps=steps, eta=eta,
+                         timesteps=timesteps, **kw)
+    return _decode(x, vae, scaling_factor)
+
+
+def _decode(x, vae, scaling_factor):
     if vae is None:
         return x
     decoded = vae.decode(x / scaling_factor).sample

@@ -127,6 +127,7 @@ thin_to_fat_conv_kernel(const float* __restrict__ thin, const float* __restrict_
 struct PSampleOps {
   float* x; const float* z; const float* coef; const int32_t* t_idx; uint64_t seed; int philox; int64_t* counter_dec;
   int64_t elem0;   // index of this launch's first element in the whole batch (a half-batch launch keeps the batch's Philox stream)
+  const int64_t* tau;   // timestep schedule (DDIM): *t_idx is the step index k, the Philox stream tau[k]; null: identity
 };
 template <int CO, bool DGRAD, bool PS, typename TF>
 __global__ void __launch_bounds__(256)
@@ -154,9 +155,11 @@ fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
 #pragma unroll
   for (int co = 0; co < CO; ++co) bv[co] = DGRAD ? 0.f : bias[co];
   int ps_t = 0;
+  uint64_t ps_nt = 0;
   float ps_c1 = 0.f, ps_c2 = 0.f, ps_sg = 0.f;
   if (PS) {
     ps_t = *ps.t_idx;
+    ps_nt = ps.tau ? (uint64_t)ps.tau[ps_t] : (uint64_t)ps_t;
     ps_c1 = ps.coef[3 * ps_t + 0]; ps_c2 = ps.coef[3 * ps_t + 1]; ps_sg = ps.coef[3 * ps_t + 2];
     // table-mode sampling: the step counter is advanced by the last kernel of the step (see p_sample_kernel)
     if (ps.counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *ps.counter_dec = (int64_t)ps_t - 1;
@@ -204,7 +207,7 @@ fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
           if (ps_t > 0) {
             if (ps.philox) {   // element idx = component idx % 4 of block idx / 4 (p_sample_kernel<true>)
               const int64_t gidx = idx + ps.elem0;
-              const float4 z4 = philox_normal4((uint64_t)(gidx >> 2), (uint64_t)ps_t, ps.seed);
+              const float4 z4 = philox_normal4((uint64_t)(gidx >> 2), ps_nt, ps.seed);
               const int k = (int)(gidx & 3);
               zv = k == 0 ? z4.x : k == 1 ? z4.y : k == 2 ? z4.z : z4.w;
             } else if (ps.z) {
@@ -494,11 +497,12 @@ int tdx_initial_conv_dgrad(const void* g_x0, const float* w, float* g_x, int B, 
 // final_conv forward with the reverse-process update fused in (sampling; PSampleOps above)
 int tdx_final_conv_fwd_psample(const void* in, const float* w, const float* bias, float* eps_out, int B, int H, int W,
                                int cout, float* x, const float* z, const float* coef, const int32_t* t_idx,
-                               uint64_t seed, int philox, int64_t* counter_dec, hipStream_t st, int io16, int64_t elem0) {
+                               uint64_t seed, int philox, int64_t* counter_dec, hipStream_t st, int io16, int64_t elem0,
+                               const int64_t* tau) {
   if (!x || !coef || !t_idx || (elem0 & 3)) return TDX_E_BADARG;
   const int64_t M = (int64_t)B * H * W;
   const int grid = (int)std::min<int64_t>((M + 15) / 16, 8192);
-  const PSampleOps ps{x, z, coef, t_idx, seed, philox, counter_dec, elem0};
+  const PSampleOps ps{x, z, coef, t_idx, seed, philox, counter_dec, elem0, tau};
   if (cout != 1 && cout != 4) return TDX_E_SHAPE;
   TDX_IO_DISPATCH(io16, T,
     if (cout == 1) fat_to_thin_conv_kernel<1, false, true, T><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps);

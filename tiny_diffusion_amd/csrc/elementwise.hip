@@ -90,8 +90,13 @@ template <bool PHILOX>
 __global__ void p_sample_kernel(float4* xo, const float4* x,  // may alias: in-place update
                                 const float4* __restrict__ eps, const float4* __restrict__ z,
                                 const float* __restrict__ coef, const int32_t* __restrict__ t_idx,
-                                int64_t n4, uint64_t seed, int64_t* counter_dec = nullptr) {
+                                int64_t n4, uint64_t seed, int64_t* counter_dec = nullptr,
+                                const int64_t* __restrict__ tau = nullptr) {
+  // t = the coefficient row.  With a timestep schedule (tau != null, DDIM) it is the step index k and the Philox
+  // stream is the network's timestep tau[k], so the identity schedule draws today's noise; the noise term is
+  // skipped at k == 0 either way.
   const int t = *t_idx;
+  const uint64_t nt = tau ? (uint64_t)tau[t] : (uint64_t)t;
   // table-mode sampling (tdx_unet_eval_step): the step counter is advanced HERE, by the last kernel of the
   // step, because the head kernel of the step reads it from every workgroup (nobody else touches it in between)
   if (counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *counter_dec = (int64_t)t - 1;
@@ -100,7 +105,7 @@ __global__ void p_sample_kernel(float4* xo, const float4* x,  // may alias: in-p
        i += (int64_t)gridDim.x * blockDim.x) {
     float4 xv = x[i], ev = eps[i], zv = make_float4(0.f, 0.f, 0.f, 0.f), o;
     if (PHILOX) {
-      if (t > 0) zv = philox_normal4((uint64_t)i, (uint64_t)t, seed);
+      if (t > 0) zv = philox_normal4((uint64_t)i, nt, seed);
     } else if (z && t > 0) {  // diffusion.py:267-270: no noise on the last step
       zv = z[i];
     }
@@ -125,16 +130,19 @@ extern "C" int tdx_p_sample_step(float* x_out, const float* x, const float* eps,
 }
 
 // the update with the counter decrement of table-mode sampling folded in (z == null: in-kernel Philox noise)
+// (counter_dec == null: no decrement; tau != null: coefficient row k, timestep tau[k] - the scheduled update)
 int tdx_p_sample_step_dec(float* x_out, const float* x, const float* eps, const float* z, const float* coef,
-                          const int32_t* t_idx, int64_t n, uint64_t seed, int64_t* counter_dec, hipStream_t st) {
+                          const int32_t* t_idx, int64_t n, uint64_t seed, int64_t* counter_dec, hipStream_t st,
+                          const int64_t* tau) {
   if (!x_out || !x || !eps || !coef || !t_idx || n <= 0) return TDX_E_BADARG;
   if (n % 4) return TDX_E_SHAPE;
   if (z)
     p_sample_kernel<false><<<ew_grid(n / 4, 256), 256, 0, st>>>((float4*)x_out, (const float4*)x, (const float4*)eps,
-                                                               (const float4*)z, coef, t_idx, n / 4, 0, counter_dec);
+                                                               (const float4*)z, coef, t_idx, n / 4, 0, counter_dec,
+                                                               tau);
   else
     p_sample_kernel<true><<<ew_grid(n / 4, 256), 256, 0, st>>>((float4*)x_out, (const float4*)x, (const float4*)eps,
-                                                              nullptr, coef, t_idx, n / 4, seed, counter_dec);
+                                                              nullptr, coef, t_idx, n / 4, seed, counter_dec, tau);
   TDX_CHECK_LAUNCH();
   return 0;
 }
@@ -150,13 +158,39 @@ extern "C" int tdx_p_sample_step_philox(float* x_out, const float* x, const floa
   return 0;
 }
 
+// The update of a timestep schedule (DDIM): coefficient row k = *k_idx of the (S,3) table, noise at k > 0 only,
+// Philox stream tau[k].  z == null in the first form: no noise term (as tdx_p_sample_step).
+extern "C" int tdx_p_sample_step_sched(float* x_out, const float* x, const float* eps, const float* z,
+                                       const float* coef, const int64_t* tau, const int32_t* k_idx, int64_t n,
+                                       tdx_stream_t stream) {
+  if (!x_out || !x || !eps || !coef || !tau || !k_idx || n <= 0) return TDX_E_BADARG;
+  if (n % 4) return TDX_E_SHAPE;
+  p_sample_kernel<false><<<ew_grid(n / 4, 256), 256, 0, to_stream(stream)>>>(
+      (float4*)x_out, (const float4*)x, (const float4*)eps, (const float4*)z, coef, k_idx, n / 4, 0, nullptr, tau);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tdx_p_sample_step_sched_philox(float* x_out, const float* x, const float* eps, const float* coef,
+                                              const int64_t* tau, const int32_t* k_idx, int64_t n, uint64_t seed,
+                                              tdx_stream_t stream) {
+  if (!x_out || !x || !eps || !coef || !tau || !k_idx || n <= 0) return TDX_E_BADARG;
+  if (n % 4) return TDX_E_SHAPE;
+  p_sample_kernel<true><<<ew_grid(n / 4, 256), 256, 0, to_stream(stream)>>>(
+      (float4*)x_out, (const float4*)x, (const float4*)eps, nullptr, coef, k_idx, n / 4, seed, nullptr, tau);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
 // Device-side step counter for graph-captured sampling: t = *counter; t_idx = t; t_vec[:] = t;
 // *counter = t - 1.  One block; lets a HIP graph hold several consecutive reverse steps with no
 // host work between them (diffusion.py:259-260 builds the same t tensor on the host each step).
+// tau != null (timestep schedule): the counter is the step index k, t_idx = k, t_vec[:] = tau[k].
 __global__ void step_begin_kernel(int64_t* __restrict__ counter, int32_t* __restrict__ t_idx,
-                                  int64_t* __restrict__ t_vec, int n) {
+                                  int64_t* __restrict__ t_vec, int n, const int64_t* __restrict__ tau = nullptr) {
   const int64_t t = *counter;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) t_vec[i] = t;
+  const int64_t tv = tau ? tau[t] : t;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) t_vec[i] = tv;
   __syncthreads();
   if (threadIdx.x == 0) {
     *t_idx = (int32_t)t;
@@ -167,6 +201,14 @@ __global__ void step_begin_kernel(int64_t* __restrict__ counter, int32_t* __rest
 extern "C" int tdx_step_begin(int64_t* counter, int32_t* t_idx, int64_t* t_vec, int n, tdx_stream_t stream) {
   if (!counter || !t_idx || !t_vec || n <= 0) return TDX_E_BADARG;
   step_begin_kernel<<<1, 256, 0, to_stream(stream)>>>(counter, t_idx, t_vec, n);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tdx_step_begin_sched(int64_t* counter, const int64_t* tau, int32_t* t_idx, int64_t* t_vec, int n,
+                                    tdx_stream_t stream) {
+  if (!counter || !tau || !t_idx || !t_vec || n <= 0) return TDX_E_BADARG;
+  step_begin_kernel<<<1, 256, 0, to_stream(stream)>>>(counter, t_idx, t_vec, n, tau);
   TDX_CHECK_LAUNCH();
   return 0;
 }

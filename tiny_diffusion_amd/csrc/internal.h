@@ -22,7 +22,7 @@ int tdx_final_conv_fwd(const void* in, const float* w, const float* bias, float*
 int tdx_final_conv_fwd_psample(const void* in, const float* w, const float* bias, float* eps_out, int B, int H, int W,
                                int cout, float* x, const float* z, const float* coef, const int32_t* t_idx,
                                uint64_t seed, int philox, int64_t* counter_dec, hipStream_t st, int io16 = 0,
-                               int64_t elem0 = 0);
+                               int64_t elem0 = 0, const int64_t* tau = nullptr);
 int tdx_final_conv_dgrad(const float* g_out, const float* w, void* g_in, int B, int H, int W,
                          int cout, hipStream_t st, int io16 = 0);
 int tdx_final_conv_wgrad(const void* in, const float* g_out, float* partial, float* dw, float* db,
@@ -120,17 +120,19 @@ int tdx_time_embed_only(const int64_t* t, const int64_t* y, const float* const* 
                         float* tf_out, int B, hipStream_t st);
 // sampling tables (time_embed.hip) and the pieces of a table-mode reverse step
 size_t tdx_time_tables_index_floats(int T);
+// tau != null: the T rows are built at the timesteps tau[0..T) (a DDIM schedule) instead of 0..T-1
 int tdx_time_tables_build(int kind, const float* const* P, int T, int td, float* tab1, float* tab2, float* tab3,
-                          float* scratch, hipStream_t st);
+                          float* scratch, hipStream_t st, const int64_t* tau = nullptr);
 int tdx_time_tables_cond(int kind, const float* const* P, const void* cond, int B, int td, float* tabc1, float* tabc2,
                          float* tabc3, float* scratch, hipStream_t st);
 // B0 < B: samples >= B0 go to the second set of destinations (o1b ...), indexed from 0 (half-batch sampling: unet.hip)
 int tdx_sample_head(const int64_t* counter, int32_t* t_idx, int64_t* t_vec, int B, int T, int kind, const float* tab1,
                     const float* tab2, const float* tab3, const float* tc1, const float* tc2, const float* tc3,
                     float* o1, float* o2, float* o3, hipStream_t st, int B0 = 0, float* o1b = nullptr, float* o2b = nullptr,
-                    float* o3b = nullptr);
+                    float* o3b = nullptr, const int64_t* tau = nullptr);
 int tdx_p_sample_step_dec(float* x_out, const float* x, const float* eps, const float* z, const float* coef,
-                          const int32_t* t_idx, int64_t n, uint64_t seed, int64_t* counter_dec, hipStream_t st);
+                          const int32_t* t_idx, int64_t n, uint64_t seed, int64_t* counter_dec, hipStream_t st,
+                          const int64_t* tau = nullptr);
 // latent MLP noise model (latent_diffusion.py:16-128), kind TDX_UNET_LATENT_MLP of tdx_unet_*
 size_t tdx_latent_workspace_floats(int B);
 size_t tdx_latent_infer_ss_floats(void);

@@ -647,15 +647,20 @@ __global__ void iota_i64_kernel(int64_t* __restrict__ out, int n) {
 size_t tdx_time_tables_index_floats(int T) { return (2 * (size_t)T + 3) & ~(size_t)3; }
 
 // tab_t{1,2,3}[t][:] = W_k MLP(t) + b_k for t < T.  scratch: tdx_time_tables_index_floats(T) + 3*T*td floats.
+// tau != null (a timestep schedule of T steps): row k is built at the timestep tau[k] - the schedule is the index list.
 int tdx_time_tables_build(int kind, const float* const* P, int T, int td, float* tab1, float* tab2, float* tab3,
-                          float* scratch, hipStream_t st) {
+                          float* scratch, hipStream_t st, const int64_t* tau) {
   if (td <= 0) td = kind == 1 ? TDL : TD;
   int64_t* tt = reinterpret_cast<int64_t*>(scratch);
   float* sin = scratch + tdx_time_tables_index_floats(T);
   float* pre = sin + (size_t)T * td;
   float* emb = pre + (size_t)T * td;
-  iota_i64_kernel<<<cdiv(T, 256), 256, 0, st>>>(tt, T);
-  TDX_CHECK_LAUNCH();
+  if (tau) {
+    TDX_HIP(hipMemcpyAsync(tt, tau, (size_t)T * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+  } else {
+    iota_i64_kernel<<<cdiv(T, 256), 256, 0, st>>>(tt, T);
+    TDX_CHECK_LAUNCH();
+  }
   return tdx_time_embed_fwd(kind, tt, nullptr, nullptr, P, sin, pre, emb, tab1, tab2, tab3, T, st, td);
 }
 
@@ -693,18 +698,20 @@ int tdx_time_tables_cond(int kind, const float* const* P, const void* cond, int 
 // Head of a reverse step in table mode: t = *counter (read only: the decrement moved to the END of the step, into
 // the update kernel, so that every workgroup here sees the same value); t_idx = t; t_vec[:] = t;
 // tp_k[b][:] = tab_tk[t][:] + tabc_k[b][:].  One launch in place of step_begin + the time MLP + the projections.
+// With a timestep schedule (tau != null) the counter is the step index k: t_idx = k, t_vec[:] = tau[k], and the
+// table (built at the schedule's timesteps) is read at row k.
 __global__ void __launch_bounds__(256)
 sample_head_kernel(const int64_t* __restrict__ counter, int32_t* __restrict__ t_idx, int64_t* __restrict__ t_vec,
                    int B, int T, int w1, int w2, int w3, const float* __restrict__ tab1,
                    const float* __restrict__ tab2, const float* __restrict__ tab3, const float* __restrict__ tc1,
                    const float* __restrict__ tc2, const float* __restrict__ tc3, float* __restrict__ o1,
                    float* __restrict__ o2, float* __restrict__ o3, int B0, float* __restrict__ o1b,
-                   float* __restrict__ o2b, float* __restrict__ o3b) {
+                   float* __restrict__ o2b, float* __restrict__ o3b, const int64_t* __restrict__ tau) {
   const int64_t t64 = *counter;
   const int t = (int)(t64 < 0 ? 0 : t64 >= T ? T - 1 : t64);   // the tables hold T rows
   const int wsum = w1 + w2 + w3;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < B) t_vec[i] = t64;
+  if (i < B) t_vec[i] = tau ? tau[t] : t64;
   if (i == 0) *t_idx = (int32_t)t64;
   if (i >= B * wsum) return;
   const int b = i / wsum, j = i - b * wsum;
@@ -723,12 +730,13 @@ sample_head_kernel(const int64_t* __restrict__ counter, int32_t* __restrict__ t_
 
 int tdx_sample_head(const int64_t* counter, int32_t* t_idx, int64_t* t_vec, int B, int T, int kind, const float* tab1,
                     const float* tab2, const float* tab3, const float* tc1, const float* tc2, const float* tc3,
-                    float* o1, float* o2, float* o3, hipStream_t st, int B0, float* o1b, float* o2b, float* o3b) {
+                    float* o1, float* o2, float* o3, hipStream_t st, int B0, float* o1b, float* o2b, float* o3b,
+                    const int64_t* tau) {
   const int w1 = kind == 1 ? 64 : 128, w2 = 2 * w1, w3 = 4 * w1;
   if (B0 <= 0 || B0 >= B || !o1b) { B0 = B; o1b = o1; o2b = o2; o3b = o3; }
   sample_head_kernel<<<cdiv((int64_t)B * (w1 + w2 + w3), 256), 256, 0, st>>>(counter, t_idx, t_vec, B, T, w1, w2, w3,
                                                                               tab1, tab2, tab3, tc1, tc2, tc3, o1, o2, o3,
-                                                                              B0, o1b, o2b, o3b);
+                                                                              B0, o1b, o2b, o3b, tau);
   TDX_CHECK_LAUNCH();
   return 0;
 }

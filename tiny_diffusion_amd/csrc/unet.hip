@@ -231,9 +231,10 @@ struct tdx_unet {
   size_t tab_floats;
   int tab_T, tab_batch, tab_gen, pack_gen;
   const void* tab_cond;
+  const int64_t* tab_tau;   // timestep schedule the T rows were built at (tdx_unet_prepare_sampling_sched); null: t = 0..T-1
   bool skip_time_path;   // set by tdx_unet_eval_step around its forward: the projections are already in the workspace
   // set by tdx_unet_eval_step around its forward: final_conv applies the reverse-process update in its epilogue
-  struct PS { float* x; const float* z; const float* coef; const int32_t* t_idx; uint64_t seed; int philox; int64_t* counter_dec; int64_t elem0; } ps;
+  struct PS { float* x; const float* z; const float* coef; const int32_t* t_idx; uint64_t seed; int philox; int64_t* counter_dec; int64_t elem0; const int64_t* tau; } ps;
   // half-batch inference (tdx_unet_forward, INFER mode): the second half runs on this stream, forked from / joined to the caller's
   hipStream_t half_own;
   hipEvent_t ev_h_fork, ev_h_join;
@@ -378,6 +379,7 @@ extern "C" int tdx_unet_create_full(tdx_unet** out, int max_batch, int kind, int
   u->tab_gen = -1;
   u->pack_gen = 0;
   u->tab_cond = nullptr;
+  u->tab_tau = nullptr;
   u->skip_time_path = false;
   u->ps = {};
   u->precision = TDX_PREC_F32;
@@ -950,7 +952,8 @@ static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const
                              S.out_hw, S.out_hw, 64, 64, 0, io16, stream));
   if (infer && ps.x)
     RC(tdx_final_conv_fwd_psample(ws + L.d1a, P[TDX_P_FINAL_W], P[TDX_P_FINAL_B], out, B, S.out_hw, S.out_hw, S.in_ch,
-                                  ps.x, ps.z, ps.coef, ps.t_idx, ps.seed, ps.philox, ps.counter_dec, st, io16, ps.elem0));
+                                  ps.x, ps.z, ps.coef, ps.t_idx, ps.seed, ps.philox, ps.counter_dec, st, io16, ps.elem0,
+                                  ps.tau));
   else
     RC(tdx_final_conv_fwd(ws + L.d1a, P[TDX_P_FINAL_W], P[TDX_P_FINAL_B], out, B, S.out_hw, S.out_hw, S.in_ch, st, io16));
 
@@ -1317,18 +1320,20 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
   return 0;
 }
 
-extern "C" int tdx_unet_eval_step(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
-                                  const void* cond, const float* z, const float* coef, int64_t* counter,
-                                  int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
-                                  void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed,
-                                  tdx_stream_t stream) {
+// tau == null: the step counter is the timestep t (tdx_unet_eval_step).  tau != null: a schedule of n_steps steps
+// (tdx_unet_eval_step_sched) - the counter is the step index k, the coefficient row, and the network runs at tau[k].
+static int eval_step_impl(tdx_unet* u, const void* const* params, void* const* buffers, float* x, const void* cond,
+                          const float* z, const float* coef, const int64_t* tau, int n_steps, int64_t* counter, int32_t* t_idx,
+                          int64_t* t_vec, float* eps, int64_t n_elems, void* workspace, size_t workspace_bytes,
+                          int batch, uint64_t philox_seed, tdx_stream_t stream) {
   if (!u || !x || !coef || !counter || !t_idx || !t_vec || !eps || batch <= 0 || n_elems <= 0)
     return TDX_E_BADARG;
   // Table mode (tdx_unet_prepare_sampling was called for this pack, batch and cond): ONE head kernel sets t and
   // adds two table rows per sample into the workspace's projection slots - in place of step_begin, the time MLP and
   // the three projections - and the update kernel advances the counter.
+  // (an identity table never serves a scheduled step nor the other way round: the schedule pointer and length match)
   const bool tab = u->spec && u->tab && u->packed && u->tab_gen == u->pack_gen && u->tab_batch == batch &&
-                   u->tab_cond == cond && workspace &&
+                   u->tab_cond == cond && u->tab_tau == tau && (!tau || u->tab_T == n_steps) && workspace &&
                    workspace_bytes >= make_layout(*u->spec, batch).total * sizeof(float);
   if (tab) {
     const NetSpec& S = *u->spec;
@@ -1347,18 +1352,20 @@ extern "C" int tdx_unet_eval_step(tdx_unet* u, const void* const* params, void* 
       float* ws1 = ws + L0.total;
       RC(tdx_sample_head(counter, t_idx, t_vec, batch, u->tab_T, u->kind, t1, t2, t3, c1, c2, c3, ws + L0.tp[0],
                          ws + L0.tp[1], ws + L0.tp[2], to_stream(stream), b0, ws1 + L1.tp[0], ws1 + L1.tp[1],
-                         ws1 + L1.tp[2]));
+                         ws1 + L1.tp[2], tau));
     } else {
       RC(tdx_sample_head(counter, t_idx, t_vec, batch, u->tab_T, u->kind, t1, t2, t3, c1, c2, c3, ws + L.tp[0],
-                         ws + L.tp[1], ws + L.tp[2], to_stream(stream)));
+                         ws + L.tp[1], ws + L.tp[2], to_stream(stream), 0, nullptr, nullptr, nullptr, tau));
     }
+  } else if (tau) {
+    RC(tdx_step_begin_sched(counter, tau, t_idx, t_vec, batch, stream));
   } else {
     RC(tdx_step_begin(counter, t_idx, t_vec, batch, stream));
   }
   u->skip_time_path = tab;
   // the UNets apply the update in final_conv's epilogue (one launch less); the latent MLP keeps the separate kernel
   const bool fuse_ps = u->spec && (g_tdx_sample_fuse & 4) && n_elems == (int64_t)batch * u->spec->in_ch * u->spec->out_hw * u->spec->out_hw;
-  if (fuse_ps) u->ps = {x, z, coef, t_idx, philox_seed, z ? 0 : 1, tab ? counter : nullptr, 0};
+  if (fuse_ps) u->ps = {x, z, coef, t_idx, philox_seed, z ? 0 : 1, tab ? counter : nullptr, 0, tau};
   const int rc = tdx_unet_forward(u, params, buffers, x, t_vec, cond, eps, workspace, workspace_bytes, batch,
                                   TDX_MODE_INFER, stream);
   u->skip_time_path = false;
@@ -1366,17 +1373,40 @@ extern "C" int tdx_unet_eval_step(tdx_unet* u, const void* const* params, void* 
   if (rc) return rc;
   if (fuse_ps) return 0;
   // elementwise, so x is updated in place; both kernels skip the noise term at t == 0
-  if (tab) return tdx_p_sample_step_dec(x, x, eps, z, coef, t_idx, n_elems, philox_seed, counter, to_stream(stream));
+  if (tab) return tdx_p_sample_step_dec(x, x, eps, z, coef, t_idx, n_elems, philox_seed, counter, to_stream(stream), tau);
+  if (tau) {
+    if (z) return tdx_p_sample_step_sched(x, x, eps, z, coef, tau, t_idx, n_elems, stream);
+    return tdx_p_sample_step_sched_philox(x, x, eps, coef, tau, t_idx, n_elems, philox_seed, stream);
+  }
   if (z) return tdx_p_sample_step(x, x, eps, z, coef, t_idx, n_elems, stream);
   return tdx_p_sample_step_philox(x, x, eps, coef, t_idx, n_elems, philox_seed, stream);
+}
+
+extern "C" int tdx_unet_eval_step(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
+                                  const void* cond, const float* z, const float* coef, int64_t* counter,
+                                  int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
+                                  void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed,
+                                  tdx_stream_t stream) {
+  return eval_step_impl(u, params, buffers, x, cond, z, coef, nullptr, 0, counter, t_idx, t_vec, eps, n_elems,
+                        workspace, workspace_bytes, batch, philox_seed, stream);
+}
+
+extern "C" int tdx_unet_eval_step_sched(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
+                                        const void* cond, const float* z, const float* coef, const int64_t* tau, int S,
+                                        int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
+                                        void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed,
+                                        tdx_stream_t stream) {
+  if (!tau || S <= 0) return TDX_E_BADARG;
+  return eval_step_impl(u, params, buffers, x, cond, z, coef, tau, S, counter, t_idx, t_vec, eps, n_elems, workspace,
+                        workspace_bytes, batch, philox_seed, stream);
 }
 
 // Build the sampling tables for the CURRENT INFER pack (call after tdx_unet_pack / the first INFER forward, once
 // per sample() call, outside any stream capture: it may allocate).  T = number of diffusion steps (the counter
 // handed to tdx_unet_eval_step must stay below it); cond = the labels / text embeddings the eval steps will be
 // given (the same pointer: the cond part is computed from its contents NOW).
-extern "C" int tdx_unet_prepare_sampling(tdx_unet* u, const void* const* params, const void* cond, int batch, int T,
-                                         tdx_stream_t stream) {
+static int prepare_sampling_impl(tdx_unet* u, const void* const* params, const void* cond, int batch, int T,
+                                 const int64_t* tau, tdx_stream_t stream) {
   if (!u || !params || batch <= 0 || batch > u->max_batch || T <= 0) return TDX_E_BADARG;
   if (!u->spec) return TDX_E_SHAPE;   // the latent MLP runs its own fused time path
   const bool needs_cond = u->kind == 1 || u->num_classes > 0;
@@ -1407,14 +1437,28 @@ extern "C" int tdx_unet_prepare_sampling(tdx_unet* u, const void* const* params,
   float* c2 = c1 + (size_t)batch * S.skip_ch[0];
   float* c3 = c2 + (size_t)batch * S.skip_ch[1];
   float* scr = c3 + (size_t)batch * S.skip_ch[2];
-  if (u->tab_gen != u->pack_gen || u->tab_T != T || u->tab_batch != batch)   // (the cond block moves with T and batch)
-    RC(tdx_time_tables_build(u->kind, P, T, S.time_dim, t1, t2, t3, scr, st));
+  // (the cond block moves with T and batch; a schedule is rebuilt on every call: its contents may change under the
+  // same pointer, and S rows cost little)
+  if (u->tab_gen != u->pack_gen || u->tab_T != T || u->tab_batch != batch || tau || u->tab_tau)
+    RC(tdx_time_tables_build(u->kind, P, T, S.time_dim, t1, t2, t3, scr, st, tau));
   if (cond) RC(tdx_time_tables_cond(u->kind, P, cond, batch, S.time_dim, c1, c2, c3, scr, st));
   u->tab_T = T;
   u->tab_batch = batch;
   u->tab_cond = cond;
+  u->tab_tau = tau;
   u->tab_gen = u->pack_gen;
   return 0;
+}
+
+extern "C" int tdx_unet_prepare_sampling(tdx_unet* u, const void* const* params, const void* cond, int batch, int T,
+                                         tdx_stream_t stream) {
+  return prepare_sampling_impl(u, params, cond, batch, T, nullptr, stream);
+}
+
+extern "C" int tdx_unet_prepare_sampling_sched(tdx_unet* u, const void* const* params, const void* cond, int batch,
+                                               const int64_t* tau, int S, tdx_stream_t stream) {
+  if (!tau) return TDX_E_BADARG;
+  return prepare_sampling_impl(u, params, cond, batch, S, tau, stream);
 }
 
 extern "C" int tdx_unet_request_input_grad(tdx_unet* u, float* g_x) {

@@ -5,10 +5,10 @@ from __future__ import annotations
 
 import torch
 
-from .schedule import ForwardProcess, sample_loop
+from .schedule import ForwardProcess, ddim_sample_loop, sample_loop
 from .unet import NoiseModelBase, TIME_DIM
 
-__all__ = ["NoiseModel", "ForwardProcess", "sample"]
+__all__ = ["NoiseModel", "ForwardProcess", "sample", "ddim_sample"]
 
 
 class NoiseModel(NoiseModelBase):
@@ -26,3 +26,13 @@ def sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples
     """diffusion.py:254-276: leaves the model in eval mode, returns x_0 in ~[-1, 1].
     Extra keyword arguments (x_T, noises, use_graph, philox_seed) are extensions."""
     return sample_loop(noise_model, diffusion, device, n_samples, None, **kw)
+
+
+@torch.no_grad()
+def ddim_sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples=16, steps=50, eta=0.0,
+                timesteps=None, **kw):
+    """DDIM sampling (Song et al. 2021) of a model trained with ``diffusion``: ``sample()``'s contract over
+    ``steps`` timesteps (or the explicit list ``timesteps``) with stochasticity ``eta`` (schedule.ddim_schedule).
+    The same extension keywords as ``sample()``."""
+    return ddim_sample_loop(noise_model, diffusion, device, n_samples, None, steps=steps, eta=eta,
+                            timesteps=timesteps, **kw)

@@ -7,11 +7,11 @@ from __future__ import annotations
 
 import torch
 
-from .schedule import ForwardProcess, sample_loop
+from .schedule import ForwardProcess, ddim_sample_loop, sample_loop
 from .unet import ARCH_LATENT, NoiseModelBase
 from .vae import VAE, VAEConfig
 
-__all__ = ["NoiseModel", "ForwardProcess", "sample", "VAE", "VAEConfig"]
+__all__ = ["NoiseModel", "ForwardProcess", "sample", "ddim_sample", "VAE", "VAEConfig"]
 
 
 class NoiseModel(NoiseModelBase):
@@ -32,10 +32,25 @@ class NoiseModel(NoiseModelBase):
 def sample(vae: VAE, noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples=16, y=None, **kw):
     """latent_diffusion.py:308-347: reverse loop over z (n,20), then ``vae.decode(z)`` viewed
     as (n,1,28,28); same argument errors."""
+    _check_labels(y, n_samples)
+    vae.eval()
+    z = sample_loop(noise_model, diffusion, device, n_samples, y, **kw)
+    return vae.decode(z).view(-1, 1, 28, 28)
+
+
+@torch.no_grad()
+def ddim_sample(vae: VAE, noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples=16, y=None, steps=50,
+                eta=0.0, timesteps=None, **kw):
+    """DDIM sampling (Song et al. 2021): ``sample()``'s contract, argument errors and VAE decode over ``steps``
+    timesteps (or the explicit list ``timesteps``) with stochasticity ``eta`` (schedule.ddim_schedule)."""
+    _check_labels(y, n_samples)
+    vae.eval()
+    z = ddim_sample_loop(noise_model, diffusion, device, n_samples, y, steps=steps, eta=eta, timesteps=timesteps, **kw)
+    return vae.decode(z).view(-1, 1, 28, 28)
+
+
+def _check_labels(y, n_samples):
     if y is None:
         raise ValueError("Class labels 'y' must be provided for conditional generation.")
     if y.shape[0] != n_samples:
         raise ValueError("y must have shape (n_samples,)")
-    vae.eval()
-    z = sample_loop(noise_model, diffusion, device, n_samples, y, **kw)
-    return vae.decode(z).view(-1, 1, 28, 28)

@@ -1,10 +1,13 @@
 """Forward process (noise schedule + q_sample) and the reverse sampling loop,
 mirroring ForwardProcess / sample() of the reference (diffusion.py:165-190,
-254-276; conditional_diffusion.py:174-199, 354-386) on libtdx kernels."""
+254-276; conditional_diffusion.py:174-199, 354-386) on libtdx kernels, and
+timestep schedules for DDIM sampling (Song et al. 2021) on the same kernels."""
 from __future__ import annotations
 
+import numbers
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -95,10 +98,131 @@ def p_sample_step(diffusion: ForwardProcess, x, eps, t_idx, z=None, out=None):
     return out
 
 
+class TimestepSchedule:
+    """A reverse chain over a subset of the T timesteps: step k = S-1 .. 0 runs the network at
+    ``timesteps[k]`` and applies ``x' = c1 (x - c2 eps) + sigma z`` with row k of ``coef``
+    (no noise term at k = 0).  Built by ``ddim_schedule`` / ``ddpm_schedule``.
+
+    ``timesteps``: int64 (S,), strictly ascending.  ``coef``: fp32 (S, 3) rows (c1, c2, sigma).
+    ``coef64``: the fp64 values ``coef`` was rounded from.  Device copies are cached per device:
+    the step index k lives in device memory and the kernels map it to ``timesteps[k]``."""
+
+    def __init__(self, num_timesteps: int, timesteps, coef64, coef=None, eta=None):
+        self.num_timesteps = int(num_timesteps)
+        self.timesteps = timesteps
+        self.coef64 = coef64
+        self.coef = coef64.to(torch.float32).contiguous() if coef is None else coef
+        self.eta = eta
+        self._dev = {}
+
+    @property
+    def steps(self) -> int:
+        return int(self.timesteps.shape[0])
+
+    def device_tables(self, device):
+        """(timesteps int64 [S], coef fp32 [S,3]) on ``device``."""
+        device = torch.device(device)
+        key = (device.type, device.index)
+        tb = self._dev.get(key)
+        if tb is None:
+            tb = (self.timesteps.to(device).contiguous(), self.coef.to(device).contiguous())
+            self._dev[key] = tb
+        return tb
+
+
+def _timestep_list(timesteps, T: int):
+    if isinstance(timesteps, torch.Tensor):
+        if timesteps.is_floating_point() or timesteps.is_complex() or timesteps.dtype == torch.bool:
+            raise ValueError("timesteps must be integers")
+        vals = timesteps.reshape(-1).tolist()
+    elif isinstance(timesteps, np.ndarray):
+        if timesteps.dtype.kind not in "iu":
+            raise ValueError("timesteps must be integers")
+        vals = timesteps.reshape(-1).tolist()
+    else:
+        vals = list(timesteps)
+        if any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in vals):
+            raise ValueError("timesteps must be integers")
+        vals = [int(v) for v in vals]
+    if not vals:
+        raise ValueError("timesteps must not be empty")
+    if any(b <= a for a, b in zip(vals, vals[1:])):
+        raise ValueError("timesteps must be strictly ascending (sorted, no duplicates)")
+    if vals[0] < 0 or vals[-1] >= T:
+        raise ValueError(f"timesteps must lie in [0, {T})")
+    return vals
+
+
+def ddim_schedule(diffusion: ForwardProcess, steps: Optional[int] = None, timesteps=None,
+                  eta: float = 0.0) -> TimestepSchedule:
+    """DDIM sampling schedule (Song et al. 2021, eq. 12) for a model trained on ``diffusion``.
+
+    ``steps=S`` (1 <= S <= T): ``tau_i = floor(i * T / S)`` - Song et al.'s ``range(0, T, T // S)`` when S
+    divides T, the identity at S = T.  ``timesteps``: an explicit strictly ascending list in [0, T).
+    ``eta``: 0 is deterministic DDIM, 1 the DDPM-like posterior variance.
+
+    In fp64 from the reference-exact fp32 ``alphas_cumprod``, with ab = acp[tau_k] and ab_prev =
+    acp[tau_{k-1}] (1 at k = 0):
+
+        sigma = eta * sqrt((1 - ab_prev) / (1 - ab)) * sqrt(1 - ab / ab_prev)
+        x0    = (x - sqrt(1 - ab) eps) / sqrt(ab)
+        x'    = sqrt(ab_prev) x0 + sqrt(1 - ab_prev - sigma^2) eps + sigma z          (x0 form)
+              = c1 (x - c2 eps) + sigma z                                               (kernel form)
+        c1 = sqrt(ab_prev / ab),  c2 = sqrt(1 - ab) - sqrt(ab / ab_prev) sqrt(1 - ab_prev - sigma^2)
+
+    The kernel form is the x0 form multiplied out; ``coef`` holds (c1, c2, sigma) rounded to fp32.
+    Raises ``ValueError`` for both or neither of ``steps`` / ``timesteps``, a bad step count or list, eta < 0,
+    or a row with 1 - ab_prev - sigma^2 < 0 (eta too large for the spacing)."""
+    T = int(diffusion.num_timesteps)
+    if steps is not None and timesteps is not None:
+        raise ValueError("give steps or timesteps, not both")
+    if timesteps is None:
+        if steps is None:
+            raise ValueError("give steps or timesteps")
+        if isinstance(steps, bool) or not isinstance(steps, numbers.Integral) or not 1 <= steps <= T:
+            raise ValueError(f"steps must be an integer in [1, {T}]")
+        S = int(steps)
+        tau = [i * T // S for i in range(S)]
+    else:
+        tau = _timestep_list(timesteps, T)
+    eta = float(eta)
+    if not eta >= 0.0:
+        raise ValueError("eta must be >= 0")
+    acp = diffusion.alphas_cumprod.to(torch.float64)
+    idx = torch.tensor(tau, dtype=torch.int64)
+    ab = acp[idx]
+    ab_prev = torch.cat([torch.ones(1, dtype=torch.float64), ab[:-1]])
+    sigma = eta * torch.sqrt((1 - ab_prev) / (1 - ab)) * torch.sqrt(1 - ab / ab_prev)
+    rem = 1 - ab_prev - sigma * sigma
+    if (rem < 0).any():
+        k = int(torch.nonzero(rem < 0)[0])
+        raise ValueError(f"eta = {eta} is too large for this spacing: 1 - ab_prev - sigma^2 < 0 at step {k}")
+    c1 = torch.sqrt(ab_prev / ab)
+    c2 = torch.sqrt(1 - ab) - torch.sqrt(ab / ab_prev) * torch.sqrt(rem)
+    coef64 = torch.stack([c1, c2, sigma], dim=1).contiguous()
+    return TimestepSchedule(T, idx, coef64, eta=eta)
+
+
+def ddpm_schedule(diffusion: ForwardProcess) -> TimestepSchedule:
+    """The reference's own update as a schedule: ``timesteps = arange(T)`` and the coefficient rows of
+    ``diffusion.tables`` (bit for bit).  ``sample_loop(schedule=ddpm_schedule(fp))`` equals ``sample_loop()``."""
+    coef = diffusion.tables("cpu")[2].clone()
+    return TimestepSchedule(diffusion.num_timesteps, torch.arange(diffusion.num_timesteps, dtype=torch.int64),
+                            coef.to(torch.float64), coef=coef)
+
+
+def ddim_sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, y=None, steps: int = 50,
+                     eta: float = 0.0, timesteps=None, **kw):
+    """``sample_loop`` on ``ddim_schedule(diffusion, steps | timesteps, eta)``: ``timesteps``, when given,
+    replaces ``steps``.  The drop-in modules' ``ddim_sample`` functions call this."""
+    sched = ddim_schedule(diffusion, steps=None if timesteps is not None else steps, timesteps=timesteps, eta=eta)
+    return sample_loop(noise_model, diffusion, device, n_samples, y, schedule=sched, **kw)
+
+
 @torch.no_grad()
 def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, y=None,
                 x_T: Optional[torch.Tensor] = None, noises=None, use_graph: bool = False,
-                philox_seed: Optional[int] = None):
+                philox_seed: Optional[int] = None, schedule: Optional[TimestepSchedule] = None):
     """Reverse process, diffusion.py:254-276.
 
     Default (``x_T is None and noises is None``): the reference's RNG consumption -
@@ -110,7 +234,12 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
     and replay it T times; the step index lives in device memory.  Together with
     ``philox_seed`` the index is also advanced on the device and each graph holds
     ``GRAPH_STEPS`` consecutive steps (no host work between steps).
+    ``schedule``: a ``TimestepSchedule`` (DDIM, ``ddim_schedule``): S steps k = S-1..0 at the timesteps
+    ``schedule.timesteps[k]`` in the same three modes; recorded noise is ``noises[timesteps[k]]``.
     """
+    if schedule is not None:
+        return _sample_loop_sched(noise_model, diffusion, schedule, device, n_samples, y, x_T, noises, use_graph,
+                                  philox_seed)
     device = torch.device(device)
     if device.type != "cuda":
         raise _lib.TdxError("sampling runs on the GPU only (no CPU fallback)")
@@ -206,6 +335,116 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
         t_vec.fill_(t)
         if philox_seed is None:
             if t > 0:
+                if noises is not None:
+                    zbuf.copy_(noises[t].to(device))
+                else:
+                    zbuf.copy_(torch.randn_like(x))
+            else:
+                zbuf.zero_()
+        if graph is not None:
+            graph.replay()
+        else:
+            step_kernels(True)
+    return x
+
+
+def _sample_loop_sched(noise_model, diffusion, schedule, device, n_samples, y, x_T, noises, use_graph, philox_seed):
+    """sample_loop over a timestep schedule: the counter / t_idx hold the step index k (the coefficient row), t_vec
+    the network's timestep tau[k]; the kernels map k to tau[k] for the noise key (tdx_*_sched)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.TdxError("sampling runs on the GPU only (no CPU fallback)")
+    if schedule.num_timesteps != diffusion.num_timesteps:
+        raise ValueError(f"the schedule was built for T = {schedule.num_timesteps}, the diffusion has "
+                         f"T = {diffusion.num_timesteps}")
+    noise_model.eval()
+    shape = tuple(getattr(getattr(noise_model, "_arch", None), "in_shape", (1, 28, 28)))
+    x = (torch.randn(n_samples, *shape) if x_T is None else x_T).to(device).float().contiguous()
+    if y is not None:
+        y = y.to(device)
+    if n_samples == 0:
+        return x
+    S = schedule.steps
+    taus = schedule.timesteps.tolist()
+    tau, coef = schedule.device_tables(device)
+    t_idx = torch.empty(1, dtype=torch.int32, device=device)
+    t_vec = torch.empty(n_samples, dtype=torch.int64, device=device)
+    st = lambda: torch.cuda.current_stream(device).cuda_stream  # noqa: E731
+    zbuf = torch.empty_like(x)
+
+    def step_kernels(use_z: bool):
+        eps = noise_model._run_forward(x, t_vec, y, mode=2)[0]
+        if philox_seed is not None:
+            check(lib.tdx_p_sample_step_sched_philox(x.data_ptr(), x.data_ptr(), eps.data_ptr(), coef.data_ptr(),
+                                                     tau.data_ptr(), t_idx.data_ptr(), x.numel(), philox_seed, st()),
+                  "tdx_p_sample_step_sched_philox")
+        else:
+            check(lib.tdx_p_sample_step_sched(x.data_ptr(), x.data_ptr(), eps.data_ptr(),
+                                              zbuf.data_ptr() if use_z else None, coef.data_ptr(), tau.data_ptr(),
+                                              t_idx.data_ptr(), x.numel(), st()), "tdx_p_sample_step_sched")
+
+    def capture(fn, warm, counter=None):
+        """Warm up with ``warm`` (one step) on a side stream, restore x (and the counter), capture ``fn``."""
+        side = torch.cuda.Stream(device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        x_keep = x.clone()
+        c_keep = None if counter is None else counter.clone()
+        with torch.cuda.stream(side):
+            warm()
+        torch.cuda.current_stream(device).wait_stream(side)
+        x.copy_(x_keep)
+        if counter is not None:
+            counter.copy_(c_keep)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            fn()
+        return g
+
+    if use_graph and philox_seed is not None:
+        counter = torch.empty(1, dtype=torch.int64, device=device)
+        eps_buf = torch.empty_like(x)
+        y_dev = None
+        if y is not None:
+            kind_laion = getattr(getattr(noise_model, "_arch", None), "kind", 0) == 1
+            y_dev = y.contiguous().float() if kind_laion else y.contiguous().to(torch.int64)
+        one_call = hasattr(noise_model, "_run_eval_step")
+
+        def steps(k):
+            def run():
+                for _ in range(k):
+                    if one_call:
+                        noise_model._run_eval_step(x, y_dev, coef, counter, t_idx, t_vec, eps_buf,
+                                                   philox_seed=philox_seed, tau=tau, S=S)
+                        continue
+                    check(lib.tdx_step_begin_sched(counter.data_ptr(), tau.data_ptr(), t_idx.data_ptr(),
+                                                   t_vec.data_ptr(), n_samples, st()), "tdx_step_begin_sched")
+                    step_kernels(False)
+            return run
+
+        if one_call and hasattr(noise_model, "_prepare_sampling"):
+            noise_model._prepare_sampling(x, y_dev, S, tau=tau)
+        unroll = min(GRAPH_STEPS, S)
+        counter.fill_(S - 1)
+        graph = capture(steps(unroll), steps(1), counter)
+        tail = S % unroll
+        tail_graph = capture(steps(tail), lambda: None) if tail else None
+        counter.fill_(S - 1)
+        for _ in range(S // unroll):
+            graph.replay()
+        if tail_graph is not None:
+            tail_graph.replay()
+        return x
+
+    graph = None
+    if use_graph:
+        t_idx.fill_(S - 1); t_vec.fill_(taus[S - 1])
+        graph = capture(lambda: step_kernels(True), lambda: step_kernels(True))
+    for k in reversed(range(S)):
+        t = taus[k]
+        t_idx.fill_(k)
+        t_vec.fill_(t)
+        if philox_seed is None:
+            if k > 0:
                 if noises is not None:
                     zbuf.copy_(noises[t].to(device))
                 else:

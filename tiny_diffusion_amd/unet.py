@@ -522,9 +522,11 @@ class NoiseModelBase(nn.Module):
             check(lib.tdx_unet_pack(plan.handle, pptr, bptr, st), "tdx_unet_pack")
             plan.infer_key = key
 
-    def _run_eval_step(self, x, y, coef, counter, t_idx, t_vec, eps, z=None, philox_seed: int = 0):
+    def _run_eval_step(self, x, y, coef, counter, t_idx, t_vec, eps, z=None, philox_seed: int = 0, tau=None,
+                       S: int = 0):
         """One reverse step of sample() in place on ``x`` (tdx_unet_eval_step): the step index is
-        read from and decremented in device memory, so the call can sit in a HIP graph."""
+        read from and decremented in device memory, so the call can sit in a HIP graph.  ``tau``: the
+        device timesteps of a schedule of ``S`` steps (tdx_unet_eval_step_sched; ``coef`` is then (S,3))."""
         B = x.shape[0]
         plan = self._plan(B, x.device, self._input_hw(x))
         self._apply_precision(plan)
@@ -532,18 +534,26 @@ class NoiseModelBase(nn.Module):
         bptr, btens = self._buffer_ptrs()
         st = torch.cuda.current_stream(x.device).cuda_stream
         self._refresh_infer_pack(plan, pptr, ptens, bptr, btens, st)
+        if tau is not None:
+            check(lib.tdx_unet_eval_step_sched(plan.handle, pptr, bptr, x.data_ptr(), None if y is None else y.data_ptr(),
+                                               None if z is None else z.data_ptr(), coef.data_ptr(), tau.data_ptr(),
+                                               int(S), counter.data_ptr(), t_idx.data_ptr(), t_vec.data_ptr(),
+                                               eps.data_ptr(), x.numel(), plan.workspace.data_ptr(), plan.ws_bytes, B,
+                                               philox_seed, st), "tdx_unet_eval_step_sched")
+            return
         check(lib.tdx_unet_eval_step(plan.handle, pptr, bptr, x.data_ptr(), None if y is None else y.data_ptr(),
                                      None if z is None else z.data_ptr(), coef.data_ptr(), counter.data_ptr(),
                                      t_idx.data_ptr(), t_vec.data_ptr(), eps.data_ptr(), x.numel(),
                                      plan.workspace.data_ptr(), plan.ws_bytes, B, philox_seed, st),
               "tdx_unet_eval_step")
 
-    def _prepare_sampling(self, x, y, T: int):
+    def _prepare_sampling(self, x, y, T: int, tau=None):
         """Once per sample() call, before the reverse loop (and before any graph capture): the per-t table of
         ``time_proj_k(time MLP(t))`` and the per-sample table of ``W_k c`` (c = class / text embedding), so that
         every reverse step replaces the time path's launches by one look-up (tdx_unet_prepare_sampling; SURVEY.md 7:
         the projections are linear in the embedding).  ``y`` must be the very tensor later handed to
-        ``_run_eval_step`` (the tables are tied to its pointer).  No-op for the latent MLP."""
+        ``_run_eval_step`` (the tables are tied to its pointer).  ``tau``: device timesteps of a schedule of ``T``
+        steps, the table rows are then built at them (tdx_unet_prepare_sampling_sched).  No-op for the latent MLP."""
         if self._arch.kind == KIND_LATENT:
             return
         B = x.shape[0]
@@ -553,6 +563,10 @@ class NoiseModelBase(nn.Module):
         bptr, btens = self._buffer_ptrs()
         st = torch.cuda.current_stream(x.device).cuda_stream
         self._refresh_infer_pack(plan, pptr, ptens, bptr, btens, st)
+        if tau is not None:
+            check(lib.tdx_unet_prepare_sampling_sched(plan.handle, pptr, None if y is None else y.data_ptr(), B,
+                                                      tau.data_ptr(), int(T), st), "tdx_unet_prepare_sampling_sched")
+            return
         check(lib.tdx_unet_prepare_sampling(plan.handle, pptr, None if y is None else y.data_ptr(), B, int(T), st),
               "tdx_unet_prepare_sampling")
 
