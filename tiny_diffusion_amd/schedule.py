@@ -12,6 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import lib, check
+from .unet import _cond_tensor
 
 
 GRAPH_STEPS = 10  # reverse steps per captured graph in the device-counter mode
@@ -237,12 +238,12 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
     ``schedule``: a ``TimestepSchedule`` (DDIM, ``ddim_schedule``): S steps k = S-1..0 at the timesteps
     ``schedule.timesteps[k]`` in the same three modes; recorded noise is ``noises[timesteps[k]]``.
     """
-    if schedule is not None:
-        return _sample_loop_sched(noise_model, diffusion, schedule, device, n_samples, y, x_T, noises, use_graph,
-                                  philox_seed)
     device = torch.device(device)
     if device.type != "cuda":
         raise _lib.TdxError("sampling runs on the GPU only (no CPU fallback)")
+    if schedule is not None and schedule.num_timesteps != diffusion.num_timesteps:
+        raise ValueError(f"the schedule was built for T = {schedule.num_timesteps}, the diffusion has "
+                         f"T = {diffusion.num_timesteps}")
     noise_model.eval()
     shape = tuple(getattr(getattr(noise_model, "_arch", None), "in_shape", (1, 28, 28)))
     x = (torch.randn(n_samples, *shape) if x_T is None else x_T).to(device).float().contiguous()
@@ -250,34 +251,58 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
         y = y.to(device)
     if n_samples == 0:
         return x  # nothing to denoise (the reference loops over empty tensors)
-    T = diffusion.num_timesteps
-    _, _, coef = diffusion.tables(device)
+    # S steps k = S-1 .. 0: the counter / t_idx hold k (the coefficient row), t_vec the network's timestep taus[k].
+    # tau is None on the reference's chain (k is the timestep: the plain C entries); with a schedule the kernels map
+    # k to tau[k] themselves (tdx_*_sched).
+    if schedule is None:
+        S = diffusion.num_timesteps
+        taus, tau, coef = range(S), None, diffusion.tables(device)[2]
+    else:
+        S, taus = schedule.steps, schedule.timesteps.tolist()
+        tau, coef = schedule.device_tables(device)
     t_idx = torch.empty(1, dtype=torch.int32, device=device)
     t_vec = torch.empty(n_samples, dtype=torch.int64, device=device)
     st = lambda: torch.cuda.current_stream(device).cuda_stream  # noqa: E731
     zbuf = torch.empty_like(x)
 
+    def update(eps, z):
+        """x <- c1 (x - c2 eps) + sigma z, elementwise and in place; Philox noise in the kernel under a seed."""
+        xp, ep, cp, kp, n = x.data_ptr(), eps.data_ptr(), coef.data_ptr(), t_idx.data_ptr(), x.numel()
+        if tau is None and philox_seed is not None:
+            check(lib.tdx_p_sample_step_philox(xp, xp, ep, cp, kp, n, philox_seed, st()), "tdx_p_sample_step")
+        elif tau is None:
+            check(lib.tdx_p_sample_step(xp, xp, ep, z, cp, kp, n, st()), "tdx_p_sample_step")
+        elif philox_seed is not None:
+            check(lib.tdx_p_sample_step_sched_philox(xp, xp, ep, cp, tau.data_ptr(), kp, n, philox_seed, st()),
+                  "tdx_p_sample_step_sched_philox")
+        else:
+            check(lib.tdx_p_sample_step_sched(xp, xp, ep, z, cp, tau.data_ptr(), kp, n, st()),
+                  "tdx_p_sample_step_sched")
+
+    def step_begin(counter):
+        """t_idx <- counter, t_vec <- its timestep, counter <- counter - 1, on the device."""
+        cp, kp, tp = counter.data_ptr(), t_idx.data_ptr(), t_vec.data_ptr()
+        if tau is None:
+            check(lib.tdx_step_begin(cp, kp, tp, n_samples, st()), "tdx_step_begin")
+        else:
+            check(lib.tdx_step_begin_sched(cp, tau.data_ptr(), kp, tp, n_samples, st()), "tdx_step_begin_sched")
+
     def step_kernels(use_z: bool):
         eps = noise_model._run_forward(x, t_vec, y, mode=2)[0]
-        # the update is elementwise: x is overwritten in place
-        if philox_seed is not None:
-            check(lib.tdx_p_sample_step_philox(x.data_ptr(), x.data_ptr(), eps.data_ptr(), coef.data_ptr(),
-                                               t_idx.data_ptr(), x.numel(), philox_seed, st()), "tdx_p_sample_step")
-        else:
-            check(lib.tdx_p_sample_step(x.data_ptr(), x.data_ptr(), eps.data_ptr(),
-                                        zbuf.data_ptr() if use_z else None, coef.data_ptr(), t_idx.data_ptr(),
-                                        x.numel(), st()), "tdx_p_sample_step")
+        update(eps, zbuf.data_ptr() if use_z else None)
 
-    def capture(fn):
-        """Warm up once on a side stream (first-launch attribute calls, packing), restore x,
-        then capture ``fn`` into a HIP graph."""
-        side = torch.cuda.Stream(device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        x_keep = x.clone()
-        with torch.cuda.stream(side):
-            fn()
-        torch.cuda.current_stream(device).wait_stream(side)
-        x.copy_(x_keep)
+    def capture(fn, warm=None, counter=None):
+        """Capture ``fn`` into a HIP graph.  ``warm`` (one step: first-launch attribute calls, packing) runs before
+        on a side stream; x and the counter are restored after it."""
+        if warm is not None:
+            keep = [(buf, buf.clone()) for buf in (x, counter) if buf is not None]
+            side = torch.cuda.Stream(device)
+            side.wait_stream(torch.cuda.current_stream(device))
+            with torch.cuda.stream(side):
+                warm()
+            torch.cuda.current_stream(device).wait_stream(side)
+            for buf, saved in keep:
+                buf.copy_(saved)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             fn()
@@ -287,12 +312,8 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
         # No per-step input from the host at all: the step index lives in device memory and is
         # advanced by a kernel, so one graph holds several consecutive reverse steps.
         counter = torch.empty(1, dtype=torch.int64, device=device)
-
         eps_buf = torch.empty_like(x)
-        y_dev = None
-        if y is not None:
-            kind_laion = getattr(getattr(noise_model, "_arch", None), "kind", 0) == 1
-            y_dev = y.contiguous().float() if kind_laion else y.contiguous().to(torch.int64)
+        y_dev = _cond_tensor(getattr(getattr(noise_model, "_arch", None), "kind", 0), y)
         one_call = hasattr(noise_model, "_run_eval_step")
 
         def steps(k):
@@ -300,135 +321,22 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
                 for _ in range(k):
                     if one_call:  # step counter + eps_theta + update behind one C-ABI entry
                         noise_model._run_eval_step(x, y_dev, coef, counter, t_idx, t_vec, eps_buf,
-                                                   philox_seed=philox_seed)
-                        continue
-                    check(lib.tdx_step_begin(counter.data_ptr(), t_idx.data_ptr(), t_vec.data_ptr(), n_samples, st()),
-                          "tdx_step_begin")
-                    step_kernels(False)
+                                                   philox_seed=philox_seed, tau=tau, S=S)
+                    else:
+                        step_begin(counter)
+                        step_kernels(False)
             return run
 
         if one_call and hasattr(noise_model, "_prepare_sampling"):
             # per-t / per-sample tables of the (linear) time projections: one look-up kernel per reverse step in
             # place of the step counter, the time MLP and the projections (tdx_unet_prepare_sampling)
-            noise_model._prepare_sampling(x, y_dev, T)
-        unroll = min(GRAPH_STEPS, T)
-        counter.fill_(T - 1)
-        graph = capture(steps(unroll))
-        tail = T % unroll
-        tail_graph = None
-        if tail:
-            counter.fill_(T - 1)
-            tail_graph = capture(steps(tail))
-        counter.fill_(T - 1)
-        for _ in range(T // unroll):
-            graph.replay()
-        if tail_graph is not None:
-            tail_graph.replay()
-        return x
-
-    graph = None
-    if use_graph:
-        t_idx.fill_(T - 1); t_vec.fill_(T - 1)
-        graph = capture(lambda: step_kernels(True))
-    for t in reversed(range(T)):
-        t_idx.fill_(t)
-        t_vec.fill_(t)
-        if philox_seed is None:
-            if t > 0:
-                if noises is not None:
-                    zbuf.copy_(noises[t].to(device))
-                else:
-                    zbuf.copy_(torch.randn_like(x))
-            else:
-                zbuf.zero_()
-        if graph is not None:
-            graph.replay()
-        else:
-            step_kernels(True)
-    return x
-
-
-def _sample_loop_sched(noise_model, diffusion, schedule, device, n_samples, y, x_T, noises, use_graph, philox_seed):
-    """sample_loop over a timestep schedule: the counter / t_idx hold the step index k (the coefficient row), t_vec
-    the network's timestep tau[k]; the kernels map k to tau[k] for the noise key (tdx_*_sched)."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _lib.TdxError("sampling runs on the GPU only (no CPU fallback)")
-    if schedule.num_timesteps != diffusion.num_timesteps:
-        raise ValueError(f"the schedule was built for T = {schedule.num_timesteps}, the diffusion has "
-                         f"T = {diffusion.num_timesteps}")
-    noise_model.eval()
-    shape = tuple(getattr(getattr(noise_model, "_arch", None), "in_shape", (1, 28, 28)))
-    x = (torch.randn(n_samples, *shape) if x_T is None else x_T).to(device).float().contiguous()
-    if y is not None:
-        y = y.to(device)
-    if n_samples == 0:
-        return x
-    S = schedule.steps
-    taus = schedule.timesteps.tolist()
-    tau, coef = schedule.device_tables(device)
-    t_idx = torch.empty(1, dtype=torch.int32, device=device)
-    t_vec = torch.empty(n_samples, dtype=torch.int64, device=device)
-    st = lambda: torch.cuda.current_stream(device).cuda_stream  # noqa: E731
-    zbuf = torch.empty_like(x)
-
-    def step_kernels(use_z: bool):
-        eps = noise_model._run_forward(x, t_vec, y, mode=2)[0]
-        if philox_seed is not None:
-            check(lib.tdx_p_sample_step_sched_philox(x.data_ptr(), x.data_ptr(), eps.data_ptr(), coef.data_ptr(),
-                                                     tau.data_ptr(), t_idx.data_ptr(), x.numel(), philox_seed, st()),
-                  "tdx_p_sample_step_sched_philox")
-        else:
-            check(lib.tdx_p_sample_step_sched(x.data_ptr(), x.data_ptr(), eps.data_ptr(),
-                                              zbuf.data_ptr() if use_z else None, coef.data_ptr(), tau.data_ptr(),
-                                              t_idx.data_ptr(), x.numel(), st()), "tdx_p_sample_step_sched")
-
-    def capture(fn, warm, counter=None):
-        """Warm up with ``warm`` (one step) on a side stream, restore x (and the counter), capture ``fn``."""
-        side = torch.cuda.Stream(device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        x_keep = x.clone()
-        c_keep = None if counter is None else counter.clone()
-        with torch.cuda.stream(side):
-            warm()
-        torch.cuda.current_stream(device).wait_stream(side)
-        x.copy_(x_keep)
-        if counter is not None:
-            counter.copy_(c_keep)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            fn()
-        return g
-
-    if use_graph and philox_seed is not None:
-        counter = torch.empty(1, dtype=torch.int64, device=device)
-        eps_buf = torch.empty_like(x)
-        y_dev = None
-        if y is not None:
-            kind_laion = getattr(getattr(noise_model, "_arch", None), "kind", 0) == 1
-            y_dev = y.contiguous().float() if kind_laion else y.contiguous().to(torch.int64)
-        one_call = hasattr(noise_model, "_run_eval_step")
-
-        def steps(k):
-            def run():
-                for _ in range(k):
-                    if one_call:
-                        noise_model._run_eval_step(x, y_dev, coef, counter, t_idx, t_vec, eps_buf,
-                                                   philox_seed=philox_seed, tau=tau, S=S)
-                        continue
-                    check(lib.tdx_step_begin_sched(counter.data_ptr(), tau.data_ptr(), t_idx.data_ptr(),
-                                                   t_vec.data_ptr(), n_samples, st()), "tdx_step_begin_sched")
-                    step_kernels(False)
-            return run
-
-        if one_call and hasattr(noise_model, "_prepare_sampling"):
             noise_model._prepare_sampling(x, y_dev, S, tau=tau)
         unroll = min(GRAPH_STEPS, S)
         counter.fill_(S - 1)
         graph = capture(steps(unroll), steps(1), counter)
-        tail = S % unroll
-        tail_graph = capture(steps(tail), lambda: None) if tail else None
-        counter.fill_(S - 1)
+        # The tail needs no warm-up of its own: the one step above already launched every kernel of a step.  A capture
+        # executes nothing and the warm-up's x and counter were restored, so the counter is still S - 1 for the replays.
+        tail_graph = capture(steps(S % unroll)) if S % unroll else None
         for _ in range(S // unroll):
             graph.replay()
         if tail_graph is not None:

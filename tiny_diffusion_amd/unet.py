@@ -188,6 +188,18 @@ class _PtrTable:
         return self.arr
 
 
+def _dptr(tensor):
+    return None if tensor is None else tensor.data_ptr()
+
+
+def _cond_tensor(kind: int, y):
+    """The conditioning input as the kernels read it: fp32 text embeddings for the LAION network, int64 labels for
+    every other one (forward and the sampling loop)."""
+    if y is None:
+        return None
+    return y.contiguous().float() if kind == KIND_LAION else y.contiguous().to(torch.int64)
+
+
 class _UNetFunction(torch.autograd.Function):
     """eps_hat = UNet(x, t[, y]); backward returns every parameter gradient."""
 
@@ -487,65 +499,55 @@ class NoiseModelBase(nn.Module):
             if (self._mode() if mode is None else mode) == MODE_TRAIN:
                 raise ValueError("empty batch in train mode: BatchNorm statistics are undefined")
             return x.new_empty((0,) + tuple(self._arch.in_shape), dtype=torch.float32), None, MODE_INFER
-        plan = self._plan(B, x.device, self._input_hw(x))
-        self._apply_precision(plan)
+        mode = self._mode() if mode is None else mode
+        plan, pptr, bptr, st = self._plan_ptrs(x, pack=mode == MODE_INFER)
         self._apply_bn_sync(plan, x.device)
         self._apply_streams(plan)
-        mode = self._mode() if mode is None else mode
-        pptr, ptens = self._param_ptrs()
-        bptr, btens = self._buffer_ptrs()
         x = x.contiguous().float()
         t = t.contiguous().to(torch.int64)
-        if y is not None:
-            y = y.contiguous().float() if self._arch.kind == KIND_LAION else y.contiguous().to(torch.int64)
+        y = _cond_tensor(self._arch.kind, y)
         out = torch.empty((B,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
-        st = torch.cuda.current_stream(x.device).cuda_stream
-        if mode == MODE_INFER:
-            self._refresh_infer_pack(plan, pptr, ptens, bptr, btens, st)
-        else:
+        if mode != MODE_INFER:
             plan.infer_key = None
             plan.generation += 1
             if mode == MODE_TRAIN:
                 self._buf_epoch += 1
-        check(lib.tdx_unet_forward(plan.handle, pptr, bptr, x.data_ptr(), t.data_ptr(),
-                                   None if y is None else y.data_ptr(), out.data_ptr(),
+        check(lib.tdx_unet_forward(plan.handle, pptr, bptr, x.data_ptr(), t.data_ptr(), _dptr(y), out.data_ptr(),
                                    plan.workspace.data_ptr(), plan.ws_bytes, B, mode, st),
               "tdx_unet_forward")
         return out, plan, mode
 
-    def _refresh_infer_pack(self, plan, pptr, ptens, bptr, btens, st):
-        """INFER reuses the packed weights / folded BN until a parameter or buffer changes."""
-        # running statistics are updated by kernels (no torch version bump): _buf_epoch
-        key = tuple(tn._version for tn in ptens if tn is not None) + tuple(tn._version for tn in btens) \
-            + tuple(self._ptab_p.key) + tuple(self._ptab_b.key) + (self._buf_epoch,)
-        if plan.infer_key != key:
-            check(lib.tdx_unet_pack(plan.handle, pptr, bptr, st), "tdx_unet_pack")
-            plan.infer_key = key
+    def _plan_ptrs(self, x, pack: bool = True):
+        """(plan, parameter pointers, buffer pointers, stream) of a launch on ``x``: the plan of its batch size and
+        resolution in the module's precision.  ``pack`` (every MODE_INFER launch): the packed weights / folded BN are
+        reused until a parameter or buffer changes."""
+        plan = self._plan(x.shape[0], x.device, self._input_hw(x))
+        self._apply_precision(plan)
+        pptr, ptens = self._param_ptrs()
+        bptr, btens = self._buffer_ptrs()
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        if pack:
+            # running statistics are updated by kernels (no torch version bump): _buf_epoch
+            key = tuple(tn._version for tn in ptens if tn is not None) + tuple(tn._version for tn in btens) \
+                + tuple(self._ptab_p.key) + tuple(self._ptab_b.key) + (self._buf_epoch,)
+            if plan.infer_key != key:
+                check(lib.tdx_unet_pack(plan.handle, pptr, bptr, st), "tdx_unet_pack")
+                plan.infer_key = key
+        return plan, pptr, bptr, st
 
     def _run_eval_step(self, x, y, coef, counter, t_idx, t_vec, eps, z=None, philox_seed: int = 0, tau=None,
                        S: int = 0):
         """One reverse step of sample() in place on ``x`` (tdx_unet_eval_step): the step index is
         read from and decremented in device memory, so the call can sit in a HIP graph.  ``tau``: the
         device timesteps of a schedule of ``S`` steps (tdx_unet_eval_step_sched; ``coef`` is then (S,3))."""
-        B = x.shape[0]
-        plan = self._plan(B, x.device, self._input_hw(x))
-        self._apply_precision(plan)
-        pptr, ptens = self._param_ptrs()
-        bptr, btens = self._buffer_ptrs()
-        st = torch.cuda.current_stream(x.device).cuda_stream
-        self._refresh_infer_pack(plan, pptr, ptens, bptr, btens, st)
-        if tau is not None:
-            check(lib.tdx_unet_eval_step_sched(plan.handle, pptr, bptr, x.data_ptr(), None if y is None else y.data_ptr(),
-                                               None if z is None else z.data_ptr(), coef.data_ptr(), tau.data_ptr(),
-                                               int(S), counter.data_ptr(), t_idx.data_ptr(), t_vec.data_ptr(),
-                                               eps.data_ptr(), x.numel(), plan.workspace.data_ptr(), plan.ws_bytes, B,
-                                               philox_seed, st), "tdx_unet_eval_step_sched")
-            return
-        check(lib.tdx_unet_eval_step(plan.handle, pptr, bptr, x.data_ptr(), None if y is None else y.data_ptr(),
-                                     None if z is None else z.data_ptr(), coef.data_ptr(), counter.data_ptr(),
-                                     t_idx.data_ptr(), t_vec.data_ptr(), eps.data_ptr(), x.numel(),
-                                     plan.workspace.data_ptr(), plan.ws_bytes, B, philox_seed, st),
-              "tdx_unet_eval_step")
+        plan, pptr, bptr, st = self._plan_ptrs(x)
+        head = (plan.handle, pptr, bptr, x.data_ptr(), _dptr(y), _dptr(z), coef.data_ptr())
+        rest = (counter.data_ptr(), t_idx.data_ptr(), t_vec.data_ptr(), eps.data_ptr(), x.numel(),
+                plan.workspace.data_ptr(), plan.ws_bytes, x.shape[0], philox_seed, st)
+        if tau is None:
+            check(lib.tdx_unet_eval_step(*head, *rest), "tdx_unet_eval_step")
+        else:
+            check(lib.tdx_unet_eval_step_sched(*head, tau.data_ptr(), int(S), *rest), "tdx_unet_eval_step_sched")
 
     def _prepare_sampling(self, x, y, T: int, tau=None):
         """Once per sample() call, before the reverse loop (and before any graph capture): the per-t table of
@@ -556,19 +558,13 @@ class NoiseModelBase(nn.Module):
         steps, the table rows are then built at them (tdx_unet_prepare_sampling_sched).  No-op for the latent MLP."""
         if self._arch.kind == KIND_LATENT:
             return
-        B = x.shape[0]
-        plan = self._plan(B, x.device, self._input_hw(x))
-        self._apply_precision(plan)
-        pptr, ptens = self._param_ptrs()
-        bptr, btens = self._buffer_ptrs()
-        st = torch.cuda.current_stream(x.device).cuda_stream
-        self._refresh_infer_pack(plan, pptr, ptens, bptr, btens, st)
-        if tau is not None:
-            check(lib.tdx_unet_prepare_sampling_sched(plan.handle, pptr, None if y is None else y.data_ptr(), B,
-                                                      tau.data_ptr(), int(T), st), "tdx_unet_prepare_sampling_sched")
-            return
-        check(lib.tdx_unet_prepare_sampling(plan.handle, pptr, None if y is None else y.data_ptr(), B, int(T), st),
-              "tdx_unet_prepare_sampling")
+        plan, pptr, _, st = self._plan_ptrs(x)
+        head = (plan.handle, pptr, _dptr(y), x.shape[0])
+        if tau is None:
+            check(lib.tdx_unet_prepare_sampling(*head, int(T), st), "tdx_unet_prepare_sampling")
+        else:
+            check(lib.tdx_unet_prepare_sampling_sched(*head, tau.data_ptr(), int(T), st),
+                  "tdx_unet_prepare_sampling_sched")
 
     def _run_backward(self, plan: _Plan, d_out, grad_views, stage_lo: int = 0, stage_hi: Optional[int] = None):
         pptr, _ = self._param_ptrs()
