@@ -608,9 +608,9 @@ int tdx_unet_tensor(const tdx_unet* u, int batch, const char* name, size_t* offs
 int tdx_unet_pack(tdx_unet* u, const void* const* params, void* const* buffers,
                   tdx_stream_t stream);
 
-/* Tuning knobs for experiments (process-global): "conv_tile" 0 auto | 1 128x128 | 2 128x64 |
- * 3 64x64; "wgrad_target" workgroups aimed at by the wgrad pixel split; "conv_impl" 0 | 1
- * (one / two register stages); "splitk" 0 | 1. */
+/* Tuning knobs for experiments (process-global; the defaults are the product): "conv_tile" 0 auto |
+ * 1 128x128 | 2 128x64 | 3 64x64; "wgrad_target" workgroups aimed at by the wgrad pixel split;
+ * "splitk" 0 | 1; the rest are listed in INTEGRATION.md.  An unknown key returns TDX_E_BADARG. */
 int tdx_tune_set(const char* key, int value);
 
 /* Diagnostics (tools/gpu_stage6_diag.py, gpu_clock_probe.py, ...): device buffer of `bytes` bytes that the

@@ -249,7 +249,39 @@ def test_conv3x3_fwd_splitk_inference(tdx, B, H, cin, cout):
     assert rel_err(nchw(out2), ref) < 3e-6
 
 
-WINO_CASES = [(4, 28, 64, 128), (3, 14, 128, 256), (5, 7, 256, 512), (7, 4, 512, 512), (3, 8, 1024, 256), (2, 16, 512, 128),
+@pytest.mark.parametrize("B,H,cin,cout", [(16, 4, 512, 512), (1, 28, 128, 128)])
+def test_conv3x3_fwd_splitk_bn_on_load(tdx, B, H, cin, cout):
+    """split-K of a BN+ReLU-on-load input (the register-staging split-K kernel) with the BN+ReLU epilogue in the
+    reduction: against torch, bitwise reproducible, and equal to the unsplit launch up to summation order."""
+    x, w, b = _conv_inputs(B, H, cin, cout, seed=1)
+    g = torch.Generator().manual_seed(5)
+    isc, ish = torch.randn(cin, generator=g), torch.randn(cin, generator=g) * 0.3
+    osc, osh = torch.randn(cout, generator=g), torch.randn(cout, generator=g) * 0.3
+    a = F.relu(x * isc.view(1, -1, 1, 1) + ish.view(1, -1, 1, 1))
+    ref = F.relu(F.conv2d(a, w, b, padding=1) * osc.view(1, -1, 1, 1) + osh.view(1, -1, 1, 1))
+    wf, _ = _pack(tdx, w)
+    need = tdx.lib.tdx_conv3x3_splitk_scratch_floats(B, H, H, cin, cout)
+    assert need > 0, "shape was expected to take the split-K path"
+    scratch = torch.full((need,), float("nan"), device="cuda")
+    xin, bd = dev(nhwc(x)), dev(b)
+    iscd, ishd, oscd, oshd = dev(isc), dev(ish), dev(osc), dev(osh)
+    outs = []
+    for _ in range(2):
+        out = torch.full((B, H, H, cout), float("nan"), device="cuda")
+        tdx.check(tdx.lib.tdx_conv3x3_fwd_splitk(xin.data_ptr(), wf.data_ptr(), bd.data_ptr(), out.data_ptr(), B, H, H,
+                                                 cin, cout, 1 | 2, iscd.data_ptr(), ishd.data_ptr(), oscd.data_ptr(),
+                                                 oshd.data_ptr(), scratch.data_ptr(), need, stream()))
+        outs.append(out)
+    assert rel_err(nchw(outs[0]), ref) < 3e-6
+    assert torch.equal(outs[0], outs[1])  # fixed reduction order: bitwise reproducible
+    unsplit = torch.full((B, H, H, cout), float("nan"), device="cuda")
+    tdx.check(tdx.lib.tdx_conv3x3_fwd(xin.data_ptr(), wf.data_ptr(), bd.data_ptr(), unsplit.data_ptr(), B, H, H, cin,
+                                      cout, 1 | 2, iscd.data_ptr(), ishd.data_ptr(), oscd.data_ptr(), oshd.data_ptr(),
+                                      None, stream()))
+    assert rel_err(outs[0], unsplit) < 3e-6
+
+
+WINO_CASES =[(4, 28, 64, 128), (3, 14, 128, 256), (5, 7, 256, 512), (7, 4, 512, 512), (3, 8, 1024, 256), (2, 16, 512, 128),
               (2, 32, 256, 64), (2, 32, 64, 64), (1, 64, 64, 64), (33, 8, 128, 128), (3, 16, 384, 128), (2, 32, 192, 64),
               (1, 2, 64, 64), (9, 4, 64, 64)]
 

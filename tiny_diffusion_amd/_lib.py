@@ -216,7 +216,7 @@ _bind()
 
 
 def _apply_env_tuning():
-    """TDX_TUNE="conv_impl=1,conv_tile=3": process-wide tuning knobs (tdx_tune_set)."""
+    """TDX_TUNE="conv_tile=3,splitk=0": process-wide tuning knobs (tdx_tune_set)."""
     spec = os.environ.get("TDX_TUNE", "")
     for item in filter(None, (x.strip() for x in spec.split(","))):
         key, _, val = item.partition("=")

@@ -19,14 +19,15 @@
 // permutation of k, so the sum over k is unchanged.
 #include "internal.h"
 #include <cstring>
-#include <type_traits>
 
 #define BK 32   // K-tile: 32 channels of one tap
 #define BKP 36  // padded LDS row (floats)
 
 #include "conv_shared.h"
 
-template <int BM, int BN, bool IN_BN, int EPI>
+// Register-staging kernel of the BN-on-load launches: relu(in * in_scale + in_shift) is applied between the staging
+// registers and LDS (raw inputs run on conv3x3_igemm_dma_kernel).
+template <int BM, int BN, int EPI>
 __global__ void __launch_bounds__(256)
 conv3x3_igemm_kernel(ConvArgs a) {
   constexpr int WGM = 2, WGN = 2;  // 4 waves as 2 x 2
@@ -117,14 +118,12 @@ conv3x3_igemm_kernel(ConvArgs a) {
 #pragma unroll
       for (int j = 0; j < BI; ++j)
         rb[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_off[j], soff_w, 0));
-      if (IN_BN) {
-        sc4 = *reinterpret_cast<const float4*>(a.in_scale + c0);
-        sh4 = *reinterpret_cast<const float4*>(a.in_shift + c0);
-      }
+      sc4 = *reinterpret_cast<const float4*>(a.in_scale + c0);
+      sh4 = *reinterpret_cast<const float4*>(a.in_shift + c0);
 #pragma unroll
       for (int i = 0; i < AI; ++i) {
         const bool ok = (a_taps[i] >> tap) & 1u;
-        if (IN_BN) okmask |= ok ? (1u << i) : 0u;
+        okmask |= ok ? (1u << i) : 0u;
         ra[i] = __builtin_bit_cast(
             f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_in, ok ? a_off[i] : OOB, soff_in, 0));
       }
@@ -159,14 +158,12 @@ conv3x3_igemm_kernel(ConvArgs a) {
 #pragma unroll
       for (int i = 0; i < AI; ++i) {
         f32x4 v = ra[i];
-        if (IN_BN) {
-          // padding must stay 0 AFTER the transform (relu(shift) != 0): only here is the mask needed
-          v[0] = fmaxf(fmaf(v[0], sc4.x, sh4.x), 0.f);
-          v[1] = fmaxf(fmaf(v[1], sc4.y, sh4.y), 0.f);
-          v[2] = fmaxf(fmaf(v[2], sc4.z, sh4.z), 0.f);
-          v[3] = fmaxf(fmaf(v[3], sc4.w, sh4.w), 0.f);
-          if (!((okmask >> i) & 1u)) v = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
+        // padding must stay 0 AFTER the transform (relu(shift) != 0): only here is the mask needed
+        v[0] = fmaxf(fmaf(v[0], sc4.x, sh4.x), 0.f);
+        v[1] = fmaxf(fmaf(v[1], sc4.y, sh4.y), 0.f);
+        v[2] = fmaxf(fmaf(v[2], sc4.z, sh4.z), 0.f);
+        v[3] = fmaxf(fmaf(v[3], sc4.w, sh4.w), 0.f);
+        if (!((okmask >> i) & 1u)) v = f32x4{0.f, 0.f, 0.f, 0.f};
         *reinterpret_cast<f32x4*>(Ab + (ld_row + 32 * i) * BKP + ld_c4) = v;
       }
 #pragma unroll
@@ -181,13 +178,14 @@ conv3x3_igemm_kernel(ConvArgs a) {
 }
 
 // ---------------------------------------------------------------------------
-// Variant 2 of the forward/dgrad kernel: two register stages.  While the MFMAs of tile k
+// Variant 2, two register stages: today only the split-K launch of a BN-on-load input (launch_splitk; its unsplit
+// instantiations lost the in-process A/B against conv3x3_igemm_kernel and are gone).  While the MFMAs of tile k
 // run from LDS[k&1], the registers loaded during iteration k-1 (tile k+1) are written to
 // LDS[(k+1)&1] in four slices BETWEEN the four MFMA groups, and the global loads of tile
 // k+2 are issued into the other register stage.  A load therefore has a whole iteration
 // (~4000 cycles) to land and the LDS stores ride in the shadow of the 64-cycle MFMAs, so a
 // wave's instruction stream is MFMA-dense even with no co-resident partner wave.
-template <int BM, int BN, bool IN_BN, int EPI, bool SPLITK = false, bool SCHED = false>
+template <int BM, int BN, bool IN_BN, int EPI, bool SPLITK = false>
 __global__ void __launch_bounds__(256)
 conv3x3_igemm2_kernel(ConvArgs a) {
   constexpr int WGM = 2, WGN = 2;
@@ -324,42 +322,17 @@ conv3x3_igemm2_kernel(ConvArgs a) {
           acc[im][in] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[im][j], bf[in][j], acc[im][in], 0, 0, 0);
   };
   // one iteration: compute tile kt from LDS[cur]; Sst (tile kt+1) -> LDS[cur^1]; load tile kt+2 -> Sld
-  auto iteration = [&](auto sid, int kt, int cur, const Stage& Sst, Stage& Sld) {
-    constexpr int SID = decltype(sid)::value;  // distinct sched-group id per unrolled copy
-    if (SCHED || !(a.dbg & 4)) load_tile(kt + 2, Sld);
-    if (!SCHED) {
-      // keep the loads at the top of the iteration: hipcc would otherwise sink them to the
-      // end, a few hundred cycles before the next iteration's first store waits for them
-      __builtin_amdgcn_sched_barrier(0);
-    }
+  auto iteration = [&](int kt, int cur, const Stage& Sst, Stage& Sld) {
+    if (!(a.dbg & 4)) load_tile(kt + 2, Sld);
+    // keep the loads at the top of the iteration: hipcc would otherwise sink them to the
+    // end, a few hundred cycles before the next iteration's first store waits for them
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int ks = 0; ks < BK / 8; ++ks) {
       mfma_group(cur, ks);
-      if (SCHED || !(a.dbg & 2)) store_slice(Sst, cur ^ 1, ks);
+      if (!(a.dbg & 2)) store_slice(Sst, cur ^ 1, ks);
     }
-    if (SCHED) {
-      // Ask the scheduler for an even interleave: the address arithmetic, the 8 global loads,
-      // the 8 LDS stores and the 16 fragment reads of one K-tile are dealt out between the
-      // 64-cycle MFMAs (which leave the issue port free most of the time) instead of sitting
-      // in clumps during which the matrix pipe drains.
-      constexpr int NMF = TM * TN * 16;        // MFMAs per K-tile per wave
-      constexpr int NDR = (TM + TN) * 4;       // ds_read_b128
-      constexpr int NVM = AI + BI;             // global_load_dwordx4
-      constexpr int NDW = AI + BI;             // ds_write_b128
-      constexpr int NVA = 14 * AI + 4 * BI + (IN_BN ? 9 * AI : 0) + 12;  // VALU (estimate)
-      constexpr int VPM = (NVA + NMF - 1) / NMF;
-      __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, SID);  // fragments of the first group
-#pragma unroll
-      for (int i = 0; i < NMF; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, SID);
-        __builtin_amdgcn_sched_group_barrier(0x002, VPM, SID);
-        if (((i + 1) * (NDR - TM - TN)) / NMF > (i * (NDR - TM - TN)) / NMF)
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, SID);
-        if (((i + 1) * NVM) / NMF > (i * NVM) / NMF) __builtin_amdgcn_sched_group_barrier(0x020, 1, SID);
-        if (((i + 1) * NDW) / NMF > (i * NDW) / NMF) __builtin_amdgcn_sched_group_barrier(0x200, 1, SID);
-      }
-    }
-    if (SCHED || !(a.dbg & 1)) __syncthreads();
+    if (!(a.dbg & 1)) __syncthreads();
   };
 
   // prologue: tile 0 -> LDS[0], tile 1 -> S1 registers
@@ -370,10 +343,10 @@ conv3x3_igemm2_kernel(ConvArgs a) {
   __syncthreads();
   int kt = 0;
   for (; kt + 1 < nk; kt += 2) {
-    iteration(std::integral_constant<int, 0>{}, kt, 0, S1, S0);      // S1 holds tile kt+1; load kt+2 -> S0
-    iteration(std::integral_constant<int, 1>{}, kt + 1, 1, S0, S1);  // S0 holds tile kt+2; load kt+3 -> S1
+    iteration(kt, 0, S1, S0);      // S1 holds tile kt+1; load kt+2 -> S0
+    iteration(kt + 1, 1, S0, S1);  // S0 holds tile kt+2; load kt+3 -> S1
   }
-  if (kt < nk) iteration(std::integral_constant<int, 2>{}, kt, 0, S1, S0);  // odd tail
+  if (kt < nk) iteration(kt, 0, S1, S0);  // odd tail
 
   conv_epilogue<BM, BN, EPI, SPLITK>(a, acc, smem, tile_m, m0, n0, wm, wn, l31, half, tid);
 }
@@ -850,16 +823,12 @@ static int lds_slots_per_cu(int lds_bytes) {
 // tuning knobs (tdx_tune_set): 0 = heuristic
 static int g_force_tile = 0;          // 1: 128x128, 2: 128x64, 3: 64x64
 static int g_min_tiles = 256;         // smallest grid a 128-row tile may have (knob conv_min_tiles)
-static int g_conv_impl = 0;           // main-loop variant of the non-split launches: 0 one register stage
-                                      // (default: fastest end to end in in-process A/B), 1 two stages,
-                                      // 2 two stages + sched_group_barrier interleave
 static int g_conv_dbg = 0;
 int tdx_conv_dbg_get() { return g_conv_dbg; }
 static int g_conv_stamp = 0;           // diagnostics: LDS-DMA forward kernels stamp their main loop into the diag buffer
 extern unsigned* g_tdx_diag_buffer;    // time_embed.hip (tdx_diag_set_buffer)
 extern size_t g_tdx_diag_bytes;
 extern int g_tdx_probe_stamp;
-static int g_conv_dma = 1;             // raw-input convolutions fetch their tiles by LDS-DMA (variant 3)
 static int g_splitk = 1;              // 0: never split K; 1: split K when the grid would not fill the chip
 static int g_splitk_tiles = 260;      // split K when the 64x64 grid has fewer tiles than this (sweep on
                                       // MI355X: 192 -> 260 is neutral at n=16 and 4 % faster at n=64)
@@ -878,10 +847,6 @@ static int g_splitk_fused = 0;       // 1: the last-arriving workgroup of a tile
 static int g_splitk_train = 1;       // training convolutions of latency-bound shapes split K (plan_splitk_train)
 static int g_splitk_train_t64 = 1024;   // ... when the 64x64 grid has fewer tiles than this
 static int g_splitk_train_target = 1536;  // ... into about this many workgroups
-static int g_splitk_train_any = 0;      // 1: also shapes whose picked tile is 128x128
-static int g_wgrad_plan = 1;          // 0: round-1 targets; 1: the same, split count rounded down to two whole rounds of slots;
-                                      // 2: tile and rounds by a cost model (experiments: best isolated, worse inside the step)
-static int g_wgrad_rounds = 0;        // experiments: force that many rounds in pick_wgrad (0: cheapest by its cost model)
 #define TDX_CONV_OUT_BNBWD 8   /* internal flag: the epilogue emits BatchNorm-backward partial sums (ConvArgs::bw_*) */
 static int g_wgrad9_wgs = 0;          // bf16 mode: workgroups of the nine-tap kernel aimed at by the split (0: the per-tap plan's splits)
 static int g_wgrad_small = 1;         // 64x64 wgrad tiles for big-weight / few-pixel layers
@@ -898,13 +863,6 @@ int g_tdx_infer_cus = 256;
 int g_tdx_wino_infer = 1;
 static int g_wino_infer_ovh = 2;   // plan of the Winograd inference launch: a workgroup's non-loop time in stages (ring fill + epilogue ~ 4 us of 2.3)
 static int g_wino_infer_red = 3;   // ... and the dependent reduction launch
-
-extern "C" int tdx_conv3x3_dgrad(const float* dy, const float* w_dgrad, float* dx, int B, int H, int W,
-                                 int cin, int cout, tdx_stream_t stream) {
-  // the forward kernel on dy with the mirrored, channel-swapped pack: its "cin" is this layer's cout
-  return tdx_conv3x3_fwd(dy, w_dgrad, nullptr, dx, B, H, W, cout, cin, 0, nullptr, nullptr, nullptr, nullptr,
-                         nullptr, stream);
-}
 
 // diagnostics: resident workgroups per CU the runtime computes for the LDS-DMA forward kernel of a tile
 // (bm*1000 + bn; training epilogue) and for the weight-gradient kernel (negative argument)
@@ -923,7 +881,6 @@ extern "C" int tdx_tune_set(const char* key, int value) {
   if (!key) return TDX_E_BADARG;
   if (!strcmp(key, "conv_tile")) { g_force_tile = value; return 0; }
   if (!strcmp(key, "conv_min_tiles")) { g_min_tiles = value > 0 ? value : 256; return 0; }
-  if (!strcmp(key, "conv_impl")) { g_conv_impl = value < 0 || value > 2 ? 0 : value; return 0; }
   if (!strcmp(key, "splitk")) { g_splitk = value; return 0; }
   if (!strcmp(key, "splitk_tiles")) { g_splitk_tiles = value; return 0; }
   if (!strcmp(key, "splitk_target")) { g_splitk_target = value; return 0; }
@@ -946,7 +903,6 @@ extern "C" int tdx_tune_set(const char* key, int value) {
   if (!strcmp(key, "splitk_train")) { g_splitk_train = value != 0; return 0; }
   if (!strcmp(key, "splitk_train_t64")) { g_splitk_train_t64 = value > 0 ? value : 1024; return 0; }
   if (!strcmp(key, "splitk_train_target")) { g_splitk_train_target = value > 0 ? value : 1536; return 0; }
-  if (!strcmp(key, "splitk_train_any")) { g_splitk_train_any = value != 0; return 0; }
   if (!strcmp(key, "time_proj_early")) { g_tdx_time_proj_early = value != 0; return 0; }
   if (!strcmp(key, "time_stage_diag")) { g_tdx_time_stage = value == 6 ? 6 : 14; return 0; }
   if (!strcmp(key, "time_l1_impl")) { g_tdx_time_l1_impl = value; return 0; }
@@ -977,9 +933,6 @@ extern "C" int tdx_tune_set(const char* key, int value) {
   if (!strcmp(key, "infer_red")) { g_infer_red = value >= 0 ? value : 12; return 0; }
   if (!strcmp(key, "infer_cus")) { g_tdx_infer_cus = value > 0 && value <= 256 ? value : 256; return 0; }
   if (!strcmp(key, "wgrad9_wgs")) { g_wgrad9_wgs = value > 0 ? value : 0; return 0; }
-  if (!strcmp(key, "wgrad_plan")) { g_wgrad_plan = value; return 0; }
-  if (!strcmp(key, "wgrad_rounds")) { g_wgrad_rounds = value; return 0; }
-  if (!strcmp(key, "conv_dma")) { g_conv_dma = value; return 0; }
   if (!strcmp(key, "wgrad_target")) { g_wgrad_target = value > 0 ? value : 2048; return 0; }
   if (!strcmp(key, "wgrad_target_big")) { g_wgrad_target_big = value > 0 ? value : 0; return 0; }
   return TDX_E_BADARG;
@@ -1005,56 +958,43 @@ static TileCfg pick_tile(int64_t M, int cout) {
   return cands[2];
 }
 
+// Unsplit launch: a raw input runs on the LDS-DMA kernel, BN+ReLU on load on the register-staging kernel
 template <int BM, int BN>
 static int launch_conv(const ConvArgs& a_in, int flags, hipStream_t st) {
-  const size_t lds = (size_t)2 * (BM + BN) * BKP * sizeof(float);
   const bool in_bn = flags & TDX_CONV_IN_BNRELU;
   ConvArgs a = a_in;
-  a.compact = !in_bn && g_conv_dma && cdiv(a.M, BM) < 64;   // (the LDS-DMA kernel knows the compact order)
+  a.compact = !in_bn && cdiv(a.M, BM) < 64;   // (the LDS-DMA kernel knows the compact order)
   const int grid = a.compact ? cdiv(a.M, BM) * a.tilesN : (cdiv(a.M, BM) + 7) / 8 * 8 * a.tilesN;
   const int epi = (flags & TDX_CONV_OUT_BNRELU) ? EPI_BNRELU
                   : (flags & TDX_CONV_OUT_STATS) ? EPI_STATS
                   : (flags & TDX_CONV_OUT_BNBWD) ? EPI_BNBWD
                                                  : EPI_PLAIN;
-  if (epi == EPI_BNBWD && (in_bn || !g_conv_dma)) return TDX_E_BADARG;  // input-gradient launches read a raw tensor
-#define TDX_LAUNCH_DMA(EPI_)                                                                \
-  do {                                                                                      \
-    auto kern = conv3x3_igemm_dma_kernel<BM, BN, EPI_>;                                     \
-    const size_t lds_dma = (size_t)2 * (BM + BN) * BK * sizeof(float);                      \
-    kern<<<grid, 256, lds_dma, st>>>(a);                                                    \
-  } while (0)
-  if (!in_bn && g_conv_dma) {
-    if (epi == EPI_BNRELU) TDX_LAUNCH_DMA(EPI_BNRELU);
-    else if (epi == EPI_STATS) TDX_LAUNCH_DMA(EPI_STATS);
-    else if (epi == EPI_BNBWD) TDX_LAUNCH_DMA(EPI_BNBWD);
-    else TDX_LAUNCH_DMA(EPI_PLAIN);
+  if (epi == EPI_BNBWD && in_bn) return TDX_E_BADARG;  // input-gradient launches read a raw tensor
+  if (!in_bn) {
+    const size_t lds = (size_t)2 * (BM + BN) * BK * sizeof(float);
+    if (epi == EPI_BNRELU) conv3x3_igemm_dma_kernel<BM, BN, EPI_BNRELU><<<grid, 256, lds, st>>>(a);
+    else if (epi == EPI_STATS) conv3x3_igemm_dma_kernel<BM, BN, EPI_STATS><<<grid, 256, lds, st>>>(a);
+    else if (epi == EPI_BNBWD) conv3x3_igemm_dma_kernel<BM, BN, EPI_BNBWD><<<grid, 256, lds, st>>>(a);
+    else conv3x3_igemm_dma_kernel<BM, BN, EPI_PLAIN><<<grid, 256, lds, st>>>(a);
     TDX_CHECK_LAUNCH();
     return 0;
   }
-#undef TDX_LAUNCH_DMA
-#define TDX_LAUNCH(INBN, EPI_)                                                              \
+  const size_t lds = (size_t)2 * (BM + BN) * BKP * sizeof(float);
+#define TDX_LAUNCH(EPI_)                                                                    \
   do {                                                                                      \
-    auto kern = g_conv_impl == 2 ? conv3x3_igemm2_kernel<BM, BN, INBN, EPI_, false, true>   \
-                : g_conv_impl    ? conv3x3_igemm2_kernel<BM, BN, INBN, EPI_>                \
-                                 : conv3x3_igemm_kernel<BM, BN, INBN, EPI_>;                \
-    static bool attr_set[3] = {false, false, false};                                        \
-    if (lds > 65536 && !attr_set[g_conv_impl]) {                                            \
+    auto kern = conv3x3_igemm_kernel<BM, BN, EPI_>;                                         \
+    static bool attr_set = false;                                                           \
+    if (lds > 65536 && !attr_set) {                                                         \
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),               \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
       if (e != hipSuccess) return (int)e;                                                   \
-      attr_set[g_conv_impl] = true;                                                         \
+      attr_set = true;                                                                      \
     }                                                                                       \
     kern<<<grid, 256, lds, st>>>(a);                                                        \
   } while (0)
-  if (in_bn) {
-    if (epi == EPI_BNRELU) TDX_LAUNCH(true, EPI_BNRELU);
-    else if (epi == EPI_STATS) TDX_LAUNCH(true, EPI_STATS);
-    else TDX_LAUNCH(true, EPI_PLAIN);
-  } else {
-    if (epi == EPI_BNRELU) TDX_LAUNCH(false, EPI_BNRELU);
-    else if (epi == EPI_STATS) TDX_LAUNCH(false, EPI_STATS);
-    else TDX_LAUNCH(false, EPI_PLAIN);
-  }
+  if (epi == EPI_BNRELU) TDX_LAUNCH(EPI_BNRELU);
+  else if (epi == EPI_STATS) TDX_LAUNCH(EPI_STATS);
+  else TDX_LAUNCH(EPI_PLAIN);
 #undef TDX_LAUNCH
   TDX_CHECK_LAUNCH();
   return 0;
@@ -1097,7 +1037,7 @@ static int plan_splitk_train(int64_t M, int cin, int cout, int* kt_per_split, si
   const TileCfg c = pick_tile(M, cout);
   const int nk = 9 * (cin / BK);
   *kt_per_split = nk;
-  if (!g_splitk_train || (c.bm == 128 && c.bn == 128 && !g_splitk_train_any) || nk < 24) return 1;
+  if (!g_splitk_train || (c.bm == 128 && c.bn == 128) || nk < 24) return 1;
   const int64_t t64 = ((M + 63) / 64) * (cout / 64);
   if (t64 >= g_splitk_train_t64) return 1;
   int s = (int)((g_splitk_train_target + t64 - 1) / t64);
@@ -1119,6 +1059,18 @@ extern "C" size_t tdx_conv3x3_train_scratch_floats(int B, int H, int W, int cin,
   return s > 1 ? (size_t)s * M * cout : hybrid_scratch_floats(M, cin, cout);
 }
 
+// the plain split-K reduction: out = bias + sum_s partial[s] over n4 float4s in the fixed order 0..splits-1, then
+// relu(. * scale + shift) if BNRELU (scale, shift: null otherwise)
+template <bool BNRELU>
+static int launch_splitk_reduce(const float* partial, int splits, int64_t n4, int cout, const float* bias,
+                                const float* scale, const float* shift, float* out, hipStream_t st) {
+  int rg = (int)((n4 + 255) / 256);
+  if (rg > 2048) rg = 2048;
+  splitk_reduce_kernel<BNRELU><<<rg, 256, 0, st>>>(partial, splits, n4, cout, bias, scale, shift, out);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
 // raw-input (LDS-DMA) 64x64 split-K launch, then the training reduction: statistics in tiles of the rows the
 // unsplit kernel would have used (tdx_conv3x3_stat_tile_rows), or the plain sum when stats is null
 static int launch_splitk_train(ConvArgs a, int splits, int per, float* scratch, int stat_rows, hipStream_t st) {
@@ -1136,14 +1088,11 @@ static int launch_splitk_train(ConvArgs a, int splits, int per, float* scratch, 
       splitk_reduce_stats_kernel<128><<<rg, 256, 0, st>>>(scratch, splits, a.M, a.Cout, a.bias, final_out, a.stats, 0);
     else
       splitk_reduce_stats_kernel<64><<<rg, 256, 0, st>>>(scratch, splits, a.M, a.Cout, a.bias, final_out, a.stats, 0);
-  } else {
-    const int64_t n4 = (int64_t)a.M * a.Cout / 4;
-    int rg = (int)((n4 + 255) / 256);
-    if (rg > 2048) rg = 2048;
-    splitk_reduce_kernel<false><<<rg, 256, 0, st>>>(scratch, splits, n4, a.Cout, a.bias, nullptr, nullptr, final_out);
+    TDX_CHECK_LAUNCH();
+    return 0;
   }
-  TDX_CHECK_LAUNCH();
-  return 0;
+  return launch_splitk_reduce<false>(scratch, splits, (int64_t)a.M * a.Cout / 4, a.Cout, a.bias, nullptr, nullptr,
+                                     final_out, st);
 }
 
 // Hybrid launch of a TRAINING convolution whose tiles do not fill a whole number of rounds of the chip's workgroup
@@ -1207,15 +1156,11 @@ static int launch_hybrid(ConvArgs a, const HybridPlan& h, float* scratch, bool s
   if (stats) {
     dim3 rg(cdiv(rem, BM), a.Cout / 64);
     splitk_reduce_stats_kernel<BM><<<rg, 256, 0, st>>>(scratch, h.sp, a.M, a.Cout, a.bias, a.out, a.stats, h.row0);
-  } else {
-    const int64_t n4 = (int64_t)rem * a.Cout / 4;
-    int rg = (int)((n4 + 255) / 256);
-    if (rg > 2048) rg = 2048;
-    splitk_reduce_kernel<false><<<rg, 256, 0, st>>>(scratch, h.sp, n4, a.Cout, a.bias, nullptr, nullptr,
-                                                    a.out + (size_t)h.row0 * a.Cout);
+    TDX_CHECK_LAUNCH();
+    return 0;
   }
-  TDX_CHECK_LAUNCH();
-  return 0;
+  return launch_splitk_reduce<false>(scratch, h.sp, (int64_t)rem * a.Cout / 4, a.Cout, a.bias, nullptr, nullptr,
+                                     a.out + (size_t)h.row0 * a.Cout, st);
 }
 
 // second half of a split-K inference launch: a.out = the partials [splits][M][Cout]; the reduction in the fixed order
@@ -1237,44 +1182,60 @@ static int splitk_finish(const ConvArgs& a, float* final_out, float* scratch, in
     if (pooled) *pooled = true;
     return 0;
   }
-  const int64_t n4 = (int64_t)a.M * a.Cout / 4;
-  int rg = (int)((n4 + 255) / 256);
-  if (rg > 2048) rg = 2048;
-  if (EPI_ == EPI_BNRELU)
-    splitk_reduce_kernel<true><<<rg, 256, 0, st>>>(scratch, splits, n4, a.Cout, a.bias, a.out_scale, a.out_shift, final_out);
-  else
-    splitk_reduce_kernel<false><<<rg, 256, 0, st>>>(scratch, splits, n4, a.Cout, a.bias, nullptr, nullptr, final_out);
-  TDX_CHECK_LAUNCH();
-  return 0;
+  constexpr bool bnrelu = EPI_ == EPI_BNRELU;
+  return launch_splitk_reduce<bnrelu>(scratch, splits, (int64_t)a.M * a.Cout / 4, a.Cout, a.bias,
+                                      bnrelu ? a.out_scale : nullptr, bnrelu ? a.out_shift : nullptr, final_out, st);
 }
 
+// extra operands of the EPI_BNBWD epilogue (tdx_conv3x3_dgrad_bnbwd; host-side only)
+struct BwOperands { const float *y, *scale, *shift, *mean, *rstd; float* partial; };
+
+// One direct convolution as its entry point asked for it: the entry points below fill this and nothing else;
+// conv3x3_fwd_impl checks it, plans and launches.
+struct FwdRequest {
+  const float *in, *wpk, *bias;
+  float* out;
+  int B, H, W, cin, cout, flags;
+  const float *in_scale, *in_shift, *out_scale, *out_shift;
+  float* stats_partial;
+  float* scratch;          // split-K / hybrid partials (null: never split)
+  size_t scratch_floats;
+  bool train;              // plan as a training convolution (plan_splitk_train, plan_hybrid), not as an inference one
+  BwOperands bw;           // TDX_CONV_OUT_BNBWD
+  // sampling only: defer the split-K reduction to the consumer / fold the following max-pool into it (internal.h);
+  // *pooled is set when pool_out was written
+  TdxSplitDefer* defer;
+  float* pool_out;
+  bool* pooled;
+  unsigned* counters;      // knob splitk_fused: n_counters zeroed tile counters owned by the caller
+  int n_counters;
+};
+
 template <int EPI_>
-static int launch_splitk(ConvArgs a, bool in_bn, int splits, int per, float* scratch, hipStream_t st,
-                         unsigned* counters = nullptr, int n_counters = 0, TdxSplitDefer* defer = nullptr,
-                         float* pool_out = nullptr, bool* pooled = nullptr) {
+static int launch_splitk(ConvArgs a, const FwdRequest& r, int splits, int per, hipStream_t st) {
+  const bool in_bn = r.flags & TDX_CONV_IN_BNRELU;
   float* final_out = a.out;
-  a.out = scratch;
+  a.out = r.scratch;
   a.splits = splits;
   a.kt_per_split = per;
-  const size_t lds = (size_t)2 * (64 + 64) * BKP * sizeof(float);
-  a.compact = !in_bn && g_conv_dma && cdiv(a.M, 64) < 64;
+  a.compact = !in_bn && cdiv(a.M, 64) < 64;
   dim3 grid(a.compact ? cdiv(a.M, 64) * a.tilesN : (cdiv(a.M, 64) + 7) / 8 * 8 * a.tilesN, splits);
-  if (counters && g_splitk_fused && !in_bn && g_conv_dma && cdiv(a.M, 64) * a.tilesN <= n_counters) {
+  const size_t lds_dma = (size_t)2 * 128 * BK * sizeof(float);
+  if (r.counters && g_splitk_fused && !in_bn && cdiv(a.M, 64) * a.tilesN <= r.n_counters) {
     // one launch: the last workgroup of every tile reduces (conv_epilogue); ~5 us per convolution of a
     // reverse step, where a kernel boundary costs as much as a small kernel
-    a.tile_counters = counters;
+    a.tile_counters = r.counters;
     a.final_out = final_out;
     if (EPI_ != EPI_BNRELU) a.out_scale = a.out_shift = nullptr;
-    conv3x3_igemm_dma_kernel<64, 64, EPI_PLAIN, true><<<grid, 256, (size_t)2 * 128 * BK * sizeof(float), st>>>(a);
+    conv3x3_igemm_dma_kernel<64, 64, EPI_PLAIN, true><<<grid, 256, lds_dma, st>>>(a);
     TDX_CHECK_LAUNCH();
     return 0;
   }
-  if (in_bn) conv3x3_igemm2_kernel<64, 64, true, EPI_PLAIN, true><<<grid, 256, lds, st>>>(a);
-  else if (g_conv_dma)
-    conv3x3_igemm_dma_kernel<64, 64, EPI_PLAIN, true><<<grid, 256, (size_t)2 * 128 * BK * sizeof(float), st>>>(a);
-  else conv3x3_igemm2_kernel<64, 64, false, EPI_PLAIN, true><<<grid, 256, lds, st>>>(a);
+  if (in_bn)
+    conv3x3_igemm2_kernel<64, 64, true, EPI_PLAIN, true><<<grid, 256, (size_t)2 * 128 * BKP * sizeof(float), st>>>(a);
+  else conv3x3_igemm_dma_kernel<64, 64, EPI_PLAIN, true><<<grid, 256, lds_dma, st>>>(a);
   TDX_CHECK_LAUNCH();
-  return splitk_finish<EPI_>(a, final_out, scratch, splits, st, defer, pool_out, pooled);
+  return splitk_finish<EPI_>(a, final_out, r.scratch, splits, st, r.defer, r.pool_out, r.pooled);
 }
 
 extern "C" int tdx_conv3x3_stat_tiles(int B, int H, int W, int cin, int cout) {
@@ -1304,47 +1265,9 @@ extern "C" int tdx_conv3x3_shape_ok(int B, int H, int W, int cin, int cout) {
          (int64_t)cout * 9 * cin * 4 < (1ll << 31);
 }
 
-// extra operands of the EPI_BNBWD epilogue (set by tdx_conv3x3_dgrad_bnbwd around its call; host-side only)
-struct BwOperands { const float *y, *scale, *shift, *mean, *rstd; float* partial; };
-static thread_local BwOperands g_bw = {};
-// sampling-only extras of tdx_conv3x3_fwd_splitk_fused, set around its call: defer the split-K reduction to the
-// consumer / fold the following max-pool into it (internal.h)
-static thread_local TdxSplitDefer* g_defer = nullptr;
-static thread_local float* g_pool_out = nullptr;
-static thread_local bool g_pool_done = false;
-
-static int conv3x3_fwd_impl(const float* in, const float* wpk, const float* bias, float* out,
-                            int B, int H, int W, int cin, int cout, int flags,
-                            const float* in_scale, const float* in_shift,
-                            const float* out_scale, const float* out_shift,
-                            float* stats_partial, float* splitk_scratch, size_t scratch_floats,
-                            tdx_stream_t stream, bool train = false, unsigned* counters = nullptr,
-                            int n_counters = 0) {
-  if (!in || !wpk || !out || B <= 0 || H <= 0 || W <= 0) return TDX_E_BADARG;
-  if (cin % BK || cout % 64) return TDX_E_SHAPE;
-  if ((flags & TDX_CONV_IN_BNRELU) && (!in_scale || !in_shift)) return TDX_E_BADARG;
-  if ((flags & TDX_CONV_OUT_BNRELU) && (!out_scale || !out_shift)) return TDX_E_BADARG;
-  if ((flags & TDX_CONV_OUT_STATS) && !stats_partial) return TDX_E_BADARG;
-  if ((flags & TDX_CONV_OUT_STATS) && (flags & TDX_CONV_OUT_BNRELU)) return TDX_E_BADARG;
-  int64_t M64 = (int64_t)B * H * W;
-  if (M64 >= (1ll << 31)) return TDX_E_SHAPE;
-  if (!descriptor_fits(M64, cin, W + 1) || (int64_t)cout * 9 * cin * 4 >= (1ll << 31)) return TDX_E_SHAPE;
-  ConvArgs a{};
-  a.in = in; a.w = wpk; a.bias = bias; a.out = out;
-  a.in_scale = in_scale; a.in_shift = in_shift; a.out_scale = out_scale; a.out_shift = out_shift;
-  a.stats = (flags & TDX_CONV_OUT_STATS) ? stats_partial : nullptr;
-  if (flags & TDX_CONV_OUT_BNBWD) {
-    if (!g_bw.y || !g_bw.partial || (flags & (TDX_CONV_OUT_STATS | TDX_CONV_OUT_BNRELU | TDX_CONV_IN_BNRELU))) return TDX_E_BADARG;
-    a.bw_y = g_bw.y; a.bw_scale = g_bw.scale; a.bw_shift = g_bw.shift; a.bw_mean = g_bw.mean; a.bw_rstd = g_bw.rstd;
-    a.bw_partial = g_bw.partial;
-  }
-  a.B = B; a.H = H; a.W = W; a.Cin = cin; a.Cout = cout; a.M = (int)M64;
-  TileCfg c = pick_tile(M64, cout);
-  a.tilesN = cout / c.bn;
-  a.splits = 1;
-  a.kt_per_split = 9 * (cin / BK);
-  a.dbg = g_conv_dbg;
-  // diagnostics: 1 = every LDS-DMA forward/dgrad launch stamps; M = only training-forward launches of M pixels;
+// diagnostics (knob conv_stamp): where the LDS-DMA forward / dgrad kernels of this launch stamp their main loop, or null
+static unsigned long long* pick_stamps(const ConvArgs& a, const float* stats_partial) {
+  // 1 = every LDS-DMA forward/dgrad launch stamps; M = only training-forward launches of M pixels;
   // -M = only plain-epilogue (dgrad) launches of M pixels
   const bool stamp = g_conv_stamp == 1 || (g_conv_stamp > 1 && g_conv_stamp == a.M && stats_partial) ||
                      (g_conv_stamp < 0 && -g_conv_stamp == a.M && !stats_partial);
@@ -1353,33 +1276,60 @@ static int conv3x3_fwd_impl(const float* in, const float* wpk, const float* bias
   static int slot = 0;
   if (g_conv_stamp == 0) slot = 0;
   // a workgroup writes one 64-byte record at index blockIdx.x; no launch has more workgroups than 64x64 tiles
-  const size_t max_wgs = (size_t)cdiv(a.M, 64) * (size_t)(cout / 64), rec = 8 * sizeof(unsigned long long);
-  a.stamps = stamp && g_tdx_diag_buffer && max_wgs * rec <= g_tdx_diag_bytes
-                 ? reinterpret_cast<unsigned long long*>(g_tdx_diag_buffer) : nullptr;
+  const size_t max_wgs = (size_t)cdiv(a.M, 64) * (size_t)(a.Cout / 64), rec = 8 * sizeof(unsigned long long);
+  unsigned long long* stamps = stamp && g_tdx_diag_buffer && max_wgs * rec <= g_tdx_diag_bytes
+                                   ? reinterpret_cast<unsigned long long*>(g_tdx_diag_buffer) : nullptr;
   if (g_conv_stamp == 2 && stats_partial && g_tdx_diag_buffer && slot < 16 && max_wgs <= 8192 &&
       (size_t)(slot + 1) * 8192 * rec <= g_tdx_diag_bytes)
-    a.stamps = reinterpret_cast<unsigned long long*>(g_tdx_diag_buffer) + (size_t)(slot++) * 8 * 8192;
+    stamps = reinterpret_cast<unsigned long long*>(g_tdx_diag_buffer) + (size_t)(slot++) * 8 * 8192;
+  return stamps;
+}
+
+static int conv3x3_fwd_impl(const FwdRequest& r, tdx_stream_t stream) {
+  const int B = r.B, H = r.H, W = r.W, cin = r.cin, cout = r.cout, flags = r.flags;
+  if (!r.in || !r.wpk || !r.out || B <= 0 || H <= 0 || W <= 0) return TDX_E_BADARG;
+  if (cin % BK || cout % 64) return TDX_E_SHAPE;
+  if ((flags & TDX_CONV_IN_BNRELU) && (!r.in_scale || !r.in_shift)) return TDX_E_BADARG;
+  if ((flags & TDX_CONV_OUT_BNRELU) && (!r.out_scale || !r.out_shift)) return TDX_E_BADARG;
+  if ((flags & TDX_CONV_OUT_STATS) && !r.stats_partial) return TDX_E_BADARG;
+  if ((flags & TDX_CONV_OUT_STATS) && (flags & TDX_CONV_OUT_BNRELU)) return TDX_E_BADARG;
+  int64_t M64 = (int64_t)B * H * W;
+  if (M64 >= (1ll << 31)) return TDX_E_SHAPE;
+  if (!descriptor_fits(M64, cin, W + 1) || (int64_t)cout * 9 * cin * 4 >= (1ll << 31)) return TDX_E_SHAPE;
+  ConvArgs a{};
+  a.in = r.in; a.w = r.wpk; a.bias = r.bias; a.out = r.out;
+  a.in_scale = r.in_scale; a.in_shift = r.in_shift; a.out_scale = r.out_scale; a.out_shift = r.out_shift;
+  a.stats = (flags & TDX_CONV_OUT_STATS) ? r.stats_partial : nullptr;
+  if (flags & TDX_CONV_OUT_BNBWD) {
+    if (!r.bw.y || !r.bw.partial || (flags & (TDX_CONV_OUT_STATS | TDX_CONV_OUT_BNRELU | TDX_CONV_IN_BNRELU))) return TDX_E_BADARG;
+    a.bw_y = r.bw.y; a.bw_scale = r.bw.scale; a.bw_shift = r.bw.shift; a.bw_mean = r.bw.mean; a.bw_rstd = r.bw.rstd;
+    a.bw_partial = r.bw.partial;
+  }
+  a.B = B; a.H = H; a.W = W; a.Cin = cin; a.Cout = cout; a.M = (int)M64;
+  TileCfg c = pick_tile(M64, cout);
+  a.tilesN = cout / c.bn;
+  a.splits = 1;
+  a.kt_per_split = 9 * (cin / BK);
+  a.dbg = g_conv_dbg;
+  a.stamps = pick_stamps(a, r.stats_partial);
   hipStream_t st = to_stream(stream);
-  if (train && splitk_scratch && !(flags & (TDX_CONV_IN_BNRELU | TDX_CONV_OUT_BNRELU)) && g_conv_dma) {
+  if (r.train && r.scratch && !(flags & (TDX_CONV_IN_BNRELU | TDX_CONV_OUT_BNRELU))) {
     int per;
-    const int splits = plan_splitk_train(M64, cin, cout, &per, scratch_floats);
-    if (splits > 1) return launch_splitk_train(a, splits, per, splitk_scratch, c.bm, st);
+    const int splits = plan_splitk_train(M64, cin, cout, &per, r.scratch_floats);
+    if (splits > 1) return launch_splitk_train(a, splits, per, r.scratch, c.bm, st);
     HybridPlan h;
-    if (plan_hybrid(M64, cin, cout, c, &h) && h.scratch_floats <= scratch_floats && !a.stamps) {
+    if (plan_hybrid(M64, cin, cout, c, &h) && h.scratch_floats <= r.scratch_floats && !a.stamps) {
       const bool stats = flags & TDX_CONV_OUT_STATS;
-      if (c.bm == 128 && c.bn == 128) return launch_hybrid<128, 128>(a, h, splitk_scratch, stats, st);
-      if (c.bm == 128 && c.bn == 64) return launch_hybrid<128, 64>(a, h, splitk_scratch, stats, st);
-      return launch_hybrid<64, 64>(a, h, splitk_scratch, stats, st);
+      if (c.bm == 128 && c.bn == 128) return launch_hybrid<128, 128>(a, h, r.scratch, stats, st);
+      if (c.bm == 128 && c.bn == 64) return launch_hybrid<128, 64>(a, h, r.scratch, stats, st);
+      return launch_hybrid<64, 64>(a, h, r.scratch, stats, st);
     }
-  } else if (splitk_scratch && !(flags & TDX_CONV_OUT_STATS)) {
+  } else if (r.scratch && !(flags & TDX_CONV_OUT_STATS)) {
     int per;
-    const int splits = plan_splitk(M64, cin, cout, &per, scratch_floats);
+    const int splits = plan_splitk(M64, cin, cout, &per, r.scratch_floats);
     if (splits > 1) {
-      const bool in_bn = flags & TDX_CONV_IN_BNRELU;
-      if (flags & TDX_CONV_OUT_BNRELU)
-        return launch_splitk<EPI_BNRELU>(a, in_bn, splits, per, splitk_scratch, st, counters, n_counters, g_defer,
-                                         g_pool_out, &g_pool_done);
-      return launch_splitk<EPI_PLAIN>(a, in_bn, splits, per, splitk_scratch, st, counters, n_counters);
+      if (flags & TDX_CONV_OUT_BNRELU) return launch_splitk<EPI_BNRELU>(a, r, splits, per, st);
+      return launch_splitk<EPI_PLAIN>(a, r, splits, per, st);
     }
   }
   if (c.bm == 128 && c.bn == 128) return launch_conv<128, 128>(a, flags, st);
@@ -1387,13 +1337,30 @@ static int conv3x3_fwd_impl(const float* in, const float* wpk, const float* bias
   return launch_conv<64, 64>(a, flags, st);
 }
 
+// the fields every entry point has; the rest of the request stays zero until the entry point sets it
+static FwdRequest fwd_request(const float* in, const float* wpk, const float* bias, float* out, int B, int H, int W,
+                              int cin, int cout, int flags) {
+  FwdRequest r{};
+  r.in = in; r.wpk = wpk; r.bias = bias; r.out = out;
+  r.B = B; r.H = H; r.W = W; r.cin = cin; r.cout = cout; r.flags = flags;
+  return r;
+}
+
 extern "C" int tdx_conv3x3_fwd(const float* in, const float* wpk, const float* bias, float* out,
                                int B, int H, int W, int cin, int cout, int flags,
                                const float* in_scale, const float* in_shift,
                                const float* out_scale, const float* out_shift,
                                float* stats_partial, tdx_stream_t stream) {
-  return conv3x3_fwd_impl(in, wpk, bias, out, B, H, W, cin, cout, flags, in_scale, in_shift, out_scale,
-                          out_shift, stats_partial, nullptr, 0, stream);
+  FwdRequest r = fwd_request(in, wpk, bias, out, B, H, W, cin, cout, flags);
+  r.in_scale = in_scale; r.in_shift = in_shift; r.out_scale = out_scale; r.out_shift = out_shift;
+  r.stats_partial = stats_partial;
+  return conv3x3_fwd_impl(r, stream);
+}
+
+extern "C" int tdx_conv3x3_dgrad(const float* dy, const float* w_dgrad, float* dx, int B, int H, int W,
+                                 int cin, int cout, tdx_stream_t stream) {
+  // the forward kernel on dy with the mirrored, channel-swapped pack: its "cin" is this layer's cout
+  return conv3x3_fwd_impl(fwd_request(dy, w_dgrad, nullptr, dx, B, H, W, cout, cin, 0), stream);
 }
 
 // tdx_conv3x3_fwd_splitk with the reduction folded into the convolution: `counters` = n_counters zeroed
@@ -1404,15 +1371,18 @@ int tdx_conv3x3_fwd_splitk_fused(const float* in, const float* wpk, const float*
                                  int n_counters, tdx_stream_t stream, TdxSplitDefer* defer, TdxPoolFuse* pool) {
   if (!scratch) return TDX_E_BADARG;
   if (defer) *defer = TdxSplitDefer{};
-  g_defer = defer;
-  g_pool_out = pool ? pool->pooled : nullptr;
-  g_pool_done = false;
-  if (g_splitk_fused) g_defer = nullptr, g_pool_out = nullptr;   // (the in-kernel reduction experiment owns the epilogue)
-  const int rc = conv3x3_fwd_impl(in, wpk, bias, out, B, H, W, cin, cout, flags, nullptr, nullptr, out_scale, out_shift,
-                                  nullptr, scratch, scratch_floats, stream, false, counters, n_counters);
-  if (pool && !g_pool_done) pool->pooled = nullptr;   // not split: the caller runs the pooling kernel
-  g_defer = nullptr;
-  g_pool_out = nullptr;
+  bool pooled = false;
+  FwdRequest r = fwd_request(in, wpk, bias, out, B, H, W, cin, cout, flags);
+  r.out_scale = out_scale; r.out_shift = out_shift;
+  r.scratch = scratch; r.scratch_floats = scratch_floats;
+  r.counters = counters; r.n_counters = n_counters;
+  if (!g_splitk_fused) {   // (the in-kernel reduction experiment owns the epilogue)
+    r.defer = defer;
+    r.pool_out = pool ? pool->pooled : nullptr;
+    r.pooled = &pooled;
+  }
+  const int rc = conv3x3_fwd_impl(r, stream);
+  if (pool && !pooled) pool->pooled = nullptr;   // not split: the caller runs the pooling kernel
   return rc;
 }
 
@@ -1420,8 +1390,11 @@ extern "C" int tdx_conv3x3_fwd_train(const float* in, const float* wpk, const fl
                                      int H, int W, int cin, int cout, int flags, float* stats_partial,
                                      float* scratch, size_t scratch_floats, tdx_stream_t stream) {
   if (flags & ~TDX_CONV_OUT_STATS) return TDX_E_BADARG;
-  return conv3x3_fwd_impl(in, wpk, bias, out, B, H, W, cin, cout, flags, nullptr, nullptr, nullptr, nullptr,
-                          stats_partial, scratch, scratch_floats, stream, true);
+  FwdRequest r = fwd_request(in, wpk, bias, out, B, H, W, cin, cout, flags);
+  r.stats_partial = stats_partial;
+  r.scratch = scratch; r.scratch_floats = scratch_floats;
+  r.train = true;
+  return conv3x3_fwd_impl(r, stream);
 }
 
 // The input gradient of a unit (tdx_conv3x3_fwd_train with flags = 0 on the dgrad pack) whose result is
@@ -1435,14 +1408,16 @@ int tdx_conv3x3_dgrad_bnbwd(const float* in, const float* wpk, float* out, int B
   *nblk = 0;
   const int64_t M = (int64_t)B * H * W;
   int per;
-  if (!(g_tdx_bnbwd_fused & 1) || !g_conv_dma || !y || !partial || cin % BK || cout % 64 || M >= (1ll << 31) ||
-      plan_splitk_train(M, cin, cout, &per, scratch_floats) > 1 || g_conv_hybrid)
-    return conv3x3_fwd_impl(in, wpk, nullptr, out, B, H, W, cin, cout, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                            scratch, scratch_floats, stream, true);
-  g_bw = {y, scale, shift, mean, rstd, partial};
-  const int rc = conv3x3_fwd_impl(in, wpk, nullptr, out, B, H, W, cin, cout, TDX_CONV_OUT_BNBWD, nullptr, nullptr,
-                                  nullptr, nullptr, nullptr, nullptr, 0, stream, false);
-  g_bw = {};
+  FwdRequest r = fwd_request(in, wpk, nullptr, out, B, H, W, cin, cout, 0);
+  if (!(g_tdx_bnbwd_fused & 1) || !y || !partial || cin % BK || cout % 64 || M >= (1ll << 31) ||
+      plan_splitk_train(M, cin, cout, &per, scratch_floats) > 1 || g_conv_hybrid) {
+    r.scratch = scratch; r.scratch_floats = scratch_floats;
+    r.train = true;
+    return conv3x3_fwd_impl(r, stream);
+  }
+  r.flags = TDX_CONV_OUT_BNBWD;
+  r.bw = {y, scale, shift, mean, rstd, partial};
+  const int rc = conv3x3_fwd_impl(r, stream);
   if (rc) return rc;
   *nblk = cdiv(M, pick_tile(M, cout).bm);
   return 0;
@@ -1454,8 +1429,10 @@ extern "C" int tdx_conv3x3_fwd_splitk(const float* in, const float* wpk, const f
                                       const float* out_scale, const float* out_shift,
                                       float* scratch, size_t scratch_floats, tdx_stream_t stream) {
   if (!scratch) return TDX_E_BADARG;
-  return conv3x3_fwd_impl(in, wpk, bias, out, B, H, W, cin, cout, flags, in_scale, in_shift, out_scale,
-                          out_shift, nullptr, scratch, scratch_floats, stream);
+  FwdRequest r = fwd_request(in, wpk, bias, out, B, H, W, cin, cout, flags);
+  r.in_scale = in_scale; r.in_shift = in_shift; r.out_scale = out_scale; r.out_shift = out_shift;
+  r.scratch = scratch; r.scratch_floats = scratch_floats;
+  return conv3x3_fwd_impl(r, stream);
 }
 
 #define RC_(call) do { int rc__ = (call); if (rc__) return rc__; } while (0)
@@ -1638,7 +1615,7 @@ extern "C" size_t tdx_conv3x3_infer_scratch_floats(int B, int H, int W, int cin,
 // row: MFMA tile `im` then holds channels  base + TM*i + im  (i = MFMA row), a
 // permutation that the epilogue undoes.
 
-template <int BM, int BN, bool IN_BN>
+template <int BM, int BN>
 __global__ void __launch_bounds__(256)
 conv3x3_wgrad_kernel(WgradArgs a) {
   constexpr int WGM = 2, WGN = 2;
@@ -1678,10 +1655,8 @@ conv3x3_wgrad_kernel(WgradArgs a) {
   const int a_c4 = (tid % ACH) * 4, a_r0 = tid / ACH;
   const int b_c4 = (tid % BCH) * 4, b_r0 = tid / BCH;
   float4 sc4 = make_float4(1.f, 1.f, 1.f, 1.f), sh4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (IN_BN) {
-    sc4 = *reinterpret_cast<const float4*>(a.in_scale + ci0 + b_c4);
-    sh4 = *reinterpret_cast<const float4*>(a.in_shift + ci0 + b_c4);
-  }
+  sc4 = *reinterpret_cast<const float4*>(a.in_scale + ci0 + b_c4);
+  sh4 = *reinterpret_cast<const float4*>(a.in_shift + ci0 + b_c4);
 
   f32x16 acc[TM][TN];
 #pragma unroll
@@ -1754,7 +1729,7 @@ conv3x3_wgrad_kernel(WgradArgs a) {
       }
       const int ih = b_oh[i] + dh, iw = b_ow[i] + dw;
       const bool ok = (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W;
-      if (IN_BN) okB |= ok ? (1u << i) : 0u;
+      okB |= ok ? (1u << i) : 0u;
       S.rb[i] = __builtin_bit_cast(
           f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_in, ok ? b_off[i] : OOB, soff_b, 0));
     }
@@ -1772,13 +1747,11 @@ conv3x3_wgrad_kernel(WgradArgs a) {
     for (int i = 0; i < BI; ++i) {
       if ((i * 4) / BI != q) continue;
       f32x4 v = S.rb[i];
-      if (IN_BN) {
-        v[0] = fmaxf(fmaf(v[0], sc4.x, sh4.x), 0.f);
-        v[1] = fmaxf(fmaf(v[1], sc4.y, sh4.y), 0.f);
-        v[2] = fmaxf(fmaf(v[2], sc4.z, sh4.z), 0.f);
-        v[3] = fmaxf(fmaf(v[3], sc4.w, sh4.w), 0.f);
-        if (!((S.okB >> i) & 1u)) v = f32x4{0.f, 0.f, 0.f, 0.f};  // padding stays 0 after the transform
-      }
+      v[0] = fmaxf(fmaf(v[0], sc4.x, sh4.x), 0.f);
+      v[1] = fmaxf(fmaf(v[1], sc4.y, sh4.y), 0.f);
+      v[2] = fmaxf(fmaf(v[2], sc4.z, sh4.z), 0.f);
+      v[3] = fmaxf(fmaf(v[3], sc4.w, sh4.w), 0.f);
+      if (!((S.okB >> i) & 1u)) v = f32x4{0.f, 0.f, 0.f, 0.f};  // padding stays 0 after the transform
       *reinterpret_cast<f32x4*>(Bb + (b_r0 + BROWS * i) * BN + b_c4) = v;
     }
   };
@@ -2001,7 +1974,8 @@ struct WgradCfg {
   int bm, bn, splits, chunk;
 };
 
-static WgradCfg pick_wgrad_legacy(int64_t M, int cin, int cout, bool bf16) {
+// Tile and pixel split of the weight gradient (shared with the bf16 kernels: tdx_wgrad_plan)
+static WgradCfg pick_wgrad(int64_t M, int cin, int cout, bool bf16 = false) {
   WgradCfg c;
   c.bm = (cout % 128 == 0) ? 128 : 64;
   c.bn = (cin % 128 == 0) ? 128 : 64;
@@ -2014,13 +1988,14 @@ static WgradCfg pick_wgrad_legacy(int64_t M, int cin, int cout, bool bf16) {
   int64_t tiles = (int64_t)(cout / c.bm) * (cin / c.bn) * 9;
   const int target = (c.bm == 128 && c.bn == 128 && g_wgrad_target_big > 0) ? g_wgrad_target_big : g_wgrad_target;
   int64_t s = (target + tiles - 1) / tiles;
-  if (!bf16 && ((g_wgrad_plan == 1 && c.bm == c.bn) || g_wgrad_plan == 3)) {   // 3: rectangular tiles too (A/B)
+  if (!bf16 && c.bm == c.bn) {
     // Both targets are two rounds of the chip's workgroup slots (64x64: 4 per CU, 128x128: 2; lds_slots_per_cu),
     // but rounding the split count UP put most layers a few workgroups ABOVE two rounds (2052 on 1024 slots,
     // 1044 on 512), i.e. into a third round for 4 of them: isolated, 554 -> 463 us (256 -> 256 at 14x14),
     // 744 -> 608 (512 -> 128 at 16x16), 201 -> 165 (128 -> 128 at 16x16).  Round DOWN where the split is fine
     // enough for that to matter.  (Inside the step, where this kernel shares the CUs with the input-gradient
-    // GEMM, it is neutral; ONE round - fewest slabs - is 5 % slower there: nothing left to rebalance with.)
+    // GEMM, it is neutral; ONE round - fewest slabs, what a per-layer cost model picks - is 5 % slower there,
+    // 16.3 vs 15.6 ms: nothing left to rebalance with.)  Square tiles only.
     const int64_t two_rounds = 2 * 256 * (int64_t)lds_slots_per_cu(2 * 32 * (c.bm + c.bn) * 4);
     if (two_rounds / tiles >= 8) s = two_rounds / tiles;
   }
@@ -2035,41 +2010,6 @@ static WgradCfg pick_wgrad_legacy(int64_t M, int cin, int cout, bool bf16) {
   c.splits = (int)s;
   c.chunk = (int)chunk;
   return c;
-}
-
-// Experimental plan (knob wgrad_plan = 2): for every tile shape the layer's channels allow and 1..4 rounds of
-// workgroup slots, the largest split count whose workgroups fit those rounds; cost = GEMM time at the fill of
-// its rounds + slab write and re-read.  It picks one round almost everywhere (fewest slabs), which is the best
-// ISOLATED choice for most layers and 5 % slower inside the step (16.3 vs 15.6 ms): one long workgroup per slot
-// cannot be rebalanced against the input-gradient GEMM sharing the CUs.
-static WgradCfg pick_wgrad(int64_t M, int cin, int cout, bool bf16 = false) {
-  if (bf16 || g_wgrad_plan != 2) return pick_wgrad_legacy(M, cin, cout, bf16);
-  const int cand[4][2] = {{128, 128}, {128, 64}, {64, 128}, {64, 64}};
-  const double flops = 2.0 * (double)M * 9.0 * cin * cout;
-  const int64_t smax = (M + 255) / 256;
-  WgradCfg best = pick_wgrad_legacy(M, cin, cout, false);
-  double best_t = 1e30;
-  for (int i = 0; i < 4; ++i) {
-    const int bm = cand[i][0], bn = cand[i][1];
-    if (cout % bm || cin % bn) continue;
-    const int64_t tiles9 = (int64_t)(cout / bm) * (cin / bn) * 9;
-    const int64_t slots = 256 * (int64_t)lds_slots_per_cu(2 * 32 * (bm + bn) * 4);
-    const double tile_eff = (bm == 128 && bn == 128) ? 1.0 : (bm == 64 && bn == 64) ? 0.94 : 0.97;
-    for (int r = 1; r <= 4; ++r) {
-      if (g_wgrad_rounds > 0 && r != g_wgrad_rounds) continue;
-      int64_t s = r * slots / tiles9;
-      if (s > smax) s = smax;
-      if (s < 1) continue;
-      int64_t chunk = ((M + s - 1) / s + 31) / 32 * 32;
-      s = (M + chunk - 1) / chunk;
-      const int64_t wgs = tiles9 * s, rounds = (wgs + slots - 1) / slots;
-      const double fill = (double)wgs / (double)(rounds * slots);
-      const double t = flops / (157.3e12 * 0.85 * tile_eff * fill) +
-                       (double)s * cout * cin * 9.0 * 4.0 * 2.0 / 4.0e12 + (chunk < 512 ? 2e-6 : 0.0);
-      if (t < best_t) { best_t = t; best.bm = bm; best.bn = bn; best.splits = (int)s; best.chunk = (int)chunk; }
-    }
-  }
-  return best;
 }
 
 // which tile a shape resolves to (tests assert that every template is exercised):
@@ -2101,9 +2041,8 @@ template <int BM, int BN>
 static int launch_wgrad(const WgradArgs& a, int splits, bool in_bn, hipStream_t st) {
   const size_t lds = (size_t)2 * 32 * (BM + BN) * sizeof(float);
   dim3 grid((unsigned)(((int64_t)a.groups + 7) / 8 * 72));
-  if (in_bn) conv3x3_wgrad_kernel<BM, BN, true><<<grid, 256, lds, st>>>(a);
-  else if (g_conv_dma) conv3x3_wgrad_dma_kernel<BM, BN><<<grid, 256, lds, st>>>(a);
-  else conv3x3_wgrad_kernel<BM, BN, false><<<grid, 256, lds, st>>>(a);
+  if (in_bn) conv3x3_wgrad_kernel<BM, BN><<<grid, 256, lds, st>>>(a);
+  else conv3x3_wgrad_dma_kernel<BM, BN><<<grid, 256, lds, st>>>(a);
   TDX_CHECK_LAUNCH();
   return 0;
 }

@@ -17,7 +17,7 @@ struct ConvArgs {
   const float* out_shift;
   float* stats;  // [tilesM][2][Cout]
   int B, H, W, Cin, Cout, M, tilesN;
-  int splits, kt_per_split;  // split-K (variant 2): blockIdx.y = split, raw partials to `out`
+  int splits, kt_per_split;  // split-K: blockIdx.y = split, raw partials to `out`
   int dbg;                   // timing experiments only (tdx_tune_set "conv_dbg"): 1 no barrier,
                              // 2 no LDS stores, 4 no global loads in the main loop -> WRONG results
   // split-K with the reduction folded in (inference): workgroups of one tile count themselves in

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B of tuning knobs in ONE process (interleaved rounds): training ms/step and
-sampling ms/step.  usage: gpu_ab.py "conv_impl=1" "conv_impl=2" ..."""
+sampling ms/step.  usage: gpu_ab.py "conv_tile=0" "conv_tile=3" ..."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -14,7 +14,7 @@ def apply(spec):
         k, v = item.split("=")
         assert lib.tdx_tune_set(k.encode(), int(v)) == 0, k
 
-specs = sys.argv[1:] or ["conv_impl=1", "conv_impl=2"]
+specs = sys.argv[1:] or ["conv_tile=0", "conv_tile=3"]
 torch.manual_seed(0)
 m = NoiseModel().cuda().train(); fp = ForwardProcess()
 ts = TrainStep(m, fp, philox_seed=1)
