@@ -96,6 +96,27 @@ int tdx_p_sample_step_sched_philox(float* x_out, const float* x, const float* ep
                                    const int64_t* tau, const int32_t* k_idx, int64_t n, uint64_t seed,
                                    tdx_stream_t stream);
 
+/* Classifier-free guidance (Ho & Salimans 2021).  The null condition is label -1 (any negative label: emb = t_emb, no
+ * read of class_embedding) or an all-zero text-embedding row.  A guided chain of n samples keeps 2n rows: x and eps hold
+ * two halves of n_half_elems floats, the first evaluated under the caller's condition, the second under the null
+ * condition, and the halves of x are equal.  For j < n_half_elems:
+ *   e = eps[j + n_half_elems] + w (eps[j] - eps[j + n_half_elems]);   x' = c1 (x[j] - c2 e) + sigma z[j]
+ * written to x[j] and x[j + n_half_elems] (in place).  z: n_half_elems floats or NULL; use_philox: in-kernel noise
+ * indexed by j (the stream of the unguided chain of n samples); no noise at step 0.  tau: the schedule's timesteps
+ * (t_idx holds the step index k) or NULL for the identity chain.  counter_dec != NULL: *counter_dec = *t_idx - 1
+ * (the table-mode step counter, advanced by the last kernel of a step). */
+int tdx_p_sample_step_guided(float* x, const float* eps, const float* z, const float* coef, const int64_t* tau,
+                             const int32_t* t_idx, int64_t n_half_elems, float w, int use_philox, uint64_t philox_seed,
+                             int64_t* counter_dec, tdx_stream_t stream);
+
+/* Condition dropout for training the unconditional branch: sample b is dropped iff a Philox uniform in [0,1) keyed by
+ * (seed, offset, b) is < p (p == 0: exact copy, p == 1: every sample).  A dropped sample gets label -1 / a zeroed row.
+ * The two entries draw the same mask for the same key.  In place (y_out == y, c_out == c) is allowed. */
+int tdx_cond_drop_labels(const int64_t* y, int64_t* y_out, int B, float p, uint64_t seed, uint64_t offset,
+                         tdx_stream_t stream);
+int tdx_cond_drop_rows(const float* c, float* c_out, int B, int dim, float p, uint64_t seed, uint64_t offset,
+                       tdx_stream_t stream);
+
 /* Caller side of the path: minibatch gather from a device-resident uint8
  * dataset fused with ToTensor + Normalize((mean,),(std,)) of diffusion.py:202-204:
  *   out[b] = ((u8[idx[b]] / 255) - mean) / std      (idx == NULL: rows 0..batch-1)
@@ -596,6 +617,15 @@ int tdx_unet_eval_step_sched(tdx_unet* u, const void* const* params, void* const
                              int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
                              void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed,
                              tdx_stream_t stream);
+/* The guided reverse step (see tdx_p_sample_step_guided): batch = 2n rows of x / cond / eps whose second half carries
+ * the null condition, n_elems = the FIRST half's elements, z = n rows or NULL (Philox).  tau == NULL: the identity
+ * chain of tdx_unet_eval_step (S ignored).  Tables are prepared at batch 2n with the 2n-row cond.  The UNets only
+ * (the latent MLP returns TDX_E_SHAPE); the "sample_halves" knob does not apply. */
+int tdx_unet_eval_step_guided(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
+                              const void* cond, const float* z, const float* coef, const int64_t* tau, int S,
+                              int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
+                              void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed, float w,
+                              tdx_stream_t stream);
 
 /* Testing aid: offset (in floats) and element count of a named intermediate inside the
  * workspace after a forward: "x0", "Y0".."Y12", "ss0".."ss12", "e1p", "cat1", "d1a", ... */

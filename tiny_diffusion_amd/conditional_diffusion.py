@@ -4,6 +4,8 @@
 (conditional_diffusion.py:19, 115, 174, 354-386)."""
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 
 from .schedule import ForwardProcess, ddim_sample_loop, sample_loop
@@ -14,7 +16,8 @@ __all__ = ["NoiseModel", "ForwardProcess", "sample", "ddim_sample"]
 
 class NoiseModel(NoiseModelBase):
     """eps_theta(x_t, t, y): time embedding + nn.Embedding(num_classes, 256)[y],
-    conditional_diffusion.py:14-172."""
+    conditional_diffusion.py:14-172.  A label ``y[n] = -1`` is the null condition (no class: the time embedding
+    alone), what ``TrainStep(cond_drop_prob=...)`` trains and ``sample(guidance_scale=...)`` evaluates."""
 
     def __init__(self, time_dim: int = TIME_DIM, num_classes: int = 10):
         super().__init__(time_dim=time_dim, num_classes=num_classes)
@@ -24,20 +27,23 @@ class NoiseModel(NoiseModelBase):
 
 
 @torch.no_grad()
-def sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples=16, y=None, **kw):
-    """conditional_diffusion.py:354-386, including its argument errors."""
+def sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples=16, y=None,
+           guidance_scale: Optional[float] = None, **kw):
+    """conditional_diffusion.py:354-386, including its argument errors.  ``guidance_scale=w``: classifier-free
+    guidance ``eps_u + w (eps_c - eps_u)`` against the null label (schedule.sample_loop); ``None``: none."""
     _check_labels(y, n_samples)
-    return sample_loop(noise_model, diffusion, device, n_samples, y, **kw)
+    return sample_loop(noise_model, diffusion, device, n_samples, y, guidance_scale=guidance_scale, **kw)
 
 
 @torch.no_grad()
 def ddim_sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples=16, y=None, steps=50, eta=0.0,
-                timesteps=None, **kw):
+                timesteps=None, guidance_scale: Optional[float] = None, **kw):
     """DDIM sampling (Song et al. 2021): ``sample()``'s contract and argument errors over ``steps`` timesteps (or
-    the explicit list ``timesteps``) with stochasticity ``eta`` (schedule.ddim_schedule)."""
+    the explicit list ``timesteps``) with stochasticity ``eta`` (schedule.ddim_schedule); ``guidance_scale`` as in
+    ``sample()``."""
     _check_labels(y, n_samples)
     return ddim_sample_loop(noise_model, diffusion, device, n_samples, y, steps=steps, eta=eta, timesteps=timesteps,
-                            **kw)
+                            guidance_scale=guidance_scale, **kw)
 
 
 def _check_labels(y, n_samples):

@@ -9,6 +9,8 @@ text encoder the reference pulls from ``diffusers`` / ``transformers`` are exter
 and stay whatever object the caller passes in (out of scope)."""
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 
 from . import _lib
@@ -41,7 +43,9 @@ def get_timestep_embedding(timesteps, embedding_dim):
 
 class NoiseModel(NoiseModelBase):
     """eps_theta(x_t, t, text_embeds) on (4,32,32) latents: sinusoidal embedding -> time_mlp,
-    + text_embeds, UNet 32/64/128/256 (conditional_diffusion_laion.py:234-332)."""
+    + text_embeds, UNet 32/64/128/256 (conditional_diffusion_laion.py:234-332).  The condition enters only as
+    ``emb = t_emb + text_embeds``, so an all-zero ``text_embeds`` row is the null condition: what
+    ``TrainStep(cond_drop_prob=...)`` trains and ``sample(guidance_scale=...)`` evaluates."""
 
     def __init__(self, time_dim: int = TIME_DIM):
         super().__init__(time_dim=time_dim, num_classes=0, arch=ARCH_LAION)
@@ -65,27 +69,30 @@ def postprocess_images(decoded):
 
 @torch.no_grad()
 def sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, text_embeds=None, vae=None,
-           scaling_factor=1.0, **kw):
+           scaling_factor=1.0, guidance_scale: Optional[float] = None, **kw):
     """conditional_diffusion_laion.py:561-600: the reverse loop over latents, then
     ``vae.decode(x / scaling_factor).sample`` and the image post-processing.  With
-    ``vae=None`` the latents are returned (the decoder is an external pretrained model)."""
+    ``vae=None`` the latents are returned (the decoder is an external pretrained model).
+    ``guidance_scale=w``: classifier-free guidance ``eps_u + w (eps_c - eps_u)`` against the all-zero text
+    embedding (schedule.sample_loop); ``None``: none."""
     if text_embeds is None:
         raise ValueError("Text embeddings must be provided for conditional generation.")
     n_samples = text_embeds.shape[0]
-    x = sample_loop(noise_model, diffusion, device, n_samples, text_embeds, **kw)
+    x = sample_loop(noise_model, diffusion, device, n_samples, text_embeds, guidance_scale=guidance_scale, **kw)
     return _decode(x, vae, scaling_factor)
 
 
 @torch.no_grad()
 def ddim_sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, text_embeds=None, vae=None,
-                scaling_factor=1.0, steps=50, eta=0.0, timesteps=None, **kw):
+                scaling_factor=1.0, steps=50, eta=0.0, timesteps=None, guidance_scale: Optional[float] = None, **kw):
     """DDIM sampling (Song et al. 2021): ``sample()``'s contract, argument errors and decode over ``steps`` timesteps
-    (or the explicit list ``timesteps``) with stochasticity ``eta`` (schedule.ddim_schedule)."""
+    (or the explicit list ``timesteps``) with stochasticity ``eta`` (schedule.ddim_schedule); ``guidance_scale`` as
+    in ``sample()``."""
     if text_embeds is None:
         raise ValueError("Text embeddings must be provided for conditional generation.")
     n_samples = text_embeds.shape[0]
     x = ddim_sample_loop(noise_model, diffusion, device, n_samples, text_embeds, steps=steps, eta=eta,
-                         timesteps=timesteps, **kw)
+                         timesteps=timesteps, guidance_scale=guidance_scale, **kw)
     return _decode(x, vae, scaling_factor)
 
 

@@ -67,6 +67,12 @@ __device__ static inline float p_step(float x, float e, float z, float c1, float
   return __fadd_rn(__fmul_rn(c1, inner), __fmul_rn(sg, z));
 }
 
+// classifier-free guidance (Ho & Salimans 2021): eps_u + w (eps_c - eps_u), each operation rounded separately - the
+// one expression both guided updates evaluate (elementwise.hip, the epilogue of final_conv in edge_conv.hip)
+__device__ static inline float cfg_eps(float e_c, float e_u, float w) {
+  return __fadd_rn(e_u, __fmul_rn(w, __fsub_rn(e_c, e_u)));
+}
+
 __device__ static inline float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

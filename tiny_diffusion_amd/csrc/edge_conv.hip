@@ -124,12 +124,19 @@ thin_to_fat_conv_kernel(const float* __restrict__ thin, const float* __restrict_
 // eps_hat of an element also reads x, draws or loads z and writes x' in place (x is not an input of this kernel:
 // the network read it in initial_conv), exactly the arithmetic and the Philox indexing of p_sample_kernel; the
 // step's last launch disappears.  eps_hat is still written to `out`.
+// GD = true (with PS; classifier-free guidance): B = 2n samples whose first half ran under the caller's condition and
+// whose second half under the null condition, both from the same x.  The pixel loop runs over the first half's n H W
+// pixels; a lane group accumulates the convolution of its pixel AND of the twin pixel n H W further on against the same
+// LDS weight reads, writes both eps_hat values to `out`, combines them (cfg_eps) and writes the one update to both halves
+// of x.  Noise as in the unguided chain of n samples: z holds n samples, Philox is indexed by the first half's element.
 struct PSampleOps {
   float* x; const float* z; const float* coef; const int32_t* t_idx; uint64_t seed; int philox; int64_t* counter_dec;
   int64_t elem0;   // index of this launch's first element in the whole batch (a half-batch launch keeps the batch's Philox stream)
   const int64_t* tau;   // timestep schedule (DDIM): *t_idx is the step index k, the Philox stream tau[k]; null: identity
+  float w;              // GD: guidance scale
+  int64_t half;         // GD: elements of one half of x / out (the twin of element idx is idx + half)
 };
-template <int CO, bool DGRAD, bool PS, typename TF>
+template <int CO, bool DGRAD, bool PS, typename TF, bool GD = false>
 __global__ void __launch_bounds__(256)
 fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
                         const float* __restrict__ bias, float* __restrict__ out, int B, int H, int W, int cor,
@@ -149,7 +156,7 @@ fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
   __syncthreads();
   const int ci = (threadIdx.x & 15) * 4, pl = threadIdx.x >> 4;
   const int HW = H * W;
-  const int64_t M = (int64_t)B * HW;
+  const int64_t M = (int64_t)(GD ? B / 2 : B) * HW;   // GD: the first half's pixels, the twin of pixel p is p + M
   const int64_t Mpad = (M + 15) / 16 * 16;
   float bv[CO];
 #pragma unroll
@@ -165,9 +172,13 @@ fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
     if (ps.counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *ps.counter_dec = (int64_t)ps_t - 1;
   }
   for (int64_t p = (int64_t)blockIdx.x * 16 + pl; p < Mpad; p += (int64_t)gridDim.x * 16) {
-    float s[CO];
+    float s[CO], s2[GD ? CO : 1];
 #pragma unroll
     for (int co = 0; co < CO; ++co) s[co] = 0.f;
+    if (GD) {
+#pragma unroll
+      for (int co = 0; co < CO; ++co) s2[co] = 0.f;
+    }
     int n = 0, r = 0;
     if (p < M) {
       n = (int)(p / HW);
@@ -178,6 +189,8 @@ fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
         const int ih = oh + tap / 3 - 1, iw = ow + tap % 3 - 1;
         if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) {
           const float4 v = ld4(in + (p + (tap / 3 - 1) * W + (tap % 3 - 1)) * IC_CO + ci);
+          float4 v2 = v;
+          if (GD) v2 = ld4(in + (p + M + (tap / 3 - 1) * W + (tap % 3 - 1)) * IC_CO + ci);
 #pragma unroll
           for (int co = 0; co < CO; ++co) {
             const float4 wv = *reinterpret_cast<const float4*>(&ws[co][tap][ci]);
@@ -185,6 +198,12 @@ fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
             s[co] = fmaf(v.y, wv.y, s[co]);
             s[co] = fmaf(v.z, wv.z, s[co]);
             s[co] = fmaf(v.w, wv.w, s[co]);
+            if (GD) {
+              s2[co] = fmaf(v2.x, wv.x, s2[co]);
+              s2[co] = fmaf(v2.y, wv.y, s2[co]);
+              s2[co] = fmaf(v2.z, wv.z, s2[co]);
+              s2[co] = fmaf(v2.w, wv.w, s2[co]);
+            }
           }
         }
       }
@@ -195,6 +214,15 @@ fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
       s[co] += __shfl_xor(s[co], 4, 64);
       s[co] += __shfl_xor(s[co], 2, 64);
       s[co] += __shfl_xor(s[co], 1, 64);
+    }
+    if (GD) {
+#pragma unroll
+      for (int co = 0; co < CO; ++co) {
+        s2[co] += __shfl_xor(s2[co], 8, 64);
+        s2[co] += __shfl_xor(s2[co], 4, 64);
+        s2[co] += __shfl_xor(s2[co], 2, 64);
+        s2[co] += __shfl_xor(s2[co], 1, 64);
+      }
     }
     if ((threadIdx.x & 15) == 0 && p < M) {
 #pragma unroll
@@ -214,7 +242,15 @@ fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
               zv = ps.z[idx];
             }
           }
-          ps.x[idx] = p_step(ps.x[idx], e, zv, ps_c1, ps_c2, ps_sg);
+          if (GD) {
+            const float eu = s2[co] + bv[co];
+            out[idx + ps.half] = eu;
+            const float xn = p_step(ps.x[idx], cfg_eps(e, eu, ps.w), zv, ps_c1, ps_c2, ps_sg);
+            ps.x[idx] = xn;
+            ps.x[idx + ps.half] = xn;
+          } else {
+            ps.x[idx] = p_step(ps.x[idx], e, zv, ps_c1, ps_c2, ps_sg);
+          }
         }
       }
     }
@@ -498,12 +534,20 @@ int tdx_initial_conv_dgrad(const void* g_x0, const float* w, float* g_x, int B, 
 int tdx_final_conv_fwd_psample(const void* in, const float* w, const float* bias, float* eps_out, int B, int H, int W,
                                int cout, float* x, const float* z, const float* coef, const int32_t* t_idx,
                                uint64_t seed, int philox, int64_t* counter_dec, hipStream_t st, int io16, int64_t elem0,
-                               const int64_t* tau) {
+                               const int64_t* tau, int guided, float gw) {
   if (!x || !coef || !t_idx || (elem0 & 3)) return TDX_E_BADARG;
-  const int64_t M = (int64_t)B * H * W;
+  if (guided && ((B & 1) || elem0)) return TDX_E_BADARG;   // two equal halves, the whole batch in one launch
+  const int64_t M = (int64_t)(guided ? B / 2 : B) * H * W;
   const int grid = (int)std::min<int64_t>((M + 15) / 16, 8192);
-  const PSampleOps ps{x, z, coef, t_idx, seed, philox, counter_dec, elem0, tau};
+  const PSampleOps ps{x, z, coef, t_idx, seed, philox, counter_dec, elem0, tau, gw, guided ? M * cout : 0};
   if (cout != 1 && cout != 4) return TDX_E_SHAPE;
+  if (guided) {
+    TDX_IO_DISPATCH(io16, T,
+      if (cout == 1) fat_to_thin_conv_kernel<1, false, true, T, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps);
+      else fat_to_thin_conv_kernel<4, false, true, T, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps));
+    TDX_CHECK_LAUNCH();
+    return 0;
+  }
   TDX_IO_DISPATCH(io16, T,
     if (cout == 1) fat_to_thin_conv_kernel<1, false, true, T><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps);
     else fat_to_thin_conv_kernel<4, false, true, T><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps));

@@ -182,6 +182,50 @@ extern "C" int tdx_p_sample_step_sched_philox(float* x_out, const float* x, cons
   return 0;
 }
 
+// Guided update (classifier-free guidance).  x and eps hold 2 n4 float4: the first half ran the network under the
+// caller's condition, the second under the null condition, and the two halves of x are equal.  For i < n4:
+// e = cfg_eps(eps[i], eps[i + n4], w), x' = p_step(x[i], e, z, ...) written to x[i] and x[i + n4].  The noise is one draw
+// per element of the FIRST half - z has n4 float4, Philox is indexed by i - so the guided chain of n samples consumes
+// the stream of the unguided chain of n samples.  t, tau and counter_dec as in p_sample_kernel.
+__global__ void p_sample_guided_kernel(float4* x, const float4* __restrict__ eps, const float4* __restrict__ z,
+                                       const float* __restrict__ coef, const int32_t* __restrict__ t_idx, int64_t n4,
+                                       float w, int philox, uint64_t seed, int64_t* counter_dec,
+                                       const int64_t* __restrict__ tau) {
+  const int t = *t_idx;
+  const uint64_t nt = tau ? (uint64_t)tau[t] : (uint64_t)t;
+  if (counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *counter_dec = (int64_t)t - 1;
+  const float c1 = coef[3 * t + 0], c2 = coef[3 * t + 1], sg = coef[3 * t + 2];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 xv = x[i], ec = eps[i], eu = eps[i + n4];
+    float4 zv = make_float4(0.f, 0.f, 0.f, 0.f), o;
+    if (t > 0) {
+      if (philox) zv = philox_normal4((uint64_t)i, nt, seed);
+      else if (z) zv = z[i];
+    }
+    o.x = p_step(xv.x, cfg_eps(ec.x, eu.x, w), zv.x, c1, c2, sg);
+    o.y = p_step(xv.y, cfg_eps(ec.y, eu.y, w), zv.y, c1, c2, sg);
+    o.z = p_step(xv.z, cfg_eps(ec.z, eu.z, w), zv.z, c1, c2, sg);
+    o.w = p_step(xv.w, cfg_eps(ec.w, eu.w, w), zv.w, c1, c2, sg);
+    x[i] = o;
+    x[i + n4] = o;
+  }
+}
+
+// tau == null: the identity chain (t_idx holds the timestep); counter_dec != null: the table-mode decrement
+extern "C" int tdx_p_sample_step_guided(float* x, const float* eps, const float* z, const float* coef,
+                                        const int64_t* tau, const int32_t* t_idx, int64_t n_half_elems, float w,
+                                        int use_philox, uint64_t philox_seed, int64_t* counter_dec,
+                                        tdx_stream_t stream) {
+  if (!x || !eps || !coef || !t_idx || n_half_elems <= 0) return TDX_E_BADARG;
+  if (n_half_elems % 4) return TDX_E_SHAPE;
+  p_sample_guided_kernel<<<ew_grid(n_half_elems / 4, 256), 256, 0, to_stream(stream)>>>(
+      (float4*)x, (const float4*)eps, (const float4*)z, coef, t_idx, n_half_elems / 4, w, use_philox != 0, philox_seed,
+      counter_dec, tau);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
 // Device-side step counter for graph-captured sampling: t = *counter; t_idx = t; t_vec[:] = t;
 // *counter = t - 1.  One block; lets a HIP graph hold several consecutive reverse steps with no
 // host work between them (diffusion.py:259-260 builds the same t tensor on the host each step).
@@ -243,6 +287,38 @@ extern "C" int tdx_u8_gather_normalize(const uint8_t* data, const int64_t* idx, 
   const int64_t n4 = (int64_t)batch * per_sample / 4;
   gather_normalize_kernel<<<ew_grid(n4, 256), 256, 0, to_stream(stream)>>>(data, idx, out, n4,
                                                                          per_sample / 4, mean, stdv);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------- condition dropout
+// Training the unconditional branch of classifier-free guidance: sample b loses its condition iff a Philox uniform in
+// [0, 1) keyed by (seed, offset, b) is < p, so p == 0 is a copy and p == 1 drops every sample.  A dropped sample gets the
+// null label -1 (y != null: dim == 1) or a zeroed embedding row (c).  Elementwise: y_out == y / c_out == c is allowed.
+__global__ void cond_drop_kernel(const int64_t* y, int64_t* y_out, const float* c, float* c_out, int64_t n, int dim,
+                                 float p, uint64_t seed, uint64_t offset) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t b = (uint64_t)(i / dim);
+    const Philox4 r = philox4x32_10(b, offset, seed);
+    const bool drop = (float)(r.v[0] >> 8) * 5.9604644775390625e-8f < p;   // 24 bits: exact in fp32, never 1
+    if (y) y_out[i] = drop ? (int64_t)-1 : y[i];
+    else c_out[i] = drop ? 0.f : c[i];
+  }
+}
+
+extern "C" int tdx_cond_drop_labels(const int64_t* y, int64_t* y_out, int B, float p, uint64_t seed, uint64_t offset,
+                                    tdx_stream_t stream) {
+  if (!y || !y_out || B <= 0 || !(p >= 0.f && p <= 1.f)) return TDX_E_BADARG;
+  cond_drop_kernel<<<ew_grid(B, 256), 256, 0, to_stream(stream)>>>(y, y_out, nullptr, nullptr, B, 1, p, seed, offset);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tdx_cond_drop_rows(const float* c, float* c_out, int B, int dim, float p, uint64_t seed, uint64_t offset,
+                                  tdx_stream_t stream) {
+  if (!c || !c_out || B <= 0 || dim <= 0 || !(p >= 0.f && p <= 1.f)) return TDX_E_BADARG;
+  const int64_t n = (int64_t)B * dim;
+  cond_drop_kernel<<<ew_grid(n, 256), 256, 0, to_stream(stream)>>>(nullptr, nullptr, c, c_out, n, dim, p, seed, offset);
   TDX_CHECK_LAUNCH();
   return 0;
 }

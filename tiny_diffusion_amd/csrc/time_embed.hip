@@ -57,7 +57,10 @@ time_emb_kernel(const int64_t* __restrict__ t, const int64_t* __restrict__ y,
     wave_dot4(w2 + (size_t)i * TD, TD, hv, lane, d);
     if (lane < 4) {
       float e = d[lane] + b2[i + lane];
-      if (y) e += cls[(size_t)y[n] * TD + i + lane];
+      if (y) {
+        const int64_t c = y[n];   // c < 0: the null condition (classifier-free guidance), emb = t_emb, no read of cls
+        if (c >= 0) e += cls[(size_t)c * TD + i + lane];
+      }
       emb_out[(size_t)n * TD + i + lane] = e;
     }
   }
@@ -252,12 +255,14 @@ __global__ void time_l1_fwd_kernel(const int64_t* __restrict__ t, const float* _
 }
 
 // emb[n][:] += E[y[n]][:]   (nn.Embedding lookup added to the time embedding, conditional_diffusion.py:121-125)
+// y[n] < 0 is the null condition (classifier-free guidance; -1 is the documented value): the row stays t_emb
 __global__ void add_class_emb_kernel(float* __restrict__ emb, const float* __restrict__ cls,
                                      const int64_t* __restrict__ y, int B, int td) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * td) return;
   const int n = i / td, j = i - n * td;
-  emb[i] += cls[(size_t)y[n] * td + j];
+  const int64_t c = y[n];
+  if (c >= 0) emb[i] += cls[(size_t)c * td + j];
 }
 
 static int time_embed_fwd_generic0(const int64_t* t, const int64_t* y, const float* const* P, float* tf,
@@ -490,7 +495,8 @@ __global__ void class_emb_bwd_kernel(const float* __restrict__ g_emb, const int6
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = idx < ncls * td;
   const int c = live ? idx / td : 0, j = live ? idx - c * td : 0;
-  // labels are read as the LOW dwords of the int64 copy (values < num_classes), 256 at a time into LDS, by
+  // labels are read as the LOW dwords of the int64 copy (values < num_classes; the null condition, a negative label,
+  // has a negative low dword for every value down to -2^31 and so matches no class), 256 at a time into LDS, by
   // agent-scope loads: served by the coherent point, whatever line of that address this XCD's L2 may hold (the one
   // unexplained miscompute of this path was one stale-looking 128-byte line of such a copy)
   const int* y32 = reinterpret_cast<const int*>(y);
@@ -664,13 +670,14 @@ int tdx_time_tables_build(int kind, const float* const* P, int T, int td, float*
   return tdx_time_embed_fwd(kind, tt, nullptr, nullptr, P, sin, pre, emb, tab1, tab2, tab3, T, st, td);
 }
 
-// e_c[b][:] = E[y[b]][:]  (kind 0, class-conditional)
+// e_c[b][:] = E[y[b]][:]  (kind 0, class-conditional); a zero row for the null condition y[b] < 0
 __global__ void class_rows_kernel(const float* __restrict__ cls, const int64_t* __restrict__ y, float* __restrict__ out,
                                   int B, int td) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * td) return;
   const int n = i / td, j = i - n * td;
-  out[i] = cls[(size_t)y[n] * td + j];
+  const int64_t c = y[n];
+  out[i] = c >= 0 ? cls[(size_t)c * td + j] : 0.f;
 }
 
 // tabc{1,2,3}[b][:] = W_k c_b (no bias), c_b = E[y_b] (kind 0, labels) or the text embedding of sample b (kind 1).

@@ -234,7 +234,8 @@ struct tdx_unet {
   const int64_t* tab_tau;   // timestep schedule the T rows were built at (tdx_unet_prepare_sampling_sched); null: t = 0..T-1
   bool skip_time_path;   // set by tdx_unet_eval_step around its forward: the projections are already in the workspace
   // set by tdx_unet_eval_step around its forward: final_conv applies the reverse-process update in its epilogue
-  struct PS { float* x; const float* z; const float* coef; const int32_t* t_idx; uint64_t seed; int philox; int64_t* counter_dec; int64_t elem0; const int64_t* tau; } ps;
+  struct PS { float* x; const float* z; const float* coef; const int32_t* t_idx; uint64_t seed; int philox; int64_t* counter_dec; int64_t elem0; const int64_t* tau; int guided; float w; } ps;
+  bool whole_batch;      // set by a guided eval step around its forward: the two halves of a guided batch are not the halves of "sample_halves"
   // half-batch inference (tdx_unet_forward, INFER mode): the second half runs on this stream, forked from / joined to the caller's
   hipStream_t half_own;
   hipEvent_t ev_h_fork, ev_h_join;
@@ -381,6 +382,7 @@ extern "C" int tdx_unet_create_full(tdx_unet** out, int max_batch, int kind, int
   u->tab_cond = nullptr;
   u->tab_tau = nullptr;
   u->skip_time_path = false;
+  u->whole_batch = false;
   u->ps = {};
   u->precision = TDX_PREC_F32;
   u->saved_precision = TDX_PREC_F32;
@@ -671,7 +673,7 @@ static int pack_tail(tdx_unet* u, const void* const* params, tdx_stream_t stream
 // convolutions.  Results equal the whole-batch forward up to the summation order of the split-K plans (which
 // depend on M); in-kernel noise keeps the whole batch's Philox indexing (PS::elem0).
 static bool infer_halves(const tdx_unet* u, int batch, size_t workspace_bytes, int* b0) {
-  if (!u->spec || !u->half_own || !g_tdx_sample_halves || batch < 2 || batch < g_tdx_sample_halves_min) return false;
+  if (!u->spec || !u->half_own || u->whole_batch || !g_tdx_sample_halves || batch < 2 || batch < g_tdx_sample_halves_min) return false;
   const int h0 = (batch + 1) / 2;
   if (workspace_bytes < (make_layout(*u->spec, h0).total + make_layout(*u->spec, batch - h0).total) * sizeof(float)) return false;
   *b0 = h0;
@@ -953,7 +955,7 @@ static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const
   if (infer && ps.x)
     RC(tdx_final_conv_fwd_psample(ws + L.d1a, P[TDX_P_FINAL_W], P[TDX_P_FINAL_B], out, B, S.out_hw, S.out_hw, S.in_ch,
                                   ps.x, ps.z, ps.coef, ps.t_idx, ps.seed, ps.philox, ps.counter_dec, st, io16, ps.elem0,
-                                  ps.tau));
+                                  ps.tau, ps.guided, ps.w));
   else
     RC(tdx_final_conv_fwd(ws + L.d1a, P[TDX_P_FINAL_W], P[TDX_P_FINAL_B], out, B, S.out_hw, S.out_hw, S.in_ch, st, io16));
 
@@ -1322,12 +1324,18 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
 
 // tau == null: the step counter is the timestep t (tdx_unet_eval_step).  tau != null: a schedule of n_steps steps
 // (tdx_unet_eval_step_sched) - the counter is the step index k, the coefficient row, and the network runs at tau[k].
+// guided (tdx_unet_eval_step_guided): batch = 2n rows of x, the second half under the null condition, n_elems the first
+// half's; the update combines the two predictions with scale w and writes both halves (z: n rows).
 static int eval_step_impl(tdx_unet* u, const void* const* params, void* const* buffers, float* x, const void* cond,
                           const float* z, const float* coef, const int64_t* tau, int n_steps, int64_t* counter, int32_t* t_idx,
                           int64_t* t_vec, float* eps, int64_t n_elems, void* workspace, size_t workspace_bytes,
-                          int batch, uint64_t philox_seed, tdx_stream_t stream) {
+                          int batch, uint64_t philox_seed, tdx_stream_t stream, bool guided = false, float w = 0.f) {
   if (!u || !x || !coef || !counter || !t_idx || !t_vec || !eps || batch <= 0 || n_elems <= 0)
     return TDX_E_BADARG;
+  if (guided) {
+    if (!u->spec) return TDX_E_SHAPE;   // the UNets only
+    if ((batch & 1) || 2 * n_elems != (int64_t)batch * u->spec->in_ch * u->spec->out_hw * u->spec->out_hw) return TDX_E_BADARG;
+  }
   // Table mode (tdx_unet_prepare_sampling was called for this pack, batch and cond): ONE head kernel sets t and
   // adds two table rows per sample into the workspace's projection slots - in place of step_begin, the time MLP and
   // the three projections - and the update kernel advances the counter.
@@ -1347,7 +1355,7 @@ static int eval_step_impl(tdx_unet* u, const void* const* params, void* const* b
     const float* c2 = cond ? c1 + (size_t)batch * w1 : nullptr;
     const float* c3 = cond ? c2 + (size_t)batch * w2 : nullptr;
     int b0 = 0;
-    if (infer_halves(u, batch, workspace_bytes, &b0)) {   // the forward below runs as two half-batches: each half's projection slots
+    if (!guided && infer_halves(u, batch, workspace_bytes, &b0)) {   // the forward below runs as two half-batches: each half's projection slots
       const Layout L0 = make_layout(S, b0), L1 = make_layout(S, batch - b0);
       float* ws1 = ws + L0.total;
       RC(tdx_sample_head(counter, t_idx, t_vec, batch, u->tab_T, u->kind, t1, t2, t3, c1, c2, c3, ws + L0.tp[0],
@@ -1363,15 +1371,21 @@ static int eval_step_impl(tdx_unet* u, const void* const* params, void* const* b
     RC(tdx_step_begin(counter, t_idx, t_vec, batch, stream));
   }
   u->skip_time_path = tab;
+  u->whole_batch = guided;   // (set here, cleared below: no early return in between)
   // the UNets apply the update in final_conv's epilogue (one launch less); the latent MLP keeps the separate kernel
-  const bool fuse_ps = u->spec && (g_tdx_sample_fuse & 4) && n_elems == (int64_t)batch * u->spec->in_ch * u->spec->out_hw * u->spec->out_hw;
-  if (fuse_ps) u->ps = {x, z, coef, t_idx, philox_seed, z ? 0 : 1, tab ? counter : nullptr, 0, tau};
+  const bool fuse_ps = u->spec && (g_tdx_sample_fuse & 4) &&
+                       (guided ? 2 : 1) * n_elems == (int64_t)batch * u->spec->in_ch * u->spec->out_hw * u->spec->out_hw;
+  if (fuse_ps) u->ps = {x, z, coef, t_idx, philox_seed, z ? 0 : 1, tab ? counter : nullptr, 0, tau, guided, w};
   const int rc = tdx_unet_forward(u, params, buffers, x, t_vec, cond, eps, workspace, workspace_bytes, batch,
                                   TDX_MODE_INFER, stream);
   u->skip_time_path = false;
+  u->whole_batch = false;
   u->ps = {};
   if (rc) return rc;
   if (fuse_ps) return 0;
+  if (guided)
+    return tdx_p_sample_step_guided(x, eps, z, coef, tau, t_idx, n_elems, w, z ? 0 : 1, philox_seed, tab ? counter : nullptr,
+                                    stream);
   // elementwise, so x is updated in place; both kernels skip the noise term at t == 0
   if (tab) return tdx_p_sample_step_dec(x, x, eps, z, coef, t_idx, n_elems, philox_seed, counter, to_stream(stream), tau);
   if (tau) {
@@ -1399,6 +1413,18 @@ extern "C" int tdx_unet_eval_step_sched(tdx_unet* u, const void* const* params, 
   if (!tau || S <= 0) return TDX_E_BADARG;
   return eval_step_impl(u, params, buffers, x, cond, z, coef, tau, S, counter, t_idx, t_vec, eps, n_elems, workspace,
                         workspace_bytes, batch, philox_seed, stream);
+}
+
+// The guided step (classifier-free guidance): tdx_unet_eval_step_sched's arguments plus the scale w; tau == null is the
+// identity chain (S ignored).  batch = 2n, n_elems = the first half's elements.
+extern "C" int tdx_unet_eval_step_guided(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
+                                         const void* cond, const float* z, const float* coef, const int64_t* tau, int S,
+                                         int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
+                                         void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed, float w,
+                                         tdx_stream_t stream) {
+  if (tau && S <= 0) return TDX_E_BADARG;
+  return eval_step_impl(u, params, buffers, x, cond, z, coef, tau, tau ? S : 0, counter, t_idx, t_vec, eps, n_elems,
+                        workspace, workspace_bytes, batch, philox_seed, stream, true, w);
 }
 
 // Build the sampling tables for the CURRENT INFER pack (call after tdx_unet_pack / the first INFER forward, once

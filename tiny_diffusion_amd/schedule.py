@@ -4,6 +4,7 @@ mirroring ForwardProcess / sample() of the reference (diffusion.py:165-190,
 timestep schedules for DDIM sampling (Song et al. 2021) on the same kernels."""
 from __future__ import annotations
 
+import math
 import numbers
 from typing import Optional
 
@@ -12,7 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import lib, check
-from .unet import _cond_tensor
+from .unet import KIND_LAION, KIND_MNIST, _cond_tensor, _with_null_cond
 
 
 GRAPH_STEPS = 10  # reverse steps per captured graph in the device-counter mode
@@ -212,10 +213,28 @@ def ddpm_schedule(diffusion: ForwardProcess) -> TimestepSchedule:
                             coef.to(torch.float64), coef=coef)
 
 
+def _guidance_scale(noise_model, guidance_scale, y) -> float:
+    """The checked scale w of a guided chain: a finite number, on a conditional UNet, with a condition."""
+    arch = getattr(noise_model, "_arch", None)
+    kind = getattr(arch, "kind", None)
+    if not (kind == KIND_LAION or (kind == KIND_MNIST and getattr(noise_model, "num_classes", 0) > 0)):
+        raise ValueError("guidance_scale needs a conditional UNet (conditional_diffusion / conditional_diffusion_laion): "
+                         "this model has no null condition")
+    if isinstance(guidance_scale, bool) or not isinstance(guidance_scale, numbers.Real) \
+            or not math.isfinite(guidance_scale):
+        raise ValueError("guidance_scale must be a finite number (or None: no guidance)")
+    if y is None:
+        raise ValueError("guidance_scale needs the condition y")
+    return float(guidance_scale)
+
+
 def ddim_sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, y=None, steps: int = 50,
                      eta: float = 0.0, timesteps=None, **kw):
     """``sample_loop`` on ``ddim_schedule(diffusion, steps | timesteps, eta)``: ``timesteps``, when given,
-    replaces ``steps``.  The drop-in modules' ``ddim_sample`` functions call this."""
+    replaces ``steps``.  The drop-in modules' ``ddim_sample`` functions call this (``guidance_scale`` and the other
+    keywords of ``sample_loop`` pass through)."""
+    if kw.get("guidance_scale") is not None:
+        _guidance_scale(noise_model, kw["guidance_scale"], y)   # an argument error comes before the schedule's
     sched = ddim_schedule(diffusion, steps=None if timesteps is not None else steps, timesteps=timesteps, eta=eta)
     return sample_loop(noise_model, diffusion, device, n_samples, y, schedule=sched, **kw)
 
@@ -223,7 +242,8 @@ def ddim_sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: 
 @torch.no_grad()
 def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, y=None,
                 x_T: Optional[torch.Tensor] = None, noises=None, use_graph: bool = False,
-                philox_seed: Optional[int] = None, schedule: Optional[TimestepSchedule] = None):
+                philox_seed: Optional[int] = None, schedule: Optional[TimestepSchedule] = None,
+                guidance_scale: Optional[float] = None):
     """Reverse process, diffusion.py:254-276.
 
     Default (``x_T is None and noises is None``): the reference's RNG consumption -
@@ -237,7 +257,16 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
     ``GRAPH_STEPS`` consecutive steps (no host work between steps).
     ``schedule``: a ``TimestepSchedule`` (DDIM, ``ddim_schedule``): S steps k = S-1..0 at the timesteps
     ``schedule.timesteps[k]`` in the same three modes; recorded noise is ``noises[timesteps[k]]``.
+    ``guidance_scale``: ``None`` (no guidance: the code path above, unchanged) or a finite w - classifier-free guidance
+    (Ho & Salimans 2021) ``eps = eps_u + w (eps_c - eps_u)`` on the two conditional UNets, in the same three modes:
+    w = 1 is the conditional chain, w = 0 the unconditional one.  The network runs at batch 2n - rows [0, n) under
+    ``y``, rows [n, 2n) under the null condition (label -1 / a zero text embedding) - on a 2n-row state whose halves
+    stay equal; the noise is one draw per element of the first half (``noises[t]`` has n rows, Philox noise is indexed
+    as in the unguided chain of n samples), and the first half is returned.  ``ValueError`` for a non-finite w or a
+    model without a null condition (unconditional, latent MLP, transformer).
     """
+    guided = guidance_scale is not None
+    w = _guidance_scale(noise_model, guidance_scale, y) if guided else None
     device = torch.device(device)
     if device.type != "cuda":
         raise _lib.TdxError("sampling runs on the GPU only (no CPU fallback)")
@@ -251,6 +280,11 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
         y = y.to(device)
     if n_samples == 0:
         return x  # nothing to denoise (the reference loops over empty tensors)
+    if guided:   # 2n rows: the state twice, the condition followed by n null rows (built once per call)
+        x = torch.cat([x, x]).contiguous()
+        y = _with_null_cond(noise_model._arch.kind, _cond_tensor(noise_model._arch.kind, y))
+    rows = x.shape[0]         # the network's batch
+    half = x.numel() // 2     # guided: elements of one half of x
     # S steps k = S-1 .. 0: the counter / t_idx hold k (the coefficient row), t_vec the network's timestep taus[k].
     # tau is None on the reference's chain (k is the timestep: the plain C entries); with a schedule the kernels map
     # k to tau[k] themselves (tdx_*_sched).
@@ -261,14 +295,18 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
         S, taus = schedule.steps, schedule.timesteps.tolist()
         tau, coef = schedule.device_tables(device)
     t_idx = torch.empty(1, dtype=torch.int32, device=device)
-    t_vec = torch.empty(n_samples, dtype=torch.int64, device=device)
+    t_vec = torch.empty(rows, dtype=torch.int64, device=device)
     st = lambda: torch.cuda.current_stream(device).cuda_stream  # noqa: E731
-    zbuf = torch.empty_like(x)
+    zbuf = torch.empty_like(x[:n_samples])   # one draw per element of the n samples, guided or not
 
     def update(eps, z):
         """x <- c1 (x - c2 eps) + sigma z, elementwise and in place; Philox noise in the kernel under a seed."""
         xp, ep, cp, kp, n = x.data_ptr(), eps.data_ptr(), coef.data_ptr(), t_idx.data_ptr(), x.numel()
-        if tau is None and philox_seed is not None:
+        if guided:   # both halves of x from the combined prediction
+            check(lib.tdx_p_sample_step_guided(xp, ep, z, cp, None if tau is None else tau.data_ptr(), kp, half, w,
+                                               int(philox_seed is not None), philox_seed or 0, None, st()),
+                  "tdx_p_sample_step_guided")
+        elif tau is None and philox_seed is not None:
             check(lib.tdx_p_sample_step_philox(xp, xp, ep, cp, kp, n, philox_seed, st()), "tdx_p_sample_step")
         elif tau is None:
             check(lib.tdx_p_sample_step(xp, xp, ep, z, cp, kp, n, st()), "tdx_p_sample_step")
@@ -283,9 +321,9 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
         """t_idx <- counter, t_vec <- its timestep, counter <- counter - 1, on the device."""
         cp, kp, tp = counter.data_ptr(), t_idx.data_ptr(), t_vec.data_ptr()
         if tau is None:
-            check(lib.tdx_step_begin(cp, kp, tp, n_samples, st()), "tdx_step_begin")
+            check(lib.tdx_step_begin(cp, kp, tp, rows, st()), "tdx_step_begin")
         else:
-            check(lib.tdx_step_begin_sched(cp, tau.data_ptr(), kp, tp, n_samples, st()), "tdx_step_begin_sched")
+            check(lib.tdx_step_begin_sched(cp, tau.data_ptr(), kp, tp, rows, st()), "tdx_step_begin_sched")
 
     def step_kernels(use_z: bool):
         eps = noise_model._run_forward(x, t_vec, y, mode=2)[0]
@@ -321,7 +359,7 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
                 for _ in range(k):
                     if one_call:  # step counter + eps_theta + update behind one C-ABI entry
                         noise_model._run_eval_step(x, y_dev, coef, counter, t_idx, t_vec, eps_buf,
-                                                   philox_seed=philox_seed, tau=tau, S=S)
+                                                   philox_seed=philox_seed, tau=tau, S=S, guidance_scale=w)
                     else:
                         step_begin(counter)
                         step_kernels(False)
@@ -341,7 +379,7 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
             graph.replay()
         if tail_graph is not None:
             tail_graph.replay()
-        return x
+        return x[:n_samples].clone() if guided else x
 
     graph = None
     if use_graph:
@@ -356,11 +394,11 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
                 if noises is not None:
                     zbuf.copy_(noises[t].to(device))
                 else:
-                    zbuf.copy_(torch.randn_like(x))
+                    zbuf.copy_(torch.randn_like(zbuf))
             else:
                 zbuf.zero_()
         if graph is not None:
             graph.replay()
         else:
             step_kernels(True)
-    return x
+    return x[:n_samples].clone() if guided else x

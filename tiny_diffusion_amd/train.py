@@ -27,7 +27,7 @@ import torch
 
 from ._lib import lib, check
 from .schedule import ForwardProcess
-from .unet import MODE_TRAIN, MODE_EVAL_GRAD, NoiseModelBase, backward_stage_params
+from .unet import KIND_LAION, KIND_MNIST, MODE_TRAIN, MODE_EVAL_GRAD, NoiseModelBase, _cond_tensor, backward_stage_params
 
 
 def merge_ranges(ranges):
@@ -106,8 +106,14 @@ class TrainStep:
                  process_group=None, bucket_floats: int = 1 << 20, philox_seed: Optional[int] = None,
                  max_grad_norm: Optional[float] = None, cosine_T_max: Optional[int] = None,
                  cosine_eta_min: float = 0.0, use_graph: bool = False, data_parallel: bool = True,
-                 sync_bn: bool = False):
-        """``data_parallel=False`` keeps the step rank-local even inside an initialised process group
+                 sync_bn: bool = False, cond_drop_prob: float = 0.0, cond_drop_seed: int = 0):
+        """``cond_drop_prob`` (classifier-free guidance, Ho & Salimans 2021): each sample of a step loses its condition
+        with this probability - its label becomes -1, its text embedding a zero row - which trains the unconditional
+        branch that ``sample(guidance_scale=...)`` combines with the conditional one.  The mask is a Philox draw keyed by
+        ``(cond_drop_seed, step * world + rank, sample)`` (``tdx_cond_drop_*``; give it a seed other than
+        ``philox_seed``), applied to a copy of ``y``.  0 launches nothing and is today's step.  The conditional UNets only.
+
+        ``data_parallel=False`` keeps the step rank-local even inside an initialised process group
         (bench.py times it beside the collective step to report what the exchange costs).
 
         BatchNorm running statistics are rank-local (each rank's forward updates its own from its
@@ -116,6 +122,13 @@ class TrainStep:
         result does not depend on which rank saves (DDP's ``broadcast_buffers=True`` has that
         effect at every forward)."""
         self.model = model
+        if isinstance(cond_drop_prob, bool) or not isinstance(cond_drop_prob, (int, float)) \
+                or not 0.0 <= cond_drop_prob <= 1.0:
+            raise ValueError("cond_drop_prob must be in [0, 1]")
+        kind = model._arch.kind
+        if cond_drop_prob > 0 and not (kind == KIND_LAION or (kind == KIND_MNIST and model.num_classes > 0)):
+            raise ValueError("cond_drop_prob > 0 needs a conditional UNet: this model has no null condition")
+        self.cond_drop_prob, self.cond_drop_seed = float(cond_drop_prob), int(cond_drop_seed)
         # CosineAnnealingLR(optimizer, T_max, eta_min) stepped after every optimizer step
         self.base_lr, self.cosine_T_max, self.cosine_eta_min = lr, cosine_T_max, cosine_eta_min
         # torch.nn.utils.clip_grad_norm_(parameters, max_norm) between backward and the
@@ -204,7 +217,23 @@ class TrainStep:
         if (self.use_graph and t is None and noise is None and self.philox_seed is None and self.world == 1
                 and not self.reducer.force):
             return self._graph_step(x_0, y)
-        return self._eager_step(x_0, y, t, noise)
+        return self._eager_step(x_0, self._drop_cond(y), t, noise)
+
+    def _drop_cond(self, y, out=None):
+        """``y`` with the condition of this step's dropped samples replaced by the null condition (a new tensor, or
+        ``out``: in place is allowed); ``y`` itself when ``cond_drop_prob`` is 0 - no launch."""
+        if self.cond_drop_prob <= 0.0 or y is None:
+            return y
+        kind = self.model._arch.kind
+        y = _cond_tensor(kind, y)
+        out = torch.empty_like(y) if out is None else out
+        st = torch.cuda.current_stream(y.device).cuda_stream
+        key = (self.cond_drop_prob, self.cond_drop_seed, self._philox_offset(), st)
+        if kind == KIND_LAION:
+            check(lib.tdx_cond_drop_rows(y.data_ptr(), out.data_ptr(), y.shape[0], y.shape[1], *key), "tdx_cond_drop_rows")
+        else:
+            check(lib.tdx_cond_drop_labels(y.data_ptr(), out.data_ptr(), y.shape[0], *key), "tdx_cond_drop_labels")
+        return out
 
     def _philox_offset(self) -> int:
         """Philox stream of this (step, rank): ranks constructed with the same seed must not draw the
@@ -219,6 +248,8 @@ class TrainStep:
     def _graph_step(self, x_0, y):
         m = self.model
         dev = x_0.device
+        if self.cond_drop_prob > 0.0 and y is not None:
+            y = _cond_tensor(m._arch.kind, y.to(dev))   # the dtype the dropout kernel writes into _gy
         key = (tuple(x_0.shape), None if y is None else (tuple(y.shape), y.dtype), m.training)
         if key != self._graph_key:
             if self._graph_key is None or self._graph_key[1:] != ("warm",) + key:
@@ -226,7 +257,7 @@ class TrainStep:
                 # the next one captures
                 self._graph = self._graph_plan = None
                 self._graph_key = ("pending", "warm") + key
-                return self._eager_step(x_0, y, None, None)
+                return self._eager_step(x_0, self._drop_cond(y), None, None)
             self._gx0 = x_0.detach().clone().contiguous().float()
             self._gy = None if y is None else y.detach().clone().contiguous()
             self._hyper = torch.zeros(3, dtype=torch.float32, device=dev)
@@ -243,6 +274,7 @@ class TrainStep:
         self._gx0.copy_(x_0)
         if y is not None:
             self._gy.copy_(y)
+            self._drop_cond(self._gy, out=self._gy)   # before the replay: the captured graph reads _gy as it always did
         self.step_count += 1
         self._hyper.copy_(torch.tensor(self._adam_hyper(1.0), dtype=torch.float32))
         self._graph.replay()

@@ -8,6 +8,12 @@ reference's names and to give the reference's default initialisation (same
 constructors in the same order => bit-identical weights under the same
 ``torch.manual_seed``); none of the torch layers' ``forward`` is ever called.
 There is no CPU/eager fallback: a non-CUDA input raises.
+
+The null condition (classifier-free guidance): a label ``y[n] < 0`` (``NULL_LABEL = -1``) of the class-conditional
+UNet means "no class" - ``emb[n] = t_emb[n]``, in every mode, with no read of ``class_embedding`` and no gradient
+to it; for the LAION UNet it is an all-zero ``text_embeds`` row (``emb = t_emb + 0``).  No parameter is added: the
+``state_dict`` stays the reference's.  Labels are not checked on the host (that would force a sync); labels
+``>= num_classes`` are undefined.
 """
 from __future__ import annotations
 
@@ -198,6 +204,15 @@ def _cond_tensor(kind: int, y):
     if y is None:
         return None
     return y.contiguous().float() if kind == KIND_LAION else y.contiguous().to(torch.int64)
+
+
+NULL_LABEL = -1   # the null condition of the class-conditional UNet (any negative label): emb = t_emb
+
+
+def _with_null_cond(kind: int, y):
+    """``y`` (n rows, as ``_cond_tensor`` returns it) followed by n rows of the null condition - label ``NULL_LABEL`` or
+    an all-zero text embedding: the condition of a guided batch of 2n rows."""
+    return torch.cat([y, torch.zeros_like(y) if kind == KIND_LAION else torch.full_like(y, NULL_LABEL)]).contiguous()
 
 
 class _UNetFunction(torch.autograd.Function):
@@ -536,15 +551,20 @@ class NoiseModelBase(nn.Module):
         return plan, pptr, bptr, st
 
     def _run_eval_step(self, x, y, coef, counter, t_idx, t_vec, eps, z=None, philox_seed: int = 0, tau=None,
-                       S: int = 0):
+                       S: int = 0, guidance_scale: Optional[float] = None):
         """One reverse step of sample() in place on ``x`` (tdx_unet_eval_step): the step index is
         read from and decremented in device memory, so the call can sit in a HIP graph.  ``tau``: the
-        device timesteps of a schedule of ``S`` steps (tdx_unet_eval_step_sched; ``coef`` is then (S,3))."""
+        device timesteps of a schedule of ``S`` steps (tdx_unet_eval_step_sched; ``coef`` is then (S,3)).
+        ``guidance_scale``: the guided step (tdx_unet_eval_step_guided) - ``x``, ``y`` and ``eps`` hold 2n rows, the
+        second half under the null condition, ``z`` n rows."""
         plan, pptr, bptr, st = self._plan_ptrs(x)
         head = (plan.handle, pptr, bptr, x.data_ptr(), _dptr(y), _dptr(z), coef.data_ptr())
         rest = (counter.data_ptr(), t_idx.data_ptr(), t_vec.data_ptr(), eps.data_ptr(), x.numel(),
                 plan.workspace.data_ptr(), plan.ws_bytes, x.shape[0], philox_seed, st)
-        if tau is None:
+        if guidance_scale is not None:
+            rest = rest[:4] + (x.numel() // 2,) + rest[5:-1] + (float(guidance_scale), st)
+            check(lib.tdx_unet_eval_step_guided(*head, _dptr(tau), int(S), *rest), "tdx_unet_eval_step_guided")
+        elif tau is None:
             check(lib.tdx_unet_eval_step(*head, *rest), "tdx_unet_eval_step")
         else:
             check(lib.tdx_unet_eval_step_sched(*head, tau.data_ptr(), int(S), *rest), "tdx_unet_eval_step_sched")
