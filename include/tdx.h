@@ -643,8 +643,8 @@ int tdx_unet_pack(tdx_unet* u, const void* const* params, void* const* buffers,
  * "splitk" 0 | 1; the rest are listed in INTEGRATION.md.  An unknown key returns TDX_E_BADARG. */
 int tdx_tune_set(const char* key, int value);
 
-/* Diagnostics (tools/gpu_stage6_diag.py, gpu_clock_probe.py, ...): device buffer of `bytes` bytes that the
- * instrumented kernels (knobs "time_l1_impl" = 2, "conv_stamp", "probe_stamp") record into; NULL disables it.
+/* Diagnostics (tools/gpu_clock_probe.py, ...): device buffer of `bytes` bytes that the instrumented
+ * kernels (knob "conv_stamp") record into; NULL disables it.
  * A path whose records would not fit in `bytes` does not stamp (never writes past the end). */
 int tdx_diag_set_buffer(void* device_buffer, size_t bytes);
 int tdx_diag_conv_occupancy(int tile);  /* resident workgroups per CU of the forward kernel of tile bm*1000+bn */

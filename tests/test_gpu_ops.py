@@ -61,6 +61,16 @@ def test_library_exports(tdx):
     assert "libtdx.so" in maps
 
 
+def test_retired_knobs_are_unknown_keys(tdx):
+    """The keys of the retired diagnostic paths are refused like a typo; a live key is still taken
+    ("wino" 1 is its default, so nothing changes for the tests that follow)."""
+    for key in (b"time_stage", b"time_stage_diag", b"time_l1_impl", b"input_copy", b"time_proj_early",
+                b"splitk_fused"):
+        assert tdx.lib.tdx_tune_set(key, 0) != 0, key
+        assert tdx.lib.tdx_tune_set(key, 14) != 0, key   # the one value "time_stage" used to accept
+    assert tdx.lib.tdx_tune_set(b"wino", 1) == 0
+
+
 def test_q_sample_bit_exact(tdx, golden_dir):
     d = np.load(os.path.join(golden_dir, "fwd_B64_train_uncond.npz"))
     from tiny_diffusion_amd.diffusion import ForwardProcess

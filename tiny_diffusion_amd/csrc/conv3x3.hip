@@ -511,7 +511,6 @@ conv3x3_igemm_dma_kernel(ConvArgs a) {
     // raw partial of this K-slice: the split-K epilogue on a view of the remainder rows
     ConvArgs b = a;
     b.out = a.hyb_scratch + ((ptrdiff_t)hyb_slice * (a.M - a.hyb_row0) - a.hyb_row0) * (ptrdiff_t)a.Cout;
-    b.tile_counters = nullptr;
     conv_epilogue<BM, BN, EPI_PLAIN, true>(b, acc, smem, tile_m, m0, n0, wm, wn, l31, half, tid);
     return;
   }
@@ -840,10 +839,6 @@ static int g_conv_hybrid = 0;        // 1: training convolutions K-slice the til
                                       // OFF: isolated it gains 1 % on the roofline leg (120.9 -> 121.7 TFLOP/s), inside the step
                                       // nothing (the reduction launch it adds sits in the forward's dependent chain: 15.53 vs
                                       // 15.56 ms), and it adds 16 % HBM traffic per launch (221.9 -> 257.7 MB, PMC)
-static int g_splitk_fused = 0;       // 1: the last-arriving workgroup of a tile reduces the split-K partials (conv_epilogue).
-                                      // OFF: the device-scope release/acquire it needs (splits of a tile sit behind
-                                      // different XCDs' L2s: buffer_wbl2 / buffer_inv) costs ~68 us per convolution,
-                                      // the launch it saves ~5 - measured n=16 reverse step 0.527 -> 1.275 ms
 static int g_splitk_train = 1;       // training convolutions of latency-bound shapes split K (plan_splitk_train)
 static int g_splitk_train_t64 = 1024;   // ... when the 64x64 grid has fewer tiles than this
 static int g_splitk_train_target = 1536;  // ... into about this many workgroups
@@ -886,10 +881,6 @@ extern "C" int tdx_tune_set(const char* key, int value) {
   if (!strcmp(key, "splitk_target")) { g_splitk_target = value; return 0; }
   if (!strcmp(key, "streams")) { g_tdx_streams = value; return 0; }
   if (!strcmp(key, "materialize")) { g_tdx_materialize = value; return 0; }
-  // The stage-6 placement of the time path is NOT a supported setting: with the first version of
-  // time_l1_bwd_kernel it gave a wrong dW1 about once in 20-30 steps, cause not found.
-  // "time_stage" therefore accepts the default only; tools/gpu_stage6_diag.py uses the _diag key.
-  if (!strcmp(key, "time_stage")) { if (value != 14) return TDX_E_BADARG; g_tdx_time_stage = 14; return 0; }
   if (!strcmp(key, "stats_epi")) { g_conv_dbg = value ? (g_conv_dbg | 8) : (g_conv_dbg & ~8); return 0; }   // 1: one-pass (Chan) statistics epilogue
   if (!strcmp(key, "bf16_storage")) { g_tdx_bf16_storage = value != 0; return 0; }
   if (!strcmp(key, "sample_fuse")) { g_tdx_sample_fuse = value & 7; return 0; }
@@ -899,14 +890,9 @@ extern "C" int tdx_tune_set(const char* key, int value) {
   if (!strcmp(key, "sample_halves_min")) { g_tdx_sample_halves_min = value > 2 ? value : 2; return 0; }
   if (!strcmp(key, "bnbwd_fused")) { g_tdx_bnbwd_fused = value & 7; return 0; }
   if (!strcmp(key, "conv_hybrid")) { g_conv_hybrid = value != 0; return 0; }
-  if (!strcmp(key, "splitk_fused")) { g_splitk_fused = value != 0; return 0; }
   if (!strcmp(key, "splitk_train")) { g_splitk_train = value != 0; return 0; }
   if (!strcmp(key, "splitk_train_t64")) { g_splitk_train_t64 = value > 0 ? value : 1024; return 0; }
   if (!strcmp(key, "splitk_train_target")) { g_splitk_train_target = value > 0 ? value : 1536; return 0; }
-  if (!strcmp(key, "time_proj_early")) { g_tdx_time_proj_early = value != 0; return 0; }
-  if (!strcmp(key, "time_stage_diag")) { g_tdx_time_stage = value == 6 ? 6 : 14; return 0; }
-  if (!strcmp(key, "time_l1_impl")) { g_tdx_time_l1_impl = value; return 0; }
-  if (!strcmp(key, "input_copy")) { g_tdx_input_copy = value; return 0; }
   if (!strcmp(key, "conv_dbg")) { g_conv_dbg = value; return 0; }
   if (!strcmp(key, "bf16_materialize")) { g_tdx_bf16_materialize = value ? 1 : 0; return 0; }   // plans run afterwards
   if (!strcmp(key, "bf16_thin")) { g_tdx_bf16_thin = value < 0 ? 0 : value; return 0; }   // 0 | 1 | 2: conv3x3_bf16_thin_kernel
@@ -1207,8 +1193,6 @@ struct FwdRequest {
   TdxSplitDefer* defer;
   float* pool_out;
   bool* pooled;
-  unsigned* counters;      // knob splitk_fused: n_counters zeroed tile counters owned by the caller
-  int n_counters;
 };
 
 template <int EPI_>
@@ -1221,16 +1205,6 @@ static int launch_splitk(ConvArgs a, const FwdRequest& r, int splits, int per, h
   a.compact = !in_bn && cdiv(a.M, 64) < 64;
   dim3 grid(a.compact ? cdiv(a.M, 64) * a.tilesN : (cdiv(a.M, 64) + 7) / 8 * 8 * a.tilesN, splits);
   const size_t lds_dma = (size_t)2 * 128 * BK * sizeof(float);
-  if (r.counters && g_splitk_fused && !in_bn && cdiv(a.M, 64) * a.tilesN <= r.n_counters) {
-    // one launch: the last workgroup of every tile reduces (conv_epilogue); ~5 us per convolution of a
-    // reverse step, where a kernel boundary costs as much as a small kernel
-    a.tile_counters = r.counters;
-    a.final_out = final_out;
-    if (EPI_ != EPI_BNRELU) a.out_scale = a.out_shift = nullptr;
-    conv3x3_igemm_dma_kernel<64, 64, EPI_PLAIN, true><<<grid, 256, lds_dma, st>>>(a);
-    TDX_CHECK_LAUNCH();
-    return 0;
-  }
   if (in_bn)
     conv3x3_igemm2_kernel<64, 64, true, EPI_PLAIN, true><<<grid, 256, (size_t)2 * 128 * BKP * sizeof(float), st>>>(a);
   else conv3x3_igemm_dma_kernel<64, 64, EPI_PLAIN, true><<<grid, 256, lds_dma, st>>>(a);
@@ -1363,24 +1337,23 @@ extern "C" int tdx_conv3x3_dgrad(const float* dy, const float* w_dgrad, float* d
   return conv3x3_fwd_impl(fwd_request(dy, w_dgrad, nullptr, dx, B, H, W, cout, cin, 0), stream);
 }
 
-// tdx_conv3x3_fwd_splitk with the reduction folded into the convolution: `counters` = n_counters zeroed
-// unsigned ints owned by the caller for this purpose (the kernel leaves them zeroed)
+// tdx_conv3x3_fwd_splitk for the sampler.  defer != null: a split convolution leaves its raw partial slabs in
+// `scratch` and describes them in *defer (TdxSplitDefer) for the kernel that reads the result, which sums them
+// (splits == 0 on return: not split or not deferrable, `out` was written as usual).  pool != null: the reduction
+// also writes the following 2x2 ceil-mode max-pool to pool->pooled (set to null on return when it did not).
 int tdx_conv3x3_fwd_splitk_fused(const float* in, const float* wpk, const float* bias, float* out, int B, int H,
                                  int W, int cin, int cout, int flags, const float* out_scale,
-                                 const float* out_shift, float* scratch, size_t scratch_floats, unsigned* counters,
-                                 int n_counters, tdx_stream_t stream, TdxSplitDefer* defer, TdxPoolFuse* pool) {
+                                 const float* out_shift, float* scratch, size_t scratch_floats, tdx_stream_t stream,
+                                 TdxSplitDefer* defer, TdxPoolFuse* pool) {
   if (!scratch) return TDX_E_BADARG;
   if (defer) *defer = TdxSplitDefer{};
   bool pooled = false;
   FwdRequest r = fwd_request(in, wpk, bias, out, B, H, W, cin, cout, flags);
   r.out_scale = out_scale; r.out_shift = out_shift;
   r.scratch = scratch; r.scratch_floats = scratch_floats;
-  r.counters = counters; r.n_counters = n_counters;
-  if (!g_splitk_fused) {   // (the in-kernel reduction experiment owns the epilogue)
-    r.defer = defer;
-    r.pool_out = pool ? pool->pooled : nullptr;
-    r.pooled = &pooled;
-  }
+  r.defer = defer;
+  r.pool_out = pool ? pool->pooled : nullptr;
+  r.pooled = &pooled;
   const int rc = conv3x3_fwd_impl(r, stream);
   if (pool && !pooled) pool->pooled = nullptr;   // not split: the caller runs the pooling kernel
   return rc;

@@ -2,7 +2,6 @@
 #pragma once
 #include "common.h"
 
-int tdx_copy_floats(const float* src, float* dst, size_t n, hipStream_t st);
 int tdx_copy_segments(const float* const* src, float* const* dst, const size_t* n, int count, hipStream_t st);
 int tdx_pixel_sum(const void* g, float* out, int B, int HW, int C, hipStream_t st, int io16 = 0);
 int tdx_reduce_partials(const float* partial, float* out, int nblk, int stride, int count,
@@ -31,7 +30,7 @@ int tdx_final_conv_wgrad(const void* in, const float* g_out, float* partial, flo
 int tdx_time_embed_fwd(int kind, const int64_t* t, const int64_t* y, const float* cond,
                        const float* const* P, float* sin, float* pre, float* emb, float* t1, float* t2,
                        float* t3, int B, hipStream_t st, int td = 0);  // td: time_dim (0 = the kind's default)
-int tdx_time_embed_bwd(int kind, const int64_t* t, const int64_t* y, const float* const* P, float* const* G,
+int tdx_time_embed_bwd(int kind, const int64_t* y, const float* const* P, float* const* G,
                        const float* sin, const float* pre, const float* emb, const float* g_t1,
                        const float* g_t2, const float* g_t3, float* scratch, int B, int ncls,
                        hipStream_t st, int td = 0, int parts = 7);
@@ -46,9 +45,8 @@ struct TdxSplitDefer;
 struct TdxPoolFuse;
 int tdx_conv3x3_fwd_splitk_fused(const float* in, const float* wpk, const float* bias, float* out, int B, int H,
                                  int W, int cin, int cout, int flags, const float* out_scale,
-                                 const float* out_shift, float* scratch, size_t scratch_floats, unsigned* counters,
-                                 int n_counters, tdx_stream_t stream, TdxSplitDefer* defer = nullptr,
-                                 TdxPoolFuse* pool = nullptr);
+                                 const float* out_shift, float* scratch, size_t scratch_floats, tdx_stream_t stream,
+                                 TdxSplitDefer* defer = nullptr, TdxPoolFuse* pool = nullptr);
 // the inference convolution (conv3x3.hip, variant 4) on the tile-major pack, with the sampling-only extras of
 // tdx_conv3x3_fwd_splitk_fused (defer the split-K reduction to the consumer / fold the following max-pool into it)
 int tdx_conv3x3_fwd_infer_ex(const float* in, const float* w_tiled, const float* bias, float* out, int B, int H, int W,
@@ -102,8 +100,8 @@ int tdx_conv3x3_wgrad_reduce_pad(const float* dw_slabs, float* dw_oihw, int spli
 // tf: float(t) per sample, as stored by the forward (tdx_time_embed_fwd kind 0 -> sin, tdx_time_embed_only)
 int tdx_time_embed_bwd_ex(const float* tf, const int64_t* y, const float* const* P, float* const* G,
                           const float* pre, const float* emb, const float* const* gk, const int* ldg,
-                          const int* widths, float* scratch, int B, int ncls, hipStream_t st,
-                          const int64_t* t_i64 = nullptr, int td = 0, int parts = 7);
+                          const int* widths, float* scratch, int B, int ncls, hipStream_t st, int td = 0,
+                          int parts = 7);
 // synchronised BatchNorm pieces (bn.hip); tdx_allreduce_fn: include/tdx.h
 int tdx_bn_moments(const float* stats_partial, int tiles, int tile_rows, int64_t count, int C, double* mom,
                    hipStream_t st);
@@ -114,8 +112,6 @@ int tdx_bn_relu_bwd_sync(float* g, const float* y, int64_t rows, int C, const fl
                          const float* save_mean, const float* save_rstd, const float* gamma, float* dgamma,
                          float* dbeta, float* dbias, float* scratch, int training, tdx_allreduce_fn sync,
                          void* sync_user, double* mom, tdx_stream_t stream, int io16 = 0);
-extern int g_tdx_time_l1_impl;   // diagnostic: 1 = first version of time_l1_bwd_kernel (int64 t from the workspace copy)
-extern int g_tdx_input_copy;     // diagnostic: 1 = forward keeps its inputs with a copy KERNEL instead of hipMemcpyAsync
 int tdx_time_embed_only(const int64_t* t, const int64_t* y, const float* const* P, float* pre, float* emb,
                         float* tf_out, int B, hipStream_t st);
 // sampling tables (time_embed.hip) and the pieces of a table-mode reverse step
@@ -153,7 +149,6 @@ extern int g_tdx_bf16_materialize;
 // tuning knob "materialize": 1 = the activation feeding the second convolution of a stage is
 // written out (post BN+ReLU) so that convolution and its wgrad run on the LDS-DMA kernels
 extern int g_tdx_materialize;
-extern int g_tdx_time_stage;
 // tuning knob "bnbwd_fused": 1 = the kernel that PRODUCES dL/d(activation) of a unit (the input-gradient
 // convolution of the unit above, the resize adjoint or the max-pool backward) also emits the partial sums of that
 // unit's BatchNorm backward, and the separate reduction pass is skipped (unet.hip, tdx_unet_backward)
@@ -189,7 +184,6 @@ int tdx_bilinear_ac_fwd_t(const void* in, const float* scale, const float* shift
                           int Hi, int Wi, int Ho, int Wo, int C, int out_cstride, int out_coff, int io16,
                           tdx_stream_t stream);
 #define TDX_BNBWD_MAX_PRODUCER_BLOCKS 2048   // workgroups of the two spatial producers above
-extern int g_tdx_time_proj_early;
 // inference: both halves of a decoder's concatenated input (resize(a) | resize(b + b_addend)) in one launch
 // A split-K convolution of the sampling path whose reduction is DEFERRED to the kernel that reads its result
 // (tdx_conv3x3_fwd_splitk_fused with a non-null `defer`): `splits` raw partial slabs of `slab` floats at `partial`,

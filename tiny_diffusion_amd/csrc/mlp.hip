@@ -648,9 +648,11 @@ int tdx_latent_forward(const float* const* P, void* const* buffers, const float*
   const bool infer = mode == TDX_MODE_INFER;
   const int training = mode == TDX_MODE_TRAIN ? 1 : 0;
   if (!infer) {
-    TDX_HIP(hipMemcpyAsync(ws + L.z, z, (size_t)B * LATENT * sizeof(float), hipMemcpyDeviceToDevice, st));
-    TDX_HIP(hipMemcpyAsync(ws + L.t, t, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-    TDX_HIP(hipMemcpyAsync(ws + L.y, y, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    // keep the inputs for backward: one copy kernel, as in the UNet (the int64 tensors count as 2*B floats)
+    const float* src[3] = {z, reinterpret_cast<const float*>(t), reinterpret_cast<const float*>(y)};
+    float* dst[3] = {ws + L.z, ws + L.t, ws + L.y};
+    const size_t cnt[3] = {(size_t)B * LATENT, 2 * (size_t)B, 2 * (size_t)B};
+    RC(tdx_copy_segments(src, dst, cnt, 3, st));
   }
   RC(tdx_time_embed_only(t, y, P, ws + L.pre, ws + L.emb, ws + L.tf, B, st));
   const int pw[3] = {TDX_P_TP1_W, TDX_P_TP2_W, TDX_P_TP3_W};

@@ -369,103 +369,6 @@ time_l1_bwd_kernel(const float* __restrict__ g_h, const float* __restrict__ pre,
   }
 }
 
-// DIAGNOSTIC ONLY (knob time_l1_impl=1, tools/gpu_stage6_diag.py): the first version of the kernel
-// above, which converts the int64 step index inside its loop and reads it from the workspace copy of
-// t made by hipMemcpyAsync.  With the time path enqueued at backward stage 6 it produced a wrong
-// dW1 in some workgroups in round 1; kept so that the cause can be pinned down on
-// the GPU with the binary that showed it.
-__global__ void __launch_bounds__(256)
-time_l1_bwd_i64_kernel(const float* __restrict__ g_h, const float* __restrict__ pre,
-                       const int64_t* __restrict__ t, float* __restrict__ dw1, float* __restrict__ db1,
-                       int B) {
-  __shared__ float red[2][8][32];
-  const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  const int j = blockIdx.x * 32 + cl;
-  float sw = 0.f, sb = 0.f;
-#pragma unroll 4
-  for (int n = sl; n < B; n += 8) {
-    const float gp = g_h[(size_t)n * TD + j] * silu_grad_f(pre[(size_t)n * TD + j]);
-    sw = fmaf(gp, (float)t[n], sw);
-    sb += gp;
-  }
-  red[0][sl][cl] = sw;
-  red[1][sl][cl] = sb;
-  __syncthreads();
-  if (sl == 0) {
-    sw = 0.f; sb = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { sw += red[0][k][cl]; sb += red[1][k][cl]; }
-    dw1[j] = sw;
-    db1[j] = sb;
-  }
-}
-// DIAGNOSTIC ONLY (time_l1_impl=3): the first version again, with t read by agent-scope atomic loads (served by
-// the coherent point, not by whatever line this XCD's L2 may hold): if the wrong dW1 is a stale L2 line - the
-// error is exactly 16 consecutive samples = one 128-byte line of t in the clean failures - it cannot recur here.
-__global__ void __launch_bounds__(256)
-time_l1_bwd_i64_coherent_kernel(const float* __restrict__ g_h, const float* __restrict__ pre,
-                                const int64_t* t, float* __restrict__ dw1, float* __restrict__ db1, int B) {
-  __shared__ float red[2][8][32];
-  const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  const int j = blockIdx.x * 32 + cl;
-  float sw = 0.f, sb = 0.f;
-#pragma unroll 4
-  for (int n = sl; n < B; n += 8) {
-    const float gp = g_h[(size_t)n * TD + j] * silu_grad_f(pre[(size_t)n * TD + j]);
-    const int64_t tv = __hip_atomic_load(t + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    sw = fmaf(gp, (float)tv, sw);
-    sb += gp;
-  }
-  red[0][sl][cl] = sw;
-  red[1][sl][cl] = sb;
-  __syncthreads();
-  if (sl == 0) {
-    sw = 0.f; sb = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { sw += red[0][k][cl]; sb += red[1][k][cl]; }
-    dw1[j] = sw;
-    db1[j] = sb;
-  }
-}
-// DIAGNOSTIC ONLY (time_l1_impl=2): the same loop, additionally recording what it loaded:
-// dbg[0..7] per workgroup = {t pointer lo, hi, XCC id, s_memrealtime lo at start, at end, B, 0, 0} then,
-// from dbg + 64*8 on, the raw int64 each (workgroup, slice, k) read, as two dwords.
-__global__ void __launch_bounds__(256)
-time_l1_bwd_i64_dbg_kernel(const float* __restrict__ g_h, const float* __restrict__ pre,
-                           const int64_t* __restrict__ t, float* __restrict__ dw1, float* __restrict__ db1,
-                           int B, unsigned* __restrict__ dbg) {
-  __shared__ float red[2][8][32];
-  const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  const int j = blockIdx.x * 32 + cl;
-  const unsigned t0 = (unsigned)__builtin_amdgcn_s_memrealtime();
-  float sw = 0.f, sb = 0.f;
-  unsigned* seen = dbg + 64 * 8 + (size_t)blockIdx.x * (2 * 1024);  // up to 1024 samples per workgroup
-#pragma unroll 4
-  for (int n = sl; n < B; n += 8) {
-    const float gp = g_h[(size_t)n * TD + j] * silu_grad_f(pre[(size_t)n * TD + j]);
-    const int64_t tv = t[n];
-    if (cl == 0 && n < 1024) { seen[2 * n] = (unsigned)tv; seen[2 * n + 1] = (unsigned)((uint64_t)tv >> 32); }
-    sw = fmaf(gp, (float)tv, sw);
-    sb += gp;
-  }
-  red[0][sl][cl] = sw;
-  red[1][sl][cl] = sb;
-  __syncthreads();
-  if (sl == 0) {
-    sw = 0.f; sb = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { sw += red[0][k][cl]; sb += red[1][k][cl]; }
-    dw1[j] = sw;
-    db1[j] = sb;
-  }
-  if (threadIdx.x == 0) {
-    unsigned* h = dbg + blockIdx.x * 8;
-    h[0] = (unsigned)(uintptr_t)t; h[1] = (unsigned)((uintptr_t)t >> 32);
-    h[2] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 0xf;   // HW_REG_XCC_ID, bits 3:0
-    h[3] = t0; h[4] = (unsigned)__builtin_amdgcn_s_memrealtime(); h[5] = (unsigned)B;
-  }
-}
-int g_tdx_time_l1_impl = 0;
 int g_tdx_probe_stamp = 0;
 unsigned* g_tdx_diag_buffer = nullptr;  // set by tdx_diag_set_buffer together with its size:
 size_t g_tdx_diag_bytes = 0;            // every diagnostic path checks what it is about to write against it
@@ -549,8 +452,7 @@ static int time_embed_bwd_laion(const float* const* P, float* const* G, const fl
 // (g_tk[n*ldg[k] + o], o < widths[k]).  scratch: g_emb (B*256) | h (B*256) | g_h (B*256)
 int tdx_time_embed_bwd_ex(const float* tf, const int64_t* y, const float* const* P, float* const* G,
                           const float* pre, const float* emb, const float* const* gk, const int* ldg,
-                          const int* widths, float* scratch, int B, int ncls, hipStream_t st,
-                          const int64_t* t_i64, int td, int parts) {
+                          const int* widths, float* scratch, int B, int ncls, hipStream_t st, int td, int parts) {
   if (td <= 0) td = TD;
   float* g_emb = scratch;
   float* h = scratch + (size_t)B * td;
@@ -577,21 +479,12 @@ int tdx_time_embed_bwd_ex(const float* tf, const int64_t* y, const float* const*
     TDX_CHECK_LAUNCH();
   }
   if (!(parts & TDX_TIME_L1)) return 0;
-  if (g_tdx_time_l1_impl == 2 && t_i64 && g_tdx_diag_buffer && td == TD &&
-      g_tdx_diag_bytes >= (64 * 8 + 8 * 2048) * sizeof(unsigned))   // what the instrumented kernel records
-    time_l1_bwd_i64_dbg_kernel<<<td / 32, 256, 0, st>>>(g_h, pre, t_i64, G[TDX_P_TE0_W], G[TDX_P_TE0_B], B,
-                                                        g_tdx_diag_buffer);
-  else if (g_tdx_time_l1_impl == 1 && t_i64 && td == TD)
-    time_l1_bwd_i64_kernel<<<td / 32, 256, 0, st>>>(g_h, pre, t_i64, G[TDX_P_TE0_W], G[TDX_P_TE0_B], B);
-  else if (g_tdx_time_l1_impl == 3 && t_i64 && td == TD)
-    time_l1_bwd_i64_coherent_kernel<<<td / 32, 256, 0, st>>>(g_h, pre, t_i64, G[TDX_P_TE0_W], G[TDX_P_TE0_B], B);
-  else
-    time_l1_bwd_kernel<<<cdiv(td, 32), 256, 0, st>>>(g_h, pre, tf, G[TDX_P_TE0_W], G[TDX_P_TE0_B], B, td);
+  time_l1_bwd_kernel<<<cdiv(td, 32), 256, 0, st>>>(g_h, pre, tf, G[TDX_P_TE0_W], G[TDX_P_TE0_B], B, td);
   TDX_CHECK_LAUNCH();
   return 0;
 }
 
-int tdx_time_embed_bwd(int kind, const int64_t* t, const int64_t* y, const float* const* P, float* const* G,
+int tdx_time_embed_bwd(int kind, const int64_t* y, const float* const* P, float* const* G,
                        const float* sin, const float* pre, const float* emb, const float* g_t1,
                        const float* g_t2, const float* g_t3, float* scratch, int B, int ncls,
                        hipStream_t st, int td, int parts) {
@@ -601,7 +494,7 @@ int tdx_time_embed_bwd(int kind, const int64_t* t, const int64_t* y, const float
     return time_embed_bwd_laion(P, G, sin, pre, emb, g_t1, g_t2, g_t3, scratch, B, td, st, parts);
   const float* gk[3] = {g_t1, g_t2, g_t3};
   const int widths[3] = {128, 256, 512};
-  return tdx_time_embed_bwd_ex(sin, y, P, G, pre, emb, gk, widths, widths, scratch, B, ncls, st, t, td, parts);
+  return tdx_time_embed_bwd_ex(sin, y, P, G, pre, emb, gk, widths, widths, scratch, B, ncls, st, td, parts);
 }
 
 // Backward of ONE time projection (k = 0, 1, 2 <-> time_proj1/2/3), for a caller that has the three
@@ -767,7 +660,7 @@ extern "C" int tdx_time_mlp_bwd(const int64_t* t, const int64_t* y, const void* 
   float* tf = scratch + (size_t)3 * batch * TD;
   t_to_float_kernel<<<cdiv(batch, 256), 256, 0, to_stream(stream)>>>(t, tf, batch);
   TDX_CHECK_LAUNCH();
-  return tdx_time_embed_bwd(0, t, y, reinterpret_cast<const float* const*>(params),
+  return tdx_time_embed_bwd(0, y, reinterpret_cast<const float* const*>(params),
                             reinterpret_cast<float* const*>(grads), tf, pre, emb, g_t1, g_t2, g_t3, scratch,
                             batch, y ? num_classes : 0, to_stream(stream));
 }

@@ -64,7 +64,6 @@ const NetSpec SPECS[2] = {
       {64, 64, 32, 1, 64}}}};
 
 constexpr int N_STAGES = 15;
-constexpr int TDX_KCOUNT = 1024;
 
 // The table rows are the reference resolutions.  The LAION network is fully convolutional
 // (floor-mode pooling, exact 2x up-sampling, skips at equal resolution:
@@ -200,9 +199,6 @@ int g_tdx_wino_min_wgs = 100;
 int g_tdx_wino_wgrad = 1;               // knob "wino_wgrad": weight gradients by F(3x3,2x2) (conv3x3_wgrad_wino_kernel)
 int g_tdx_wino_wgrad_min_tiles = 1024;  // knob "wino_wgrad_min_tiles"
 int g_tdx_wino_infer_min_units = 700;   // knob "wino_infer_min_units" (n = 16: 784 for the first 64->128 layer, 512 for the 4x4 / 64-channel ones)
-int g_tdx_time_proj_early = 1;  // time_proj backward right behind each pixel sum (0: with the rest, at the end)
-int g_tdx_time_stage = 14;  // backward stage after which the time/class path runs (14, or 6: see DESIGN.md 3.2)
-int g_tdx_input_copy = 2;   // knob "input_copy": 0 hipMemcpyAsync, 1 three copy kernels, 2 one fused copy kernel (default)
 int g_tdx_streams = -1;  // tuning knob "streams": -1 = per-network default (NetSpec::overlap), 0 / 1 = force
 
 struct PlanHandles {
@@ -220,7 +216,6 @@ struct tdx_unet {
   size_t uf_off[13], ud_off[13];
   bool wino_f[13], wino_d[13], wino_w[13];   // this step's forward / input gradient / weight gradient of unit i runs on the Winograd kernels (decided per forward)
   float* infer_ss;         // device: per unit scale|shift from running stats (INFER mode)
-  unsigned* kcount;        // device: TDX_KCOUNT zeroed tile counters of the fused split-K reduction (INFER mode)
   size_t iss_off[13];
   bool packed;
   bool wf_tiled;           // INFER pack of the fp32 mode: wf holds the tile-major pack of the inference convolution (conv3x3.hip, variant 4)
@@ -368,10 +363,7 @@ extern "C" int tdx_unet_create_full(tdx_unet** out, int max_batch, int kind, int
     if (e != hipSuccess) { (void)hipFree(u->wpack); delete u; return (int)e; }
   }
   e = hipMalloc(&u->infer_ss, so * sizeof(float));
-  if (e != hipSuccess) { (void)hipFree(u->wpack); delete u; return (int)e; }
-  e = hipMalloc(&u->kcount, TDX_KCOUNT * sizeof(unsigned));
-  if (e == hipSuccess) e = hipMemset(u->kcount, 0, TDX_KCOUNT * sizeof(unsigned));
-  if (e != hipSuccess) { (void)hipFree(u->wpack); (void)hipFree(u->infer_ss); (void)hipFree(u->kcount); delete u; return (int)e; }
+  if (e != hipSuccess) { (void)hipFree(u->wpack); if (u->upack) (void)hipFree(u->upack); delete u; return (int)e; }
   u->packed = false;
   u->wf_tiled = false;
   u->tab = nullptr;
@@ -399,7 +391,7 @@ extern "C" int tdx_unet_create_full(tdx_unet** out, int max_batch, int kind, int
   u->materialize = g_tdx_materialize != 0;
   u->use_streams = g_tdx_streams < 0 ? (u->spec ? u->spec->overlap : 0) : g_tdx_streams;
   if (!make_handles(&u->handles)) {
-    (void)hipFree(u->wpack); if (u->upack) (void)hipFree(u->upack); (void)hipFree(u->infer_ss); (void)hipFree(u->kcount);
+    (void)hipFree(u->wpack); if (u->upack) (void)hipFree(u->upack); (void)hipFree(u->infer_ss);
     delete u;
     return TDX_E_STATE;
   }
@@ -454,7 +446,6 @@ extern "C" int tdx_unet_destroy(tdx_unet* u) {
   (void)hipFree(u->wpack);
   if (u->upack) (void)hipFree(u->upack);
   (void)hipFree(u->infer_ss);
-  (void)hipFree(u->kcount);
   if (u->tab) (void)hipFree(u->tab);
   delete u;
   return 0;
@@ -761,28 +752,14 @@ static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const
   if (!infer) RC(pack_impl(u, params, nullptr, stream, true, B));  // weights change every step
   else if (!u->packed) RC(pack_impl(u, params, buffers, stream));
   if (!infer) {
-    // keep the inputs for backward (caller tensors may be gone by then).  Default (knob input_copy = 2, round 4): ONE
-    // copy KERNEL on the compute stream for x, t and the labels.  Rounds 1-3 used hipMemcpyAsync and found one
-    // 128-byte line of such a copy stale in ONE XCD's L2 about once in 30 steps (a copy-engine write
-    // into recycled allocator memory that a later kernel's acquire did not invalidate) - patched reader by reader
-    // with agent-scope loads.  A kernel's writes are released at its end and acquired by the next kernel like every
-    // other tensor of the step, which removes the class of bug; the sc1 loads stay as a second line of defence.
-    // Cost measured at B = 256 (tools/gpu_ab.py): three copy kernels (input_copy = 1) +47 us per step, one fused: see DESIGN.md 6.
+    // keep the inputs for backward (caller tensors may be gone by then): ONE copy kernel on the compute stream for
+    // x, t and the labels.  A kernel's writes are released at its end and acquired by the next kernel like every
+    // other tensor of the step; the agent-scope loads of the readers stay as a second line of defence.
     const size_t nx = (size_t)B * S.hw0 * S.hw0 * S.in_ch;
-    if (g_tdx_input_copy == 2) {
-      const float* src[3] = {x, reinterpret_cast<const float*>(t), reinterpret_cast<const float*>(labels)};
-      float* dst[3] = {ws + L.x, ws + L.t, ws + L.y};
-      const size_t cnt[3] = {nx, 2 * (size_t)B, labels ? 2 * (size_t)B : 0};
-      RC(tdx_copy_segments(src, dst, cnt, 3, st));
-    } else if (g_tdx_input_copy == 1) {
-      RC(tdx_copy_floats(x, ws + L.x, nx, st));
-      RC(tdx_copy_floats(reinterpret_cast<const float*>(t), ws + L.t, 2 * (size_t)B, st));
-      if (labels) RC(tdx_copy_floats(reinterpret_cast<const float*>(labels), ws + L.y, 2 * (size_t)B, st));
-    } else {
-      TDX_HIP(hipMemcpyAsync(ws + L.x, x, nx * sizeof(float), hipMemcpyDeviceToDevice, st));
-      TDX_HIP(hipMemcpyAsync(ws + L.t, t, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-      if (labels) TDX_HIP(hipMemcpyAsync(ws + L.y, labels, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-    }
+    const float* src[3] = {x, reinterpret_cast<const float*>(t), reinterpret_cast<const float*>(labels)};
+    float* dst[3] = {ws + L.x, ws + L.t, ws + L.y};
+    const size_t cnt[3] = {nx, 2 * (size_t)B, labels ? 2 * (size_t)B : 0};
+    RC(tdx_copy_segments(src, dst, cnt, 3, st));
   }
 
   // The time / class MLP feeds only the skip branches (t_k is added where e_k is resized into the decoder's
@@ -867,8 +844,7 @@ static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const
         return tdx_conv3x3_fwd_infer_ex(in, wf, bias, Y, B, d.hw, d.hw, d.cin, d.cout, iss, iss + d.cout, ws + L.G1,
                                         2 * L.gbuf, stream, defer, pool);
       return tdx_conv3x3_fwd_splitk_fused(in, wf, bias, Y, B, d.hw, d.hw, d.cin, d.cout, TDX_CONV_OUT_BNRELU, iss,
-                                          iss + d.cout, ws + L.G1, 2 * L.gbuf, u->kcount, TDX_KCOUNT, stream, defer,
-                                          pool);
+                                          iss + d.cout, ws + L.G1, 2 * L.gbuf, stream, defer, pool);
     }
     const bool bn_on_load = d.in_bn && !u->materialize;
     if (d.in_bn && u->materialize) in = ws + L.A[i - 1];
@@ -1170,8 +1146,7 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
   auto ssh = [&](int i) { return ws + L.ss[i] + S.units[i].cout; };
   // the time / class path's backward on the third stream, in `parts` (internal.h)
   auto time_path_parts = [&](int parts) -> int {
-    return tdx_time_embed_bwd(u->kind, reinterpret_cast<const int64_t*>(ws + L.t),
-                              u->num_classes > 0 ? reinterpret_cast<const int64_t*>(ws + L.y) : nullptr,
+    return tdx_time_embed_bwd(u->kind, u->num_classes > 0 ? reinterpret_cast<const int64_t*>(ws + L.y) : nullptr,
                               P, G, ws + L.sin, ws + L.pre, ws + L.emb, ws + L.gtp[0], ws + L.gtp[1],
                               ws + L.gtp[2], ws + L.timescr, B, u->num_classes, u->side2, S.time_dim, parts);
   };
@@ -1202,13 +1177,11 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
     // arrive in the order time_proj1, 2, 3 = the summation order of tdx_time_embed_bwd): six of the
     // time path's small kernels leave the tail of the step.  The REST of that path stays after the last
     // stage (see time_path_bwd).
-    if (g_tdx_time_proj_early) {
-      RC(tdx_time_proj_bwd(u->kind, skip_k, P, G, ws + L.emb, ws + L.gtp[skip_k], ws + L.timescr, B, u->side2,
-                           S.time_dim));
-      // after the third projection g(emb) is complete: the middle of the time path follows at once (for kind 1
-      // that is all of it); only kind 0's first-layer kernel waits for the last stage (see time_path_bwd)
-      if (skip_k == 2 && g_tdx_time_stage != 6) RC(time_path_parts(TDX_TIME_MID));
-    }
+    RC(tdx_time_proj_bwd(u->kind, skip_k, P, G, ws + L.emb, ws + L.gtp[skip_k], ws + L.timescr, B, u->side2,
+                         S.time_dim));
+    // after the third projection g(emb) is complete: the middle of the time path follows at once (for kind 1
+    // that is all of it); only kind 0's first-layer kernel waits for the last stage (see time_path_bwd)
+    if (skip_k == 2) RC(time_path_parts(TDX_TIME_MID));
     find(gcat)->s2 = k;
     float* gup;
     RC(acquire(gcat, nullptr, &gup));
@@ -1223,21 +1196,13 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
     g_next = gup;
     return 0;
   };
-  // the time / class path only needs the three pixel sums, which the third stream produced itself
-  // (dec_level_bwd).  Default: after the last stage.  Knob time_stage=6 enqueues it right after the
-  // last decoder level, hidden under the encoder's backward (+0.8..1.3 % throughput).  Opt-in only:
-  // with the first version of time_l1_bwd_kernel (int64 t converted in the loop) that placement
-  // produced a wrong dW1 in some workgroups when the kernel ran beside the weight-gradient GEMMs
-  // (memory was right - a snapshot kernel on the same stream just before read t correctly - and any
-  // change to the kernel's code made it disappear).  The kernel now reads float(t)
-  // stored by the forward and tools/gpu_time_stage6_check.py passes, but the default stays put.
+  // what dec_level_bwd has not issued: kind 0's first-layer kernel, after the last stage, ordered on the third
+  // stream behind `st` (kind 1 has no separate first-layer part, its time path is complete after TDX_TIME_MID)
   auto time_path_bwd = [&](hipStream_t st) -> int {
     TDX_HIP(hipEventRecord(u->ev_fork, st));
     TDX_HIP(hipStreamWaitEvent(u->side2, u->ev_fork, 0));
-    // what dec_level_bwd has not issued already
-    const int parts = !g_tdx_time_proj_early ? 7 : g_tdx_time_stage == 6 ? (TDX_TIME_MID | TDX_TIME_L1) : TDX_TIME_L1;
-    if (parts == TDX_TIME_L1 && u->kind == 1) return 0;   // kind 1 has no separate first-layer part
-    return time_path_parts(parts);
+    if (u->kind == 1) return 0;
+    return time_path_parts(TDX_TIME_L1);
   };
   // first unit of an encoder level below the top, or the bottleneck (units 6, 4, 2): its input is a
   // pooled tensor; route the gradient through the max-pool and add the skip-path gradient
@@ -1291,10 +1256,7 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
       case 3: RC(plain_unit_bwd(10, ws + L.Y[9])); break;
       case 4: RC(dec_level_bwd(1)); break;
       case 5: RC(plain_unit_bwd(8, ws + L.Y[7])); break;
-      case 6:
-        RC(dec_level_bwd(0));
-        if (g_tdx_time_stage == 6) RC(time_path_bwd(st));
-        break;
+      case 6: RC(dec_level_bwd(0)); break;
       case 7: RC(pooled_unit_bwd(6, 2)); break;
       case 8: RC(plain_unit_bwd(5, ws + L.Y[4])); break;
       case 9: RC(pooled_unit_bwd(4, 1)); break;
@@ -1303,7 +1265,7 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
       case 12: RC(plain_unit_bwd(1, ws + L.Y[0])); break;
       case 13: RC(plain_unit_bwd(0, ws + L.x0)); break;  // g(x0)
       case 14:
-        if (g_tdx_time_stage != 6) RC(time_path_bwd(st));
+        RC(time_path_bwd(st));
         RC(tdx_initial_conv_wgrad(ws + L.x, g_next, ws + L.smallp, G[TDX_P_INIT_W], G[TDX_P_INIT_B], B, S.hw0,
                                   S.hw0, S.in_ch, S.x0_real, st, io16));
         if (u->g_x) {   // d loss / d x, on request only (tdx_unet_request_input_grad)
