@@ -748,8 +748,10 @@ extern "C" int tdx_conv3x3_fwd_wino(const float* in, const float* u, const float
 // behind the single barrier per stage that makes stage s+1 visible.  The DMA addressing is scalar: a wave's two tiles
 // of a stage are wave-uniform, so their base offsets ride in soffset and the validity of a piece's pixels in a 64-bit
 // lane mask built by the scalar unit; one v_cndmask per piece puts the out-of-range voffset on the lanes of invalid
-// pixels (zero padding: image borders, odd maps, the ragged end of the chunk).  The table the workgroup builds once in
-// LDS holds one word per tile: its first output pixel and the validity of its patch rows and columns.  Epilogue:
+// pixels (zero padding: image borders, odd maps, the ragged end of the chunk; soffset is outside the range check, so
+// this v_cndmask is the bounds protection).  The table the workgroup builds once in LDS holds one word per tile: its
+// first output pixel and the validity of its patch rows and columns.  The accumulators are never zeroed: a
+// workgroup's first stage is a second copy of the stage's code whose first tile-iteration takes the constant 0 as C.  Epilogue:
 // G^T . G mixes all four xi rows, held by two waves - each wave hands the rows of the OTHER channel parity to its
 // partner through LDS (the ring is free by then) and finalises its own.  Output: the direct kernel's slabs
 // [split][Cout][9][Cin], summed by the shared fixed-order reduction.
@@ -774,10 +776,14 @@ struct WinoWgArgs {
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // bit q of m (wave-uniform) -> lanes 16q .. 16q+15: the DMA lanes of pixel column q (patch) or output pixel q (dy)
+// (m < 16; s_bitreplicate doubles every bit of its 32-bit source: four of them widen a bit to sixteen lanes)
 __device__ __forceinline__ unsigned long long wg_lanes16(unsigned m) {
-  const unsigned lo = ((m & 1u) ? 0x0000ffffu : 0u) | ((m & 2u) ? 0xffff0000u : 0u);
-  const unsigned hi = ((m & 4u) ? 0x0000ffffu : 0u) | ((m & 8u) ? 0xffff0000u : 0u);
-  return (unsigned long long)hi << 32 | lo;
+  unsigned long long r;
+  asm("s_bitreplicate_b64_b32 %0, %1" : "=s"(r) : "s"(m));
+  asm("s_bitreplicate_b64_b32 %0, %1" : "=s"(r) : "s"((unsigned)r));
+  asm("s_bitreplicate_b64_b32 %0, %1" : "=s"(r) : "s"((unsigned)r));
+  asm("s_bitreplicate_b64_b32 %0, %1" : "=s"(r) : "s"((unsigned)r));
+  return r;
 }
 // per lane: mask bit of the lane ? x : y - one VALU, the mask read from an SGPR pair
 __device__ __forceinline__ unsigned wg_sel(unsigned long long mask, unsigned x, unsigned y) {
@@ -846,19 +852,23 @@ conv3x3_wgrad_wino_kernel(WinoWgArgs a) {
   // the wave-uniform DMA state of this wave's two tiles 2*wave, 2*wave+1 of a stage, from their table entries
   struct Pair { unsigned xb[2], rows[2], db[2]; unsigned long long cm[2], dm[2]; };
   // (patch pixel (0,0) of the tile is (W+1) pixels before its output pixel (0,0): the input descriptor's base)
+  // of table entry w (in an SGPR): the patch half (tile t's base offset, row validity, lane mask of its columns) ...
+  auto pair_x = [&](Pair& P, int t, unsigned w) {
+    P.xb[t] = (w >> 8) * cin4;
+    P.rows[t] = w & 15u;
+    P.cm[t] = wg_lanes16((w >> 4) & 15u);
+  };
+  // ... and the dy half
+  auto pair_dy = [&](Pair& P, int t, unsigned w) {
+    const unsigned r12 = (w >> 1) & 3u, c12 = (w >> 5) & 3u;   // output rows / columns 0, 1
+    P.db[t] = (w >> 8) * cout4;
+    P.dm[t] = wg_lanes16(((r12 & 1u) ? c12 : 0u) | ((r12 & 2u) ? c12 << 2 : 0u));   // output pixel q = 2 row + column
+  };
   auto pair_of = [&](uint2 e) {
     Pair P;
     const unsigned w[2] = {(unsigned)__builtin_amdgcn_readfirstlane(e.x), (unsigned)__builtin_amdgcn_readfirstlane(e.y)};
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const unsigned pix = w[t] >> 8, rows = w[t] & 15u, cols = (w[t] >> 4) & 15u;
-      const unsigned r12 = (rows >> 1) & 3u, c12 = (cols >> 1) & 3u;   // output rows / columns 0, 1
-      P.xb[t] = pix * cin4;
-      P.rows[t] = rows;
-      P.cm[t] = wg_lanes16(cols);
-      P.db[t] = pix * cout4;
-      P.dm[t] = wg_lanes16(((r12 & 1u) ? c12 : 0u) | ((r12 & 2u) ? c12 << 2 : 0u));   // output pixel q = 2 row + column
-    }
+    for (int t = 0; t < 2; ++t) { pair_x(P, t, w[t]); pair_dy(P, t, w[t]); }
     return P;
   };
   auto entries = [&](int s) {   // (past the end: a redundant copy of the last stage, never read)
@@ -886,11 +896,10 @@ conv3x3_wgrad_wino_kernel(WinoWgArgs a) {
   // d0 - d2, d1 + d2; rows 2/3 are d2 - d1, d1 - d3), so each has its own copy of the loop.
   auto body = [&](auto Hc) {
     constexpr int H = decltype(Hc)::value;
-    f32x16 acc[16];   // [c][xi - 2H][nu]: output channels 2 m + c (m the accumulator row)
-#pragma unroll
-    for (int p = 0; p < 16; ++p)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
+    // [c][xi - 2H][nu]: output channels 2 m + c (m the accumulator row).  Never zeroed: the first tile-iteration of the
+    // workgroup's first stage takes the constant 0 as C (the first stage is a second copy of the stage's code)
+    f32x16 acc[16];
+    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
     // operands of one tile for this lane: E'[c][xi - 2H][nu] (output channels 2 l31, 2 l31 + 1), V[xi - 2H][nu] (its
     // input channel)
@@ -946,9 +955,15 @@ conv3x3_wgrad_wino_kernel(WinoWgArgs a) {
     };
 
     // ---- main loop.  The raw values of tile j+2 are read at position 8 of tile-iteration j (the patch registers are free
-    // by then), eight MFMAs before their first use.  The one barrier per stage sits at the top of tile-iteration 2 (the
-    // reads of that iteration are the first into stage s+1), and stage s+2 is requested behind it, in tile-iterations 2
-    // and 3, with its table entries read once.
+    // by then), nine MFMAs before their first use: the 28 adds that prepare the next tile stand together behind MFMA 1
+    // (per stage, profiles/r11_wino_phases_wgrad_ablation.txt: 2.20 us with four behind every second MFMA, 2.16 with
+    // eight behind every fourth, 2.14 with 16 + 12, 2.13 with all 28 in one gap; over MFMAs 0-7 with the raw reads at
+    // position 11: 2.23).  The one barrier per stage sits at the top of tile-iteration 2 (the reads of that iteration
+    // are the first into stage s+1), and stage s+2 is requested behind it, in tile-iterations 2 and 3.  Its two table
+    // entries are read with the raw values of tile-iteration 0 (the table never changes) and turned into the scalar DMA
+    // state in the even gaps of tile-iteration 1, a part per gap: a wave is alone on its SIMD, so a run of scalar
+    // instructions that outlasts one MFMA leaves the matrix pipe idle - built in one piece behind the barrier, the
+    // ~80 instructions of the state cost 0.17 us per stage.
     {
       const Pair P0 = pair_of(entries(0));
 #pragma unroll
@@ -965,12 +980,14 @@ conv3x3_wgrad_wino_kernel(WinoWgArgs a) {
     if (a.stamps) { t_first = __builtin_amdgcn_s_memrealtime(); c_loop = __builtin_amdgcn_s_memtime(); }
     unsigned rx0 = rx_lane, re0 = re_lane;   // the addresses in the buffers of stages s and s+1 (rx1, re1)
     int b0 = 0;   // buffer of stage s
-    for (int s = 0; s < ns; ++s) {
+    auto stage = [&](auto first_c, int s) {
+      constexpr bool FIRST = decltype(first_c)::value;
       int b1 = b0 + 1; b1 = b1 == WNST ? 0 : b1;
       int b2 = b1 + 1; b2 = b2 == WNST ? 0 : b2;
       unsigned rx1 = rx_lane + (unsigned)(b1 * WST_F * 4), re1 = re_lane + (unsigned)(b1 * WST_F * 4);
       asm volatile("" : "+v"(rx1), "+v"(re1));
       uint2 e2 = {0u, 0u};
+      unsigned w0 = 0, w1 = 0;
       Pair P;
       auto tile_iter = [&](auto Jc) {
         constexpr int J = decltype(Jc)::value;
@@ -978,19 +995,27 @@ conv3x3_wgrad_wino_kernel(WinoWgArgs a) {
           // stage s+1 has landed (requested a stage ago) and every wave has finished reading stage s-1, whose buffer the
           // requests of stage s+2 overwrite
           asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-          e2 = entries(s + 2);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int p = 0; p < 16; ++p) {   // MFMA p: output channels 2 m + (p >> 3), position 2H + (p >> 2 & 1), nu = p & 3
-          acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ec[p], Vc[p & 7], acc[p], 0, 0, 0);
-          if (p & 1) {   // four of the 28 adds behind every second MFMA
+          if (FIRST && J == 0) acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ec[p], Vc[p & 7], zero16, 0, 0, 0);
+          else acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ec[p], Vc[p & 7], acc[p], 0, 0, 0);
+          if (p == 1) {   // all 28 adds in ONE gap: every group of adds between two MFMAs costs the matrix pipe a restart
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-              if ((p >> 1) * 4 + k < 28) xop((p >> 1) * 4 + k, Vn, En);
+            for (int k = 0; k < 28; ++k) xop(k, Vn, En);
           }
-          if (p == 8) read_raw(J < 2 ? rx0 : rx1, J < 2 ? re0 : re1, (J + 2) & 3, ern);   // raw values of tile J + 2
-          if (J == 2 && p == 1) P = pair_of(e2);
+          if (p == 8) {
+            read_raw(J < 2 ? rx0 : rx1, J < 2 ? re0 : re1, (J + 2) & 3, ern);   // raw values of tile J + 2
+            if (J == 0) e2 = entries(s + 2);
+          }
+          if (J == 1) {
+            if (p == 0) { w0 = (unsigned)__builtin_amdgcn_readfirstlane(e2.x); w1 = (unsigned)__builtin_amdgcn_readfirstlane(e2.y); }
+            if (p == 2) pair_x(P, 0, w0);
+            if (p == 4) pair_x(P, 1, w1);
+            if (p == 6) pair_dy(P, 0, w0);
+            if (p == 10) pair_dy(P, 1, w1);
+          }
           if ((J == 2 || J == 3) && p % 3 == 1 && p / 3 < 5) issue_piece(J == 2 ? p / 3 : 5 + p / 3, P, b2);
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -1004,7 +1029,9 @@ conv3x3_wgrad_wino_kernel(WinoWgArgs a) {
       tile_iter(std::integral_constant<int, 2>{});
       tile_iter(std::integral_constant<int, 3>{});
       b0 = b1; rx0 = rx1; re0 = re1;
-    }
+    };
+    stage(std::true_type{}, 0);
+    for (int s = 1; s < ns; ++s) stage(std::false_type{}, s);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the ring is free
 
     if (a.stamps) { t_loop = __builtin_amdgcn_s_memrealtime(); c_loop = __builtin_amdgcn_s_memtime() - c_loop; }
