@@ -161,6 +161,28 @@ int tdx_adam_step_clip(float* param, const float* grad, float* exp_avg, float* e
                        float grad_scale, float max_norm, const float* hyper_dev, void* scratch,
                        tdx_stream_t stream);
 
+/* Adam with an exponential moving average of the parameters fused into the same pass (36 B/param): the
+ * three updates above, bit-identical in param / exp_avg / exp_avg_sq, and for the same element
+ *   ema = ema + ema_one_minus_decay * (param_new - ema)
+ * as three separately rounded fp32 operations (torch's e + a * (p - e)).  ema_one_minus_decay = 1 - decay in
+ * [0, 1]; in the device-scalar forms it is hyper4[3], after the three floats of tdx_adam_step_dev (the clip
+ * form with hyper4_dev then ignores lr / step / grad_scale / ema_one_minus_decay).  ema must not overlap
+ * param.  No alignment requirement beyond fp32's; no allocation, no synchronisation, graph-capturable. */
+int tdx_adam_ema_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
+                      int64_t n, float lr, float beta1, float beta2, float eps, int step, float grad_scale,
+                      float ema_one_minus_decay, tdx_stream_t stream);
+int tdx_adam_ema_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
+                          int64_t n, const float* hyper4, float beta1, float beta2, float eps, tdx_stream_t stream);
+int tdx_adam_ema_step_clip(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
+                           int64_t n, float lr, float beta1, float beta2, float eps, int step, float grad_scale,
+                           float max_norm, float ema_one_minus_decay, const float* hyper4_dev, void* scratch,
+                           tdx_stream_t stream);
+
+/* Exchange the contents of two fp32 buffers of n elements in place (16 B/element; the ranges must not
+ * overlap): how TrainStep.ema_weights() puts the averaged weights where every plan and captured graph
+ * already points. */
+int tdx_swap_f32(float* a, float* b, int64_t n, tdx_stream_t stream);
+
 /* ---- building blocks (exported for unit tests and re-use) --------------- */
 
 /* OIHW (Cout,Cin,3,3) -> forward pack [Cout][9][Cin] and dgrad pack

@@ -68,6 +68,11 @@ _SIGS = {
     "tdx_adam_clip_scratch_bytes": (C.c_size_t, []),
     "tdx_adam_step_clip": (C.c_int, [_ptr, _ptr, _ptr, _ptr, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                      C.c_int, C.c_float, C.c_float, _ptr, _ptr, _ptr]),
+    "tdx_adam_ema_step": (C.c_int, [_ptr] * 5 + [C.c_int64] + [C.c_float] * 4 + [C.c_int, C.c_float, C.c_float, _ptr]),
+    "tdx_adam_ema_step_dev": (C.c_int, [_ptr] * 5 + [C.c_int64, _ptr, C.c_float, C.c_float, C.c_float, _ptr]),
+    "tdx_adam_ema_step_clip": (C.c_int, [_ptr] * 5 + [C.c_int64] + [C.c_float] * 4 + [C.c_int] + [C.c_float] * 3
+                               + [_ptr, _ptr, _ptr]),
+    "tdx_swap_f32": (C.c_int, [_ptr, _ptr, C.c_int64, _ptr]),
     "tdx_edge_conv_wgrad_scratch_floats": (C.c_size_t, [C.c_int] * 3),
     "tdx_initial_conv_forward": (C.c_int, [_ptr, _ptr, _ptr, _ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ptr]),
     "tdx_initial_conv_backward": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

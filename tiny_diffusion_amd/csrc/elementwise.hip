@@ -593,6 +593,141 @@ extern "C" int tdx_adam_step_clip(float* param, const float* grad, float* exp_av
   return 0;
 }
 
+// ------------------------------------------- Adam with a fused EMA of the parameters
+// The Adam update of the kernels above and, for the same element, the exponential moving average
+//     e = e + a * (p_new - e) ,  a = 1 - decay
+// of the parameter value just computed (Ho et al. 2020 sample from it): the average costs its own read and
+// write, 8 B/param on top of Adam's 28, where a pass of its own would read p again (12 B/param) and launch.
+// adam_elem holds the expressions of adam_kernel in the same order, so p, m and v come out bit-identical
+// to the entries without the average; the average is three separately rounded fp32 operations, like
+// torch's e + a * (p - e) on tensors.
+__device__ __forceinline__ float adam_elem(float p, float g, float& m, float& v, float gs, float lr_bc1, float b1,
+                                           float b2, float eps, float inv_sqrt_bc2) {
+  float gi = g * gs;
+  float mi = m * b1 + (1.0f - b1) * gi;
+  float vi = v * b2 + (1.0f - b2) * gi * gi;
+  m = mi;
+  v = vi;
+  float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
+  return p - lr_bc1 * (mi / denom);
+}
+
+__device__ __forceinline__ float ema_elem(float e, float p, float a) {
+  return __fadd_rn(e, __fmul_rn(a, __fsub_rn(p, e)));
+}
+
+static bool overlap(const float* a, const float* b, int64_t n) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, len = (uintptr_t)n * sizeof(float);
+  return x < y + len && y < x + len;
+}
+
+// Five streams of 4 B per element, one float per lane like adam_kernel: a float4 body for 16-byte aligned buffers was
+// measured and not kept (0.6 - 1.7 % faster in isolation, inside the spread in one of two runs).
+// DEV_HYPER: the scalars come from hyper = {lr/bc1, 1/sqrt(bc2), grad_scale, a}.  CLIP: clip_grad_norm_ from
+// grad_sumsq_kernel's partials, re-added in adam_clip_kernel's order.
+template <bool DEV_HYPER, bool CLIP>
+__global__ void __launch_bounds__(256)
+adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                float* __restrict__ v, float* __restrict__ e, int64_t n, float lr_bc1, float b1, float b2,
+                float eps, float inv_sqrt_bc2, float gs, float a, const float* __restrict__ hyper,
+                const double* __restrict__ partials, float max_norm) {
+  if (DEV_HYPER) { lr_bc1 = hyper[0]; inv_sqrt_bc2 = hyper[1]; gs = hyper[2]; a = hyper[3]; }
+  float ge = gs;
+  if (CLIP) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (int k = threadIdx.x; k < CLIP_BLOCKS; k += 256) s += partials[k];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int half = 128; half > 0; half >>= 1) {
+      if ((int)threadIdx.x < half) red[threadIdx.x] += red[threadIdx.x + half];
+      __syncthreads();
+    }
+    const float total_norm = (float)sqrt(red[0]) * fabsf(gs);
+    const float clip = fminf(1.0f, max_norm / (total_norm + 1e-6f));
+    ge = gs * clip;
+  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    float mi = m[i], vi = v[i];
+    const float pi = adam_elem(p[i], g[i], mi, vi, ge, lr_bc1, b1, b2, eps, inv_sqrt_bc2);
+    m[i] = mi;
+    v[i] = vi;
+    p[i] = pi;
+    e[i] = ema_elem(e[i], pi, a);
+  }
+}
+
+static bool ema_args_ok(const float* param, const float* grad, const float* exp_avg, const float* exp_avg_sq,
+                        const float* ema, int64_t n) {
+  return param && grad && exp_avg && exp_avg_sq && ema && n > 0 && !overlap(param, ema, n);
+}
+
+extern "C" int tdx_adam_ema_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
+                                 int64_t n, float lr, float beta1, float beta2, float eps, int step,
+                                 float grad_scale, float ema_one_minus_decay, tdx_stream_t stream) {
+  if (!ema_args_ok(param, grad, exp_avg, exp_avg_sq, ema, n) || step <= 0) return TDX_E_BADARG;
+  if (!(ema_one_minus_decay >= 0.f && ema_one_minus_decay <= 1.f)) return TDX_E_BADARG;
+  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+  adam_ema_kernel<false, false><<<ew_grid(n, 256), 256, 0, to_stream(stream)>>>(
+      param, grad, exp_avg, exp_avg_sq, ema, n, (float)(lr / bc1), beta1, beta2, eps, (float)(1.0 / sqrt(bc2)),
+      grad_scale, ema_one_minus_decay, nullptr, nullptr, 0.f);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tdx_adam_ema_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
+                                     int64_t n, const float* hyper4, float beta1, float beta2, float eps,
+                                     tdx_stream_t stream) {
+  if (!ema_args_ok(param, grad, exp_avg, exp_avg_sq, ema, n) || !hyper4) return TDX_E_BADARG;
+  adam_ema_kernel<true, false><<<ew_grid(n, 256), 256, 0, to_stream(stream)>>>(
+      param, grad, exp_avg, exp_avg_sq, ema, n, 0.f, beta1, beta2, eps, 0.f, 0.f, 0.f, hyper4, nullptr, 0.f);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tdx_adam_ema_step_clip(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
+                                      int64_t n, float lr, float beta1, float beta2, float eps, int step,
+                                      float grad_scale, float max_norm, float ema_one_minus_decay,
+                                      const float* hyper4_dev, void* scratch, tdx_stream_t stream) {
+  if (!ema_args_ok(param, grad, exp_avg, exp_avg_sq, ema, n) || !scratch || !(max_norm > 0.f)) return TDX_E_BADARG;
+  if (!hyper4_dev && (step <= 0 || !(ema_one_minus_decay >= 0.f && ema_one_minus_decay <= 1.f))) return TDX_E_BADARG;
+  hipStream_t st = to_stream(stream);
+  double* partials = static_cast<double*>(scratch);
+  grad_sumsq_kernel<<<CLIP_BLOCKS, 256, 0, st>>>(grad, n, partials);
+  TDX_CHECK_LAUNCH();
+  const int grid = ew_grid(n, 256);
+  if (hyper4_dev) {
+    adam_ema_kernel<true, true><<<grid, 256, 0, st>>>(param, grad, exp_avg, exp_avg_sq, ema, n, 0.f, beta1, beta2,
+                                                      eps, 0.f, 0.f, 0.f, hyper4_dev, partials, max_norm);
+  } else {
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    adam_ema_kernel<false, true><<<grid, 256, 0, st>>>(param, grad, exp_avg, exp_avg_sq, ema, n, (float)(lr / bc1),
+                                                       beta1, beta2, eps, (float)(1.0 / sqrt(bc2)), grad_scale,
+                                                       ema_one_minus_decay, nullptr, partials, max_norm);
+  }
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+// Exchange the contents of two buffers (TrainStep.ema_weights: the parameters and their average trade
+// places, no pointer changes).  Each lane reads both values and writes both: exact, order-free.
+__global__ void __launch_bounds__(256) swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const float x = a[i], y = b[i];
+    a[i] = y;
+    b[i] = x;
+  }
+}
+
+extern "C" int tdx_swap_f32(float* a, float* b, int64_t n, tdx_stream_t stream) {
+  if (!a || !b || n <= 0 || overlap(a, b, n)) return TDX_E_BADARG;
+  swap_f32_kernel<<<ew_grid(n, 256), 256, 0, to_stream(stream)>>>(a, b, n);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
 // -------------------------------------------------------------------- probes
 // fp32 MFMA peak: 4 independent 32x32x2 accumulator chains per wave, 4 waves per block.
 __global__ void __launch_bounds__(256) probe_mfma_kernel(float* out, int iters, unsigned long long* stamps) {

@@ -19,6 +19,7 @@ statistics stay rank-local (DistributedDataParallel semantics).
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import List, Optional, Tuple
@@ -100,14 +101,34 @@ def cosine_annealing_lr(step: int, base_lr: float, T_max: int, eta_min: float = 
     return eta_min + (base_lr - eta_min) * (1.0 + math.cos(math.pi * step / T_max)) / 2.0
 
 
+def ema_decay_at(step_index: int, decay: float, warmup: bool) -> float:
+    """Decay of the parameter average at optimizer step ``step_index`` (0 at the first one): ``decay``, or with
+    ``warmup`` ``min(decay, (1 + k) / (10 + k))`` - the average follows the parameters closely while they still move
+    fast (0.1 at the first step, 2/11 at the second) and reaches ``decay`` from the first k with
+    ``(1 + k) / (10 + k) >= decay`` on."""
+    if not warmup:
+        return decay
+    k = int(step_index)
+    return min(decay, (1 + k) / (10 + k))
+
+
 class TrainStep:
     def __init__(self, model: NoiseModelBase, diffusion: ForwardProcess, lr: float = 1e-3,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  process_group=None, bucket_floats: int = 1 << 20, philox_seed: Optional[int] = None,
                  max_grad_norm: Optional[float] = None, cosine_T_max: Optional[int] = None,
                  cosine_eta_min: float = 0.0, use_graph: bool = False, data_parallel: bool = True,
-                 sync_bn: bool = False, cond_drop_prob: float = 0.0, cond_drop_seed: int = 0):
-        """``cond_drop_prob`` (classifier-free guidance, Ho & Salimans 2021): each sample of a step loses its condition
+                 sync_bn: bool = False, cond_drop_prob: float = 0.0, cond_drop_seed: int = 0,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
+        """``ema_decay`` (Ho et al. 2020 sample from an exponential moving average of the parameters): a number in
+        [0, 1] keeps ``self.ema``, a flat fp32 buffer beside ``flat_param`` that starts as a copy of the parameters and
+        that the optimizer kernel updates in the same pass, ``e += (1 - decay_k) * (p_new - e)`` with ``decay_k =
+        ema_decay_at(k, ema_decay, ema_warmup)`` (``tdx_adam_ema_step*``: 8 B/parameter on top of Adam's 28).
+        ``ema_weights()`` swaps the average into the model for sampling, ``ema_state_dict()`` exports it.  BatchNorm
+        running statistics are averages already and are shared with the live model
+        (``torch.optim.swa_utils.AveragedModel(use_buffers=False)``).  ``None`` allocates and launches nothing new.
+
+        ``cond_drop_prob`` (classifier-free guidance, Ho & Salimans 2021): each sample of a step loses its condition
         with this probability - its label becomes -1, its text embedding a zero row - which trains the unconditional
         branch that ``sample(guidance_scale=...)`` combines with the conditional one.  The mask is a Philox draw keyed by
         ``(cond_drop_seed, step * world + rank, sample)`` (``tdx_cond_drop_*``; give it a seed other than
@@ -122,6 +143,15 @@ class TrainStep:
         result does not depend on which rank saves (DDP's ``broadcast_buffers=True`` has that
         effect at every forward)."""
         self.model = model
+        if ema_decay is None:
+            if ema_warmup:
+                raise ValueError("ema_warmup=True needs an ema_decay")
+        elif isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 <= ema_decay <= 1.0:
+            raise ValueError("ema_decay must be None or a number in [0, 1]")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema = None          # flat average of flat_param (_flatten)
+        self._ema_swapped = False   # inside ema_weights(): flat_param holds the average, ema the parameters
         if isinstance(cond_drop_prob, bool) or not isinstance(cond_drop_prob, (int, float)) \
                 or not 0.0 <= cond_drop_prob <= 1.0:
             raise ValueError("cond_drop_prob must be in [0, 1]")
@@ -163,7 +193,8 @@ class TrainStep:
         # use_graph: capture the whole step (randint, q_sample, forward, loss, backward, clip, Adam)
         # into one HIP graph and replay it.  Single rank, noise and t drawn by torch inside the
         # graph; step-dependent scalars (lr, Adam bias corrections) live in a 3-float device tensor
-        # refreshed before each replay.  Measured on MI355X it buys little: the small-batch steps
+        # refreshed before each replay (4 floats with ema_decay: 1 - decay of the step, so a warm-up
+        # decay does not freeze at its capture-time value).  Measured on MI355X it buys little: the small-batch steps
         # are bound by the GPU-side cost of ~100-170 tiny dependent kernels, not by host launches
         # (LAION B=8: 2.18 -> 2.05 ms/step; latent MLP B=128: 0.62 -> 0.68), so it is off by default.
         self.use_graph = use_graph
@@ -203,6 +234,8 @@ class TrainStep:
         self.flat_grad, self.grad_views = m._grad_buffers(dev)
         self.exp_avg = torch.zeros_like(flat)
         self.exp_avg_sq = torch.zeros_like(flat)
+        if self.ema_decay is not None:
+            self.ema = flat.clone()
         self.n_stages = lib.tdx_unet_backward_stages()
 
     # ------------------------------------------------------------------- step
@@ -214,6 +247,8 @@ class TrainStep:
         m, fp = self.model, self.diffusion
         B = x_0.shape[0]
         dev = x_0.device
+        if self._ema_swapped:
+            raise RuntimeError("step() inside ema_weights(): the model holds the averaged weights")
         if (self.use_graph and t is None and noise is None and self.philox_seed is None and self.world == 1
                 and not self.reducer.force):
             return self._graph_step(x_0, y)
@@ -243,7 +278,13 @@ class TrainStep:
     def _adam_hyper(self, gscale: float):
         bc1 = 1.0 - self.betas[0] ** self.step_count
         bc2 = 1.0 - self.betas[1] ** self.step_count
-        return [self.lr / bc1, 1.0 / math.sqrt(bc2), gscale]
+        hyper = [self.lr / bc1, 1.0 / math.sqrt(bc2), gscale]
+        return hyper if self.ema is None else hyper + [self._ema_a()]
+
+    def _ema_a(self) -> float:
+        """1 - decay of the optimizer step that ``step_count`` (already incremented) counts, in double: the
+        conversion to the kernel's fp32 scalar is its one rounding."""
+        return 1.0 - ema_decay_at(self.step_count - 1, self.ema_decay, self.ema_warmup)
 
     def _graph_step(self, x_0, y):
         m = self.model
@@ -260,7 +301,7 @@ class TrainStep:
                 return self._eager_step(x_0, self._drop_cond(y), None, None)
             self._gx0 = x_0.detach().clone().contiguous().float()
             self._gy = None if y is None else y.detach().clone().contiguous()
-            self._hyper = torch.zeros(3, dtype=torch.float32, device=dev)
+            self._hyper = torch.zeros(3 if self.ema is None else 4, dtype=torch.float32, device=dev)
             # (a plan whose finalizer runs inside the capture is parked, not destroyed: unet._Plan.__del__)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
@@ -357,32 +398,43 @@ class TrainStep:
             cur.wait_stream(self.comm)
         gscale = self.reducer.finish()
         self.step_count += 1
+        bufs = (self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr())
+        n = self.flat_param.numel()
         if self.max_grad_norm is not None:
             # clip_grad_norm_ fused into the optimizer pass (conditional_diffusion_laion.py:469-472): the
             # flat buffer holds every gradient, so one sum of squares gives the total norm, and the
             # Adam kernel applies the clip coefficient on the fly
             if self._clip_scratch is None:
                 self._clip_scratch = torch.empty(lib.tdx_adam_clip_scratch_bytes(), dtype=torch.uint8, device=dev)
-            check(lib.tdx_adam_step_clip(self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
-                                         self.exp_avg_sq.data_ptr(), self.flat_param.numel(), self.lr, self.betas[0],
-                                         self.betas[1], self.eps, self.step_count, gscale, float(self.max_grad_norm),
-                                         None if hyper is None else hyper.data_ptr(), self._clip_scratch.data_ptr(),
-                                         st), "tdx_adam_step_clip")
+            hyp = None if hyper is None else hyper.data_ptr()
+            if self.ema is not None:
+                check(lib.tdx_adam_ema_step_clip(*bufs, self.ema.data_ptr(), n, self.lr, self.betas[0], self.betas[1],
+                                                 self.eps, self.step_count, gscale, float(self.max_grad_norm),
+                                                 self._ema_a(), hyp, self._clip_scratch.data_ptr(), st),
+                      "tdx_adam_ema_step_clip")
+            else:
+                check(lib.tdx_adam_step_clip(*bufs, n, self.lr, self.betas[0], self.betas[1], self.eps, self.step_count,
+                                             gscale, float(self.max_grad_norm), hyp, self._clip_scratch.data_ptr(), st),
+                      "tdx_adam_step_clip")
             m._buf_epoch += 1
             if hyper is None and self.cosine_T_max is not None:
                 self.lr = cosine_annealing_lr(self.step_count, self.base_lr, self.cosine_T_max, self.cosine_eta_min)
             return self.loss
         if hyper is not None:  # being captured: scalars come from device memory at replay time
-            check(lib.tdx_adam_step_dev(self.flat_param.data_ptr(), self.flat_grad.data_ptr(),
-                                        self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.flat_param.numel(),
-                                        hyper.data_ptr(), self.betas[0], self.betas[1], self.eps, st),
-                  "tdx_adam_step_dev")
+            if self.ema is not None:
+                check(lib.tdx_adam_ema_step_dev(*bufs, self.ema.data_ptr(), n, hyper.data_ptr(), self.betas[0],
+                                                self.betas[1], self.eps, st), "tdx_adam_ema_step_dev")
+            else:
+                check(lib.tdx_adam_step_dev(*bufs, n, hyper.data_ptr(), self.betas[0], self.betas[1], self.eps, st),
+                      "tdx_adam_step_dev")
             m._buf_epoch += 1
             return self.loss
-        check(lib.tdx_adam_step(self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
-                                self.exp_avg_sq.data_ptr(), self.flat_param.numel(), self.lr, self.betas[0],
-                                self.betas[1], self.eps, self.step_count, gscale, st),
-              "tdx_adam_step")                                                 # diffusion.py:236
+        if self.ema is not None:
+            check(lib.tdx_adam_ema_step(*bufs, self.ema.data_ptr(), n, self.lr, self.betas[0], self.betas[1], self.eps,
+                                        self.step_count, gscale, self._ema_a(), st), "tdx_adam_ema_step")
+        else:
+            check(lib.tdx_adam_step(*bufs, n, self.lr, self.betas[0], self.betas[1], self.eps, self.step_count, gscale,
+                                    st), "tdx_adam_step")                      # diffusion.py:236
         # the kernel wrote the parameters through raw pointers (no torch version bump): packed
         # inference weights of every plan are stale now, whatever mode this step ran in
         m._buf_epoch += 1
@@ -401,5 +453,66 @@ class TrainStep:
         """Identical replicas at start (parameters and BN buffers)."""
         if self.world > 1:
             torch.distributed.broadcast(self.flat_param, src, group=self.pg)
+            if self.ema is not None:
+                torch.distributed.broadcast(self.ema, src, group=self.pg)
             for b in self.model.buffers():
                 torch.distributed.broadcast(b, src, group=self.pg)
+
+    # -------------------------------------------------------------------- EMA
+    def _need_ema(self, what: str):
+        if self.ema is None:
+            raise RuntimeError(f"{what} needs TrainStep(ema_decay=...)")
+        if self._ema_swapped:
+            raise RuntimeError(f"{what} inside ema_weights(): the average and the parameters have traded places")
+
+    def reset_ema(self):
+        """The average starts again from the current parameters (after loading a checkpoint into the model of a
+        step that already exists)."""
+        self._need_ema("reset_ema()")
+        self.ema.copy_(self.flat_param)
+
+    def ema_state_dict(self):
+        """The model's ``state_dict()`` with the averaged parameters: the same keys, clones of the slices of ``self.ema``
+        for the parameters and clones of the live BatchNorm buffers (running statistics are averages already, and
+        shared).  Loads into the reference's modules unchanged."""
+        self._need_ema("ema_state_dict()")
+        out = type(self.model.state_dict())()
+        for k, v in self.model.state_dict().items():
+            if k in self.offsets:
+                lo, hi = self.offsets[k]
+                out[k] = self.ema[lo:hi].view(v.shape).clone()
+            else:
+                out[k] = v.detach().clone()
+        return out
+
+    def load_ema_state_dict(self, sd):
+        """Inverse of ``ema_state_dict()`` for the parameter entries (buffers belong to the model)."""
+        self._need_ema("load_ema_state_dict()")
+        for k, (lo, hi) in self.offsets.items():
+            v = sd[k]
+            if v.numel() != hi - lo:
+                raise ValueError(f"{k}: {tuple(v.shape)} does not fit the parameter's {hi - lo} elements")
+        for k, (lo, hi) in self.offsets.items():
+            self.ema[lo:hi].copy_(sd[k].detach().reshape(-1))
+
+    def _swap_ema(self):
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        check(lib.tdx_swap_f32(self.flat_param.data_ptr(), self.ema.data_ptr(), self.flat_param.numel(), st),
+              "tdx_swap_f32")
+        # the launch went in: from here on the two buffers hold each other's contents.  Written through raw pointers,
+        # so the packed inference weights of every plan are stale
+        self._ema_swapped = not self._ema_swapped
+        self.model._buf_epoch += 1
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the module IS the averaged model: one ``tdx_swap_f32`` launch exchanges the contents of
+        ``flat_param`` and ``ema`` on entry and again on exit (also when the body raises), so ``forward``, ``sample``,
+        ``ddim_sample``, guidance and ``state_dict()`` see the averaged weights, and no pointer that a plan or a
+        captured step holds changes.  ``step()`` and a nested ``ema_weights()`` raise inside."""
+        self._need_ema("ema_weights()")
+        self._swap_ema()     # flips _ema_swapped once its launch is in; nothing may come between it and the try
+        try:
+            yield self.model
+        finally:
+            self._swap_ema()
