@@ -64,6 +64,19 @@ int tdx_q_sample_philox(const float* x0, const int64_t* t, const float* sqrt_ac,
                         int batch, int per_sample, uint64_t seed, uint64_t offset,
                         tdx_stream_t stream);
 
+/* q_sample that also writes the training target of a parameterisation (an addition: the reference trains on
+ * eps only).  x_t as tdx_q_sample, bit for bit.  kind 0 (eps): target = noise.  kind 1 (v, Salimans & Ho 2022):
+ * target = sqrt_ac[t]*noise - sqrt_1mac[t]*x0, both products and the subtraction rounded separately.  target may be
+ * the noise buffer.  Another kind: TDX_E_BADARG; per_sample % 4: TDX_E_SHAPE. */
+int tdx_q_sample_target(const float* x0, const float* noise, const int64_t* t, const float* sqrt_ac,
+                        const float* sqrt_1mac, float* x_t, float* target, int batch, int per_sample, int kind,
+                        tdx_stream_t stream);
+/* ... with the in-kernel noise of tdx_q_sample_philox (same stream and indexing: x_t equals that entry's for the
+ * same seed and offset).  Writes x_t and target only: 12 B/element. */
+int tdx_q_sample_target_philox(const float* x0, const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac,
+                               float* x_t, float* target, int batch, int per_sample, int kind, uint64_t seed,
+                               uint64_t offset, tdx_stream_t stream);
+
 /* One reverse step, diffusion.py:272-274:
  *   x_out = c1*(x - c2*eps) + sigma*z        (z == NULL or t == 0: z = 0, diffusion.py:267-270)
  * coef: device table (T,3) of (c1,c2,sigma) = (1/sqrt(alpha), (1-alpha)/sqrt(1-acp), sqrt(beta));
@@ -135,6 +148,14 @@ int tdx_mse_loss(const float* a, const float* b, float* loss_out, float* d_a,
 size_t tdx_mse_scratch_bytes(void);
 int tdx_mse_loss_grad(const float* a, const float* b, float* loss_out, float* d_a, float gscale,
                       int64_t n, void* scratch, tdx_stream_t stream);
+/* ... with a loss weight per timestep (min-SNR weighting, Hang et al. 2023), n = batch*per_sample, sample s of
+ * the batch at timestep t[s]:  loss = sum_s w_table[t[s]] sum_j (a-b)^2 / n,  d_a = (a-b) * k_s with
+ * k_s = fl(fl(2*gscale/n) * w_table[t[s]]).  Same passes, scratch and summation order as tdx_mse_loss_grad: a table of
+ * ones reproduces its loss and gradient bit for bit.  d_a may be NULL.  t is not range-checked (as in tdx_q_sample):
+ * w_table, like sqrt_ac / sqrt_1mac, must hold at least max(t) + 1 entries and every t[s] must be >= 0. */
+int tdx_mse_loss_grad_weighted(const float* a, const float* b, const int64_t* t, const float* w_table,
+                               float* loss_out, float* d_a, float gscale, int batch, int per_sample, void* scratch,
+                               tdx_stream_t stream);
 
 /* Adam, torch defaults (diffusion.py:211/236): one fused pass over a flat
  * parameter buffer, 28 B/param.  step is the 1-based step count. */

@@ -81,6 +81,82 @@ extern "C" int tdx_q_sample_philox(const float* x0, const int64_t* t, const floa
   return 0;
 }
 
+// q_sample that also writes the training target of the chosen parameterisation (TrainStep(prediction=...)):
+// kind 0 (eps): target = noise; kind 1 (v, Salimans & Ho 2022): target = a*noise - b*x0, the two products and the
+// subtraction rounded separately like x_t.  x_t is the expression of q_sample_kernel, element for element.
+// noise / target carry no __restrict__: target may be the noise buffer (each lane reads its element before it writes
+// it).  target == null (kind 0 in place): nothing to write.
+#define TDX_TARGET_EPS 0
+#define TDX_TARGET_V 1
+
+__device__ __forceinline__ float4 q_mix(float a, float b, const float4 x, const float4 e) {
+  float4 o;
+  o.x = __fadd_rn(__fmul_rn(a, x.x), __fmul_rn(b, e.x));
+  o.y = __fadd_rn(__fmul_rn(a, x.y), __fmul_rn(b, e.y));
+  o.z = __fadd_rn(__fmul_rn(a, x.z), __fmul_rn(b, e.z));
+  o.w = __fadd_rn(__fmul_rn(a, x.w), __fmul_rn(b, e.w));
+  return o;
+}
+
+__device__ __forceinline__ float4 v_target(float a, float b, const float4 x, const float4 e) {
+  float4 o;
+  o.x = __fsub_rn(__fmul_rn(a, e.x), __fmul_rn(b, x.x));
+  o.y = __fsub_rn(__fmul_rn(a, e.y), __fmul_rn(b, x.y));
+  o.z = __fsub_rn(__fmul_rn(a, e.z), __fmul_rn(b, x.z));
+  o.w = __fsub_rn(__fmul_rn(a, e.w), __fmul_rn(b, x.w));
+  return o;
+}
+
+template <bool PHILOX>
+__global__ void __launch_bounds__(256)
+q_sample_target_kernel(const float4* __restrict__ x0, const float4* noise, const int64_t* __restrict__ t,
+                       const float* __restrict__ sqrt_ac, const float* __restrict__ sqrt_1mac,
+                       float4* __restrict__ x_t, float4* target, int64_t n4, int per_sample4, int kind,
+                       uint64_t seed, uint64_t offset) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int s = (int)(i / per_sample4);
+    int64_t ts = t[s];
+    float a = sqrt_ac[ts], b = sqrt_1mac[ts];
+    const float4 e = PHILOX ? philox_normal4((uint64_t)i, offset, seed) : noise[i];
+    const float4 x = x0[i];
+    x_t[i] = q_mix(a, b, x, e);
+    if (target) target[i] = kind == TDX_TARGET_V ? v_target(a, b, x, e) : e;
+  }
+}
+
+extern "C" int tdx_q_sample_target(const float* x0, const float* noise, const int64_t* t, const float* sqrt_ac,
+                                   const float* sqrt_1mac, float* x_t, float* target, int batch, int per_sample,
+                                   int kind, tdx_stream_t stream) {
+  if (!x0 || !noise || !t || !sqrt_ac || !sqrt_1mac || !x_t || !target || batch <= 0 || per_sample <= 0)
+    return TDX_E_BADARG;
+  if (kind != TDX_TARGET_EPS && kind != TDX_TARGET_V) return TDX_E_BADARG;
+  if (per_sample % 4) return TDX_E_SHAPE;
+  int64_t n4 = (int64_t)batch * per_sample / 4;
+  // the eps target in place is the noise as it stands
+  float4* tg = (kind == TDX_TARGET_EPS && target == noise) ? nullptr : (float4*)target;
+  q_sample_target_kernel<false><<<ew_grid(n4, 256), 256, 0, to_stream(stream)>>>(
+      (const float4*)x0, (const float4*)noise, t, sqrt_ac, sqrt_1mac, (float4*)x_t, tg, n4, per_sample / 4, kind, 0, 0);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tdx_q_sample_target_philox(const float* x0, const int64_t* t, const float* sqrt_ac,
+                                          const float* sqrt_1mac, float* x_t, float* target, int batch,
+                                          int per_sample, int kind, uint64_t seed, uint64_t offset,
+                                          tdx_stream_t stream) {
+  if (!x0 || !t || !sqrt_ac || !sqrt_1mac || !x_t || !target || batch <= 0 || per_sample <= 0)
+    return TDX_E_BADARG;
+  if (kind != TDX_TARGET_EPS && kind != TDX_TARGET_V) return TDX_E_BADARG;
+  if (per_sample % 4) return TDX_E_SHAPE;
+  int64_t n4 = (int64_t)batch * per_sample / 4;
+  q_sample_target_kernel<true><<<ew_grid(n4, 256), 256, 0, to_stream(stream)>>>(
+      (const float4*)x0, nullptr, t, sqrt_ac, sqrt_1mac, (float4*)x_t, (float4*)target, n4, per_sample / 4, kind, seed,
+      offset);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
 // ------------------------------------------------------------- p_sample step
 // x' = c1*(x - c2*eps) + sigma*z, evaluated in the reference's operation order
 // (diffusion.py:272-274): mul, sub, mul, mul, add - each rounded separately.
@@ -444,6 +520,55 @@ extern "C" int tdx_mse_loss_grad(const float* a, const float* b, float* loss_out
   mse_loss_grad_kernel<<<grid, 256, 0, st>>>(a, b, d_a, 2.0f * gscale / (float)n, n, static_cast<double*>(scratch));
   TDX_CHECK_LAUNCH();
   mse_finish_kernel<<<1, 256, 0, st>>>(static_cast<const double*>(scratch), grid, loss_out, 1.0 / (double)n);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+// The same pass with a per-timestep loss weight (TrainStep(loss_weighting=...)): sample s = i / per_sample carries
+// w = w_table[t[s]];  loss = sum w (a-b)^2 / n,  d_a = fl(fl(a-b) * fl(scale * w)) with scale as above.  The grid, the
+// element -> block mapping, the double partials and the finish are those of mse_loss_grad_kernel, so a table of ones
+// gives its loss and gradient bit for bit (1.0 * x is exact in both precisions).
+template <typename IDX>
+__global__ void __launch_bounds__(256)
+mse_loss_grad_weighted_kernel(const float* __restrict__ a, const float* __restrict__ b, const int64_t* __restrict__ t,
+                              const float* __restrict__ w_table, float* __restrict__ d_a, float scale, int64_t n,
+                              int per_sample, double* __restrict__ partials) {
+  __shared__ double red[4];
+  double s = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float w = w_table[t[(IDX)i / (IDX)per_sample]];
+    const float d = a[i] - b[i];
+    if (d_a) d_a[i] = __fmul_rn(d, __fmul_rn(scale, w));
+    s += (double)w * ((double)d * (double)d);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    long long v = __double_as_longlong(s);
+    int lo = __shfl_xor((int)(v & 0xffffffffll), o, 64);
+    int hi = __shfl_xor((int)(v >> 32), o, 64);
+    s += __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+  }
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+extern "C" int tdx_mse_loss_grad_weighted(const float* a, const float* b, const int64_t* t, const float* w_table,
+                                          float* loss_out, float* d_a, float gscale, int batch, int per_sample,
+                                          void* scratch, tdx_stream_t stream) {
+  if (!a || !b || !t || !w_table || !loss_out || !scratch || batch <= 0 || per_sample <= 0) return TDX_E_BADARG;
+  hipStream_t st = to_stream(stream);
+  const int64_t n = (int64_t)batch * per_sample;
+  int grid = (int)((n + 1023) / 1024);
+  if (grid > MSE_BLOCKS) grid = MSE_BLOCKS;
+  const float scale = 2.0f * gscale / (float)n;
+  double* partials = static_cast<double*>(scratch);
+  if (n <= 0x7fffffff)   // the sample index by a 32-bit division
+    mse_loss_grad_weighted_kernel<uint32_t><<<grid, 256, 0, st>>>(a, b, t, w_table, d_a, scale, n, per_sample, partials);
+  else
+    mse_loss_grad_weighted_kernel<int64_t><<<grid, 256, 0, st>>>(a, b, t, w_table, d_a, scale, n, per_sample, partials);
+  TDX_CHECK_LAUNCH();
+  mse_finish_kernel<<<1, 256, 0, st>>>(partials, grid, loss_out, 1.0 / (double)n);
   TDX_CHECK_LAUNCH();
   return 0;
 }
