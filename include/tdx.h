@@ -122,6 +122,24 @@ int tdx_p_sample_step_guided(float* x, const float* eps, const float* z, const f
                              const int32_t* t_idx, int64_t n_half_elems, float w, int use_philox, uint64_t philox_seed,
                              int64_t* counter_dec, tdx_stream_t stream);
 
+/* Clipped-x0 sampling ("clip_denoised", Ho et al. 2020; Imagen's static thresholding): the update in x0 form with the
+ * implied x0 clamped to [lo, hi].  coef5: device table (S,5) of rows (p, q, A, Bx, sigma) (schedule.py
+ * TimestepSchedule.x0_form), row t = *t_idx:
+ *   x0 = p*x + q*out;   x0c = min(max(x0, lo), hi);   x_out = (A*x0c + Bx*x) + sigma*z
+ * every product and sum rounded separately, in this order.  out is the network's output (eps or v: the row's p, q say
+ * which).  Noise: z (n floats) or NULL, or in-kernel Philox when use_philox != 0 (z ignored) - block j/4, component j%4,
+ * stream tau[t] (t when tau == NULL), as tdx_p_sample_step{,_sched}_philox; none at t == 0.  tau, counter_dec as in
+ * tdx_p_sample_step_guided.  x_out may be x.  Infinite bounds never bind.  TDX_E_BADARG: a null pointer, n <= 0,
+ * n % 4, or not lo < hi (a NaN bound included). */
+int tdx_p_sample_step_x0(float* x_out, const float* x, const float* out, const float* z, const float* coef5,
+                         const int64_t* tau, const int32_t* t_idx, int64_t n, float lo, float hi, int use_philox,
+                         uint64_t philox_seed, int64_t* counter_dec, tdx_stream_t stream);
+/* ... guided: the layout, the combination e = out_u + w (out_c - out_u) and the noise of tdx_p_sample_step_guided, then
+ * the x0 form above on e; written to both halves of x (in place). */
+int tdx_p_sample_step_x0_guided(float* x, const float* out, const float* z, const float* coef5, const int64_t* tau,
+                                const int32_t* t_idx, int64_t n_half_elems, float w, float lo, float hi,
+                                int use_philox, uint64_t philox_seed, int64_t* counter_dec, tdx_stream_t stream);
+
 /* Condition dropout for training the unconditional branch: sample b is dropped iff a Philox uniform in [0,1) keyed by
  * (seed, offset, b) is < p (p == 0: exact copy, p == 1: every sample).  A dropped sample gets label -1 / a zeroed row.
  * The two entries draw the same mask for the same key.  In place (y_out == y, c_out == c) is allowed. */
@@ -669,6 +687,16 @@ int tdx_unet_eval_step_guided(tdx_unet* u, const void* const* params, void* cons
                               int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
                               void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed, float w,
                               tdx_stream_t stream);
+
+/* The clipped-x0 reverse step (see tdx_p_sample_step_x0): the arguments of tdx_unet_eval_step_guided with coef5 the
+ * (S,5) table and the clamp [lo, hi].  guided == 0: an unguided step of any model (w ignored, n_elems = all of x);
+ * guided != 0: batch = 2n, n_elems = the first half's (the UNets only).  tau == NULL: the identity chain (S ignored).
+ * Sampling tables, the counter and the half-batch forward as in the other eval steps. */
+int tdx_unet_eval_step_x0(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
+                          const void* cond, const float* z, const float* coef5, const int64_t* tau, int S,
+                          int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
+                          void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed, int guided, float w,
+                          float lo, float hi, tdx_stream_t stream);
 
 /* Testing aid: offset (in floats) and element count of a named intermediate inside the
  * workspace after a forward: "x0", "Y0".."Y12", "ss0".."ss12", "e1p", "cat1", "d1a", ... */

@@ -1,0 +1,189 @@
+"""Clipped-x0 sampling, host side (no GPU): the x0-form coefficient table (``TimestepSchedule.x0_form``) against the
+schedule's own update in fp64, the row-0 rule, the ``clip_denoised`` argument errors of ``sample_loop`` and the module
+wrappers, and the new C entries being declared, listed and exported."""
+import math
+import os
+import re
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ("tdx_p_sample_step_x0", "tdx_p_sample_step_x0_guided", "tdx_unet_eval_step_x0")
+INF = float("inf")
+
+
+def _fp(T):
+    from tiny_diffusion_amd.schedule import ForwardProcess
+
+    return ForwardProcess(num_timesteps=T)
+
+
+def _schedule(fp, name):
+    from tiny_diffusion_amd.schedule import ddim_schedule, ddpm_schedule
+
+    if name == "ddpm":
+        return ddpm_schedule(fp)
+    return ddim_schedule(fp, steps=10, eta={"ddim_eta0": 0.0, "ddim_eta05": 0.5}[name])
+
+
+# ------------------------------------------------------------------ 1. x0_form against fp64
+@pytest.mark.parametrize("prediction", ["eps", "v"])
+@pytest.mark.parametrize("T,name", [(20, "ddpm"), (1000, "ddpm"), (1000, "ddim_eta0"), (1000, "ddim_eta05"),
+                                    (20, "ddim_eta0"), (20, "ddim_eta05")])
+def test_x0_form_is_the_schedules_update(T, name, prediction):
+    fp = _fp(T)
+    sched = _schedule(fp, name)
+    S = sched.steps
+    t64 = sched.x0_form(fp, prediction, dtype=torch.float64)
+    t32 = sched.x0_form(fp, prediction)
+    assert t64.shape == (S, 5) and t64.dtype == torch.float64 and t32.dtype == torch.float32
+    assert t32.device.type == "cpu" and t32.is_contiguous()
+    assert torch.equal(t32, t64.to(torch.float32))                       # rounded once
+    assert torch.isfinite(t64).all() and torch.isfinite(t32).all()       # T = 1000 at k = T - 1 included
+    assert torch.equal(t64[:, 4], sched.coef64[:, 2]) and torch.equal(t32[:, 4], sched.coef[:, 2])   # sigma unchanged
+    assert t64[0, 2].item() == 1.0 and t64[0, 3].item() == 0.0           # row 0 by definition
+    assert t32[0, 2].item() == 1.0 and t32[0, 3].item() == 0.0
+    # (p, q) are the prediction's: x0 from x and the network's output
+    acp = fp.alphas_cumprod.double()
+    taus = sched.timesteps.tolist()
+    for k in (0, 1, S - 1):
+        a, b = math.sqrt(acp[taus[k]].item()), math.sqrt(1 - acp[taus[k]].item())
+        p, q = (1 / a, -b / a) if prediction == "eps" else (a, -b)
+        assert abs(t64[k, 0].item() - p) <= 1e-15 * abs(p) and abs(t64[k, 1].item() - q) <= 1e-15 * abs(q)
+    # the existing update of the same chain, for_prediction for a v-model
+    ref = sched.for_prediction(fp, prediction).coef64
+    g = torch.Generator().manual_seed(T + len(name))
+    x, out, z = (torch.randn(64, dtype=torch.float64, generator=g) for _ in range(3))
+    for k in range(1, S):
+        p, q, A, Bx, sg = t64[k].tolist()
+        c1, c2, sg_ref = ref[k].tolist()
+        x0c = torch.clamp(p * x + q * out, -INF, INF)
+        got = A * x0c + Bx * x + sg * z
+        want = c1 * (x - c2 * out) + sg_ref * z
+        scale = want.abs().max().item()
+        assert (got - want).abs().max().item() <= 1e-12 * scale, (k, (got - want).abs().max().item() / scale)
+    # k = 0: the clamped prediction itself (no noise term)
+    p, q, A, Bx, _ = t64[0].tolist()
+    for lo, hi in ((-INF, INF), (-1.0, 1.0), (-0.5, 0.25)):
+        x0c = torch.clamp(p * x + q * out, lo, hi)
+        assert torch.equal(A * x0c + Bx * x, x0c)
+        assert x0c.min() >= lo and x0c.max() <= hi
+    if name != "ddpm":
+        # the closed forms of the DDIM rows: A = sqrt(ab_prev) - a r / b, Bx = r / b, r = sqrt(1 - ab_prev - sigma^2)
+        for k in range(1, S):
+            ab, ab_prev = acp[taus[k]].item(), acp[taus[k - 1]].item()
+            a, b, sg = math.sqrt(ab), math.sqrt(1 - ab), t64[k, 4].item()
+            r = math.sqrt(1 - ab_prev - sg * sg)
+            assert abs(t64[k, 2].item() - (math.sqrt(ab_prev) - a * r / b)) <= 1e-12
+            assert abs(t64[k, 3].item() - r / b) <= 1e-12
+
+
+def test_x0_form_tables_are_cached_and_checked():
+    fp = _fp(20)
+    sched = _schedule(fp, "ddim_eta05")
+    a = sched.x0_form(fp, "eps", device="cpu")
+    assert a is sched.x0_form(fp, "eps", device="cpu") and torch.equal(a, sched.x0_form(fp))
+    assert sched.x0_form(fp, "v", device="cpu") is not a
+    assert sched.x0_form(fp) is sched.x0_form(fp, "eps")
+    tau, coef = sched.device_tables("cpu")          # the (S,3) tables live beside it, untouched
+    assert coef.shape == (10, 3) and sched.device_tables("cpu")[1] is coef and torch.equal(coef, sched.coef)
+    for p in ("x0", None, 1):
+        with pytest.raises(ValueError, match="prediction"):
+            sched.x0_form(fp, p)
+    with pytest.raises(ValueError, match="T = 20"):
+        sched.x0_form(_fp(1000))
+
+
+# ------------------------------------------------------------------ 2. argument errors
+class _NoModel:
+    def eval(self):
+        raise AssertionError("the argument errors come before the model is touched")
+
+
+BAD = ["yes", (1, -1), (0, 0), (float("nan"), 1), (-1.0, 0.0, 1.0)]
+GOOD = [True, False, None, (-INF, INF)]
+
+
+@pytest.mark.parametrize("bad", BAD, ids=repr)
+def test_clip_denoised_argument_errors_come_first(bad):
+    from tiny_diffusion_amd import _lib
+    from tiny_diffusion_amd import conditional_diffusion as C
+    from tiny_diffusion_amd import conditional_diffusion_laion as LA
+    from tiny_diffusion_amd import diffusion as D
+    from tiny_diffusion_amd import diffusion_transformer as DT
+    from tiny_diffusion_amd import latent_diffusion as LD
+    from tiny_diffusion_amd.schedule import ddim_sample_loop, sample_loop
+
+    fp = _fp(20)
+    y = torch.tensor([1, 2])
+    # a CPU device: the "GPU only" error would be a TdxError (not a ValueError), and it must not be reached
+    with pytest.raises(ValueError, match="clip_denoised"):
+        sample_loop(_NoModel(), fp, "cpu", 2, clip_denoised=bad)
+    with pytest.raises(ValueError, match="clip_denoised"):
+        ddim_sample_loop(_NoModel(), fp, "cpu", 2, steps=5, clip_denoised=bad)
+    with pytest.raises(ValueError, match="clip_denoised"):     # before the schedule's own errors
+        ddim_sample_loop(_NoModel(), fp, "cpu", 2, steps=0, clip_denoised=bad)
+    with pytest.raises(ValueError, match="clip_denoised"):
+        D.sample(_NoModel(), fp, "cpu", n_samples=2, clip_denoised=bad)
+    with pytest.raises(ValueError, match="clip_denoised"):
+        D.ddim_sample(_NoModel(), fp, "cpu", n_samples=2, steps=5, clip_denoised=bad)
+    with pytest.raises(ValueError, match="clip_denoised"):
+        C.sample(_NoModel(), fp, "cpu", n_samples=2, y=y, clip_denoised=bad)
+    with pytest.raises(ValueError, match="clip_denoised"):
+        C.ddim_sample(_NoModel(), fp, "cpu", n_samples=2, y=y, steps=5, clip_denoised=bad)
+    with pytest.raises(ValueError, match="clip_denoised"):
+        LA.sample(_NoModel(), fp, "cpu", text_embeds=torch.zeros(2, 768), clip_denoised=bad)
+    with pytest.raises(ValueError, match="clip_denoised"):
+        LA.ddim_sample(_NoModel(), fp, "cpu", text_embeds=torch.zeros(2, 768), steps=5, clip_denoised=bad)
+
+    class _NoVAE:
+        def eval(self):
+            pass
+
+    for mod in (LD, DT):
+        with pytest.raises(ValueError, match="clip_denoised"):
+            mod.sample(_NoVAE(), _NoModel(), fp, "cpu", n_samples=2, y=y, clip_denoised=bad)
+        with pytest.raises(ValueError, match="clip_denoised"):
+            mod.ddim_sample(_NoVAE(), _NoModel(), fp, "cpu", n_samples=2, y=y, steps=5, clip_denoised=bad)
+    assert issubclass(_lib.TdxError, RuntimeError) and not issubclass(_lib.TdxError, ValueError)
+
+
+@pytest.mark.parametrize("good", GOOD, ids=repr)
+def test_clip_denoised_accepted_values_reach_the_device_check(good):
+    from tiny_diffusion_amd import _lib
+    from tiny_diffusion_amd import diffusion as D
+    from tiny_diffusion_amd.schedule import ddim_sample_loop, sample_loop
+
+    fp = _fp(20)
+    for call in (lambda: sample_loop(_NoModel(), fp, "cpu", 2, clip_denoised=good),
+                 lambda: ddim_sample_loop(_NoModel(), fp, "cpu", 2, steps=5, clip_denoised=good),
+                 lambda: D.sample(_NoModel(), fp, "cpu", n_samples=2, clip_denoised=good)):
+        with pytest.raises(_lib.TdxError, match="GPU only"):
+            call()
+
+
+def test_clip_denoised_values():
+    import numpy as np
+
+    from tiny_diffusion_amd.schedule import _clip_denoised
+
+    assert _clip_denoised(None) is None and _clip_denoised(False) is None and _clip_denoised(np.bool_(False)) is None
+    assert _clip_denoised(True) == (-1.0, 1.0) and _clip_denoised(np.bool_(True)) == (-1.0, 1.0)
+    assert _clip_denoised((-INF, INF)) == (-INF, INF) and _clip_denoised([-0.5, 0.25]) == (-0.5, 0.25)
+    assert _clip_denoised((np.float32(-2), 3)) == (-2.0, 3.0) and _clip_denoised((-INF, 0)) == (-INF, 0.0)
+    for bad in BAD + [(True, 2), (1,), 1.0, (None, 1), ("a", "b"), (1, float("nan")), torch.tensor([-1.0, 1.0]), {}]:
+        with pytest.raises(ValueError, match="clip_denoised"):
+            _clip_denoised(bad)
+
+
+# ------------------------------------------------------------------ 3. ABI
+def test_new_symbols_declared_listed_and_exported():
+    import tiny_diffusion_amd._lib as L
+
+    hdr = open(os.path.join(ROOT, "include", "tdx.h")).read()
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\b" + name + r"\s*\(", hdr), name
+        assert name in L.EXPORTS, name
+        assert getattr(L.lib, name).argtypes is not None, name   # bound: the library exports it
+    assert L.lib.tdx_version() == 400   # the ABI only grows

@@ -30,7 +30,9 @@ class NoiseModel(NoiseModelBase):
 def sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples=16, y=None,
            guidance_scale: Optional[float] = None, **kw):
     """conditional_diffusion.py:354-386, including its argument errors.  ``guidance_scale=w``: classifier-free
-    guidance ``eps_u + w (eps_c - eps_u)`` against the null label (schedule.sample_loop); ``None``: none."""
+    guidance ``eps_u + w (eps_c - eps_u)`` against the null label (schedule.sample_loop); ``None``: none.
+    ``clip_denoised=True | (lo, hi)`` (through ``**kw``, like ``prediction``): clipped-x0 sampling, which keeps guided
+    samples inside the data range at w > 1."""
     _check_labels(y, n_samples)
     return sample_loop(noise_model, diffusion, device, n_samples, y, guidance_scale=guidance_scale, **kw)
 

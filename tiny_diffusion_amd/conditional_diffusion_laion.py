@@ -74,7 +74,8 @@ def sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, text_embe
     ``vae.decode(x / scaling_factor).sample`` and the image post-processing.  With
     ``vae=None`` the latents are returned (the decoder is an external pretrained model).
     ``guidance_scale=w``: classifier-free guidance ``eps_u + w (eps_c - eps_u)`` against the all-zero text
-    embedding (schedule.sample_loop); ``None``: none."""
+    embedding (schedule.sample_loop); ``None``: none.  ``clip_denoised=(lo, hi)`` (through ``**kw``): clipped-x0
+    sampling with the latents' own range (``True`` is [-1, 1], the range of pixel data)."""
     if text_embeds is None:
         raise ValueError("Text embeddings must be provided for conditional generation.")
     n_samples = text_embeds.shape[0]

@@ -67,6 +67,17 @@ __device__ static inline float p_step(float x, float e, float z, float c1, float
   return __fadd_rn(__fmul_rn(c1, inner), __fmul_rn(sg, z));
 }
 
+// The update in x0 form with the implied x0 clamped to [lo, hi] (clipped-x0 sampling, "static thresholding"):
+//   x0 = p*x + q*out;  x0c = min(max(x0, lo), hi);  x' = (A*x0c + Bx*x) + sigma*z
+// from a (p, q, A, Bx, sigma) row (schedule.py x0_form).  Every product and sum is rounded separately, in this
+// order - a CPU fp32 tensor expression reproduces it bit for bit, as it does p_step.
+__device__ static inline float p_step_x0(float x, float o, float z, float p, float q, float A, float Bx, float sg,
+                                         float lo, float hi) {
+  const float x0 = __fadd_rn(__fmul_rn(p, x), __fmul_rn(q, o));
+  const float x0c = fminf(fmaxf(x0, lo), hi);
+  return __fadd_rn(__fadd_rn(__fmul_rn(A, x0c), __fmul_rn(Bx, x)), __fmul_rn(sg, z));
+}
+
 // classifier-free guidance (Ho & Salimans 2021): eps_u + w (eps_c - eps_u), each operation rounded separately - the
 // one expression both guided updates evaluate (elementwise.hip, the epilogue of final_conv in edge_conv.hip)
 __device__ static inline float cfg_eps(float e_c, float e_u, float w) {

@@ -302,6 +302,96 @@ extern "C" int tdx_p_sample_step_guided(float* x, const float* eps, const float*
   return 0;
 }
 
+// ------------------------------------------------------------- p_sample step, x0 form (clipped-x0 sampling)
+// x' = p_step_x0(x, out, z, row t of the (S,5) table (p, q, A, Bx, sigma), lo, hi) (common.h; the boundary convolution
+// fuses the same update into its epilogue).  t, tau, counter_dec, the noise term (none at t == 0) and the Philox
+// indexing (block i, component of the float4, stream tau[t]) are p_sample_kernel's, so a clipped chain consumes the
+// noise of the unclipped chain of the same seed.
+__device__ __forceinline__ float4 p_step_x0_4(const float4 x, const float4 o, const float4 z, float p, float q, float A,
+                                              float Bx, float sg, float lo, float hi) {
+  float4 r;
+  r.x = p_step_x0(x.x, o.x, z.x, p, q, A, Bx, sg, lo, hi);
+  r.y = p_step_x0(x.y, o.y, z.y, p, q, A, Bx, sg, lo, hi);
+  r.z = p_step_x0(x.z, o.z, z.z, p, q, A, Bx, sg, lo, hi);
+  r.w = p_step_x0(x.w, o.w, z.w, p, q, A, Bx, sg, lo, hi);
+  return r;
+}
+
+__global__ void p_sample_x0_kernel(float4* xo, const float4* x,  // may alias: in-place update
+                                   const float4* __restrict__ out, const float4* __restrict__ z,
+                                   const float* __restrict__ coef, const int32_t* __restrict__ t_idx, int64_t n4,
+                                   float lo, float hi, int philox, uint64_t seed, int64_t* counter_dec,
+                                   const int64_t* __restrict__ tau) {
+  const int t = *t_idx;
+  const uint64_t nt = tau ? (uint64_t)tau[t] : (uint64_t)t;
+  if (counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *counter_dec = (int64_t)t - 1;
+  const float p = coef[5 * t + 0], q = coef[5 * t + 1], A = coef[5 * t + 2], Bx = coef[5 * t + 3], sg = coef[5 * t + 4];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 xv = x[i], ov = out[i];
+    float4 zv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (t > 0) {
+      if (philox) zv = philox_normal4((uint64_t)i, nt, seed);
+      else if (z) zv = z[i];
+    }
+    xo[i] = p_step_x0_4(xv, ov, zv, p, q, A, Bx, sg, lo, hi);
+  }
+}
+
+// Guided: the layout and the noise of p_sample_guided_kernel; the two outputs are combined first (cfg_eps is linear in
+// the network's output, whatever it predicts), the x0 form is applied to the combination.
+__global__ void p_sample_x0_guided_kernel(float4* x, const float4* __restrict__ out, const float4* __restrict__ z,
+                                          const float* __restrict__ coef, const int32_t* __restrict__ t_idx,
+                                          int64_t n4, float w, float lo, float hi, int philox, uint64_t seed,
+                                          int64_t* counter_dec, const int64_t* __restrict__ tau) {
+  const int t = *t_idx;
+  const uint64_t nt = tau ? (uint64_t)tau[t] : (uint64_t)t;
+  if (counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *counter_dec = (int64_t)t - 1;
+  const float p = coef[5 * t + 0], q = coef[5 * t + 1], A = coef[5 * t + 2], Bx = coef[5 * t + 3], sg = coef[5 * t + 4];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 xv = x[i], oc = out[i], ou = out[i + n4];
+    float4 zv = make_float4(0.f, 0.f, 0.f, 0.f), e;
+    if (t > 0) {
+      if (philox) zv = philox_normal4((uint64_t)i, nt, seed);
+      else if (z) zv = z[i];
+    }
+    e.x = cfg_eps(oc.x, ou.x, w);
+    e.y = cfg_eps(oc.y, ou.y, w);
+    e.z = cfg_eps(oc.z, ou.z, w);
+    e.w = cfg_eps(oc.w, ou.w, w);
+    const float4 o = p_step_x0_4(xv, e, zv, p, q, A, Bx, sg, lo, hi);
+    x[i] = o;
+    x[i + n4] = o;
+  }
+}
+
+// One entry for every mode: z a noise tensor or null, use_philox in-kernel noise (z ignored), tau null (t_idx holds the
+// timestep) or the schedule's timesteps, counter_dec null or the table-mode step counter.  !(lo < hi) - a NaN
+// included - is a bad argument; infinite bounds never bind.
+extern "C" int tdx_p_sample_step_x0(float* x_out, const float* x, const float* out, const float* z, const float* coef5,
+                                    const int64_t* tau, const int32_t* t_idx, int64_t n, float lo, float hi,
+                                    int use_philox, uint64_t philox_seed, int64_t* counter_dec, tdx_stream_t stream) {
+  if (!x_out || !x || !out || !coef5 || !t_idx || n <= 0 || (n % 4) || !(lo < hi)) return TDX_E_BADARG;
+  p_sample_x0_kernel<<<ew_grid(n / 4, 256), 256, 0, to_stream(stream)>>>(
+      (float4*)x_out, (const float4*)x, (const float4*)out, (const float4*)z, coef5, t_idx, n / 4, lo, hi,
+      use_philox != 0, philox_seed, counter_dec, tau);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tdx_p_sample_step_x0_guided(float* x, const float* out, const float* z, const float* coef5,
+                                           const int64_t* tau, const int32_t* t_idx, int64_t n_half_elems, float w,
+                                           float lo, float hi, int use_philox, uint64_t philox_seed,
+                                           int64_t* counter_dec, tdx_stream_t stream) {
+  if (!x || !out || !coef5 || !t_idx || n_half_elems <= 0 || (n_half_elems % 4) || !(lo < hi)) return TDX_E_BADARG;
+  p_sample_x0_guided_kernel<<<ew_grid(n_half_elems / 4, 256), 256, 0, to_stream(stream)>>>(
+      (float4*)x, (const float4*)out, (const float4*)z, coef5, t_idx, n_half_elems / 4, w, lo, hi, use_philox != 0,
+      philox_seed, counter_dec, tau);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
 // Device-side step counter for graph-captured sampling: t = *counter; t_idx = t; t_vec[:] = t;
 // *counter = t - 1.  One block; lets a HIP graph hold several consecutive reverse steps with no
 // host work between them (diffusion.py:259-260 builds the same t tensor on the host each step).

@@ -24,7 +24,9 @@ class NoiseModel(NoiseModelBase):
 @torch.no_grad()
 def sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples=16, **kw):
     """diffusion.py:254-276: leaves the model in eval mode, returns x_0 in ~[-1, 1].
-    Extra keyword arguments (x_T, noises, use_graph, philox_seed) are extensions."""
+    Extra keyword arguments (x_T, noises, use_graph, philox_seed, prediction, clip_denoised) are extensions;
+    ``clip_denoised=True | (lo, hi)`` clamps the implied x_0 at every step (schedule.sample_loop) and returns x_0 in
+    [-1, 1] / [lo, hi] exactly."""
     return sample_loop(noise_model, diffusion, device, n_samples, None, **kw)
 
 

@@ -118,7 +118,7 @@ class NoiseModel(nn.Module):
 
 @torch.no_grad()
 def sample(vae: VAE, noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples=16, y=None, **kw):
-    """diffusion_transformer.py:284-323 (identical to latent_diffusion.sample)."""
+    """diffusion_transformer.py:284-323 (identical to latent_diffusion.sample, ``clip_denoised`` included)."""
     _check_labels(y, n_samples)
     vae.eval()
     z = sample_loop(noise_model, diffusion, device, n_samples, y, **kw)

@@ -31,7 +31,8 @@ class NoiseModel(NoiseModelBase):
 @torch.no_grad()
 def sample(vae: VAE, noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples=16, y=None, **kw):
     """latent_diffusion.py:308-347: reverse loop over z (n,20), then ``vae.decode(z)`` viewed
-    as (n,1,28,28); same argument errors."""
+    as (n,1,28,28); same argument errors.  ``sample_loop``'s extension keywords pass through (``clip_denoised=(lo, hi)``
+    clamps the implied z_0, in the latent's own range)."""
     _check_labels(y, n_samples)
     vae.eval()
     z = sample_loop(noise_model, diffusion, device, n_samples, y, **kw)
