@@ -140,6 +140,24 @@ int tdx_p_sample_step_x0_guided(float* x, const float* out, const float* z, cons
                                 const int32_t* t_idx, int64_t n_half_elems, float w, float lo, float hi,
                                 int use_philox, uint64_t philox_seed, int64_t* counter_dec, tdx_stream_t stream);
 
+/* The multistep sampler (DPM-Solver++(2M), Lu et al. 2022): the x0-form update plus one term in the clamped x0 of the
+ * step before.  coef5: device table (S,5) of rows (p, q, A, Bx, H) (schedule.py TimestepSchedule.multistep_form),
+ * row t = *t_idx:
+ *   x0 = p*x + q*out;   x0c = min(max(x0, lo), hi);   x_out = (A*x0c + Bx*x) + H*hist;   hist = x0c
+ * every product and sum rounded separately, in this order; deterministic (no noise).  hist: n floats that the caller
+ * keeps from step to step; when the row's H == 0 (the first and the last step, order 1) it is not read and the term is
+ * not added, so it never has to be initialised; it is always written.  x_out may be x; counter_dec as in
+ * tdx_p_sample_step_x0.  Infinite bounds never bind (no clipping).  TDX_E_BADARG: a null pointer, n <= 0, n % 4, or
+ * not lo < hi (a NaN bound included). */
+int tdx_p_sample_step_ms(float* x_out, const float* x, const float* out, float* hist, const float* coef5,
+                         const int32_t* t_idx, int64_t n, float lo, float hi, int64_t* counter_dec,
+                         tdx_stream_t stream);
+/* ... guided: the layout and the combination e = out_u + w (out_c - out_u) of tdx_p_sample_step_guided, then the
+ * update above on e against one history of n_half_elems floats; written to both halves of x (in place). */
+int tdx_p_sample_step_ms_guided(float* x, const float* out, float* hist, const float* coef5, const int32_t* t_idx,
+                                int64_t n_half_elems, float w, float lo, float hi, int64_t* counter_dec,
+                                tdx_stream_t stream);
+
 /* Condition dropout for training the unconditional branch: sample b is dropped iff a Philox uniform in [0,1) keyed by
  * (seed, offset, b) is < p (p == 0: exact copy, p == 1: every sample).  A dropped sample gets label -1 / a zeroed row.
  * The two entries draw the same mask for the same key.  In place (y_out == y, c_out == c) is allowed. */
@@ -697,6 +715,14 @@ int tdx_unet_eval_step_x0(tdx_unet* u, const void* const* params, void* const* b
                           int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
                           void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed, int guided, float w,
                           float lo, float hi, tdx_stream_t stream);
+
+/* The multistep reverse step (see tdx_p_sample_step_ms): the arguments of tdx_unet_eval_step_x0 without z and
+ * philox_seed (the chain is deterministic) plus the history hist (n_elems floats, kept by the caller from step to
+ * step).  coef5 is the (S,5) table (p, q, A, Bx, H). */
+int tdx_unet_eval_step_ms(tdx_unet* u, const void* const* params, void* const* buffers, float* x, const void* cond,
+                          const float* coef5, const int64_t* tau, int S, int64_t* counter, int32_t* t_idx,
+                          int64_t* t_vec, float* eps, int64_t n_elems, void* workspace, size_t workspace_bytes,
+                          int batch, int guided, float w, float lo, float hi, float* hist, tdx_stream_t stream);
 
 /* Testing aid: offset (in floats) and element count of a named intermediate inside the
  * workspace after a forward: "x0", "Y0".."Y12", "ss0".."ss12", "e1p", "cat1", "d1a", ... */

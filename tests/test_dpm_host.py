@@ -1,0 +1,311 @@
+"""The DPM-Solver++(2M) sampler, host side (no GPU): log-SNR timestep spacing, the multistep coefficient table
+(``MultistepSchedule.multistep_form``) against DDIM and its own row structure, the solver's order of convergence on an
+analytic Gaussian model in Python doubles, the argument errors of ``dpm_sample`` in every module, and the new C entries
+being declared, listed and exported."""
+import math
+import os
+import re
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ("tdx_p_sample_step_ms", "tdx_p_sample_step_ms_guided", "tdx_unet_eval_step_ms")
+LOGSNR_10 = [0, 5, 22, 73, 202, 410, 603, 757, 886, 999]   # the default ForwardProcess(), steps = 10
+
+
+def _fp(T=1000):
+    from tiny_diffusion_amd.schedule import ForwardProcess
+
+    return ForwardProcess(num_timesteps=T)
+
+
+# ------------------------------------------------------------------ 1. log-SNR spacing
+def test_logsnr_timesteps_fixture_and_shape():
+    from tiny_diffusion_amd.schedule import ddim_schedule, logsnr_timesteps
+
+    fp = _fp()
+    T = fp.num_timesteps
+    assert logsnr_timesteps(fp, 10) == LOGSNR_10
+    assert logsnr_timesteps(fp, 1) == [T - 1]
+    for S in (1, 2, 40, T):
+        tau = logsnr_timesteps(fp, S)
+        assert isinstance(tau, list) and all(isinstance(t, int) for t in tau)
+        assert 1 <= len(tau) <= S
+        assert all(b > a for a, b in zip(tau, tau[1:]))            # ascending, no duplicates
+        assert tau[0] >= 0 and tau[-1] < T and tau[-1] == T - 1
+        if S > 1:
+            assert tau[0] == 0
+        assert ddim_schedule(fp, timesteps=tau).timesteps.tolist() == tau    # a list ddim_sample accepts
+    # the rule itself, restated in Python doubles: nearest lam_t to each target, the lowest t on a tie
+    acp = fp.alphas_cumprod.double().tolist()
+    lam = [0.5 * math.log(a / (1 - a)) for a in acp]
+    want = set()
+    for i in range(7):
+        target = lam[0] + i * (lam[T - 1] - lam[0]) / 6
+        want.add(min(range(T), key=lambda t: (abs(lam[t] - target), t)))
+    assert logsnr_timesteps(fp, 7) == sorted(want)
+
+
+@pytest.mark.parametrize("bad", [0, -1, 1001, 2.0, "10", None, True], ids=repr)
+def test_logsnr_timesteps_errors(bad):
+    from tiny_diffusion_amd.schedule import dpm_solver_schedule, logsnr_timesteps
+
+    with pytest.raises(ValueError, match="steps"):
+        logsnr_timesteps(_fp(), bad)
+    if bad is not None:
+        with pytest.raises(ValueError, match="steps"):
+            dpm_solver_schedule(_fp(), steps=bad)
+        with pytest.raises(ValueError, match="steps"):
+            dpm_solver_schedule(_fp(), steps=bad, spacing="uniform")
+
+
+def test_dpm_solver_schedule_arguments():
+    from tiny_diffusion_amd.schedule import TimestepSchedule, ddim_schedule, dpm_solver_schedule
+
+    fp = _fp()
+    s = dpm_solver_schedule(fp, steps=10)
+    assert isinstance(s, TimestepSchedule) and s.order == 2 and s.timesteps.tolist() == LOGSNR_10
+    d = ddim_schedule(fp, timesteps=LOGSNR_10, eta=0.0)
+    assert torch.equal(s.coef64, d.coef64) and torch.equal(s.coef, d.coef) and s.eta == 0.0
+    u = dpm_solver_schedule(fp, steps=10, spacing="uniform", order=1)
+    assert u.order == 1 and u.timesteps.tolist() == ddim_schedule(fp, steps=10).timesteps.tolist()
+    e = dpm_solver_schedule(fp, timesteps=[3, 500, 900])
+    assert e.timesteps.tolist() == [3, 500, 900]
+    for order in (0, 3, 2.0, "2", None, True):
+        with pytest.raises(ValueError, match="order"):
+            dpm_solver_schedule(fp, steps=10, order=order)
+    for spacing in ("log", "", None, 1):
+        with pytest.raises(ValueError, match="spacing"):
+            dpm_solver_schedule(fp, steps=10, spacing=spacing)
+    with pytest.raises(ValueError, match="not both"):
+        dpm_solver_schedule(fp, steps=10, timesteps=[1, 2])
+    with pytest.raises(ValueError, match="steps or timesteps"):
+        dpm_solver_schedule(fp)
+    for bad in ([], [5, 5], [9, 3], [-1, 4], [0, 1000], [0.5, 2]):
+        with pytest.raises(ValueError, match="timesteps"):
+            dpm_solver_schedule(fp, timesteps=bad)
+
+
+# ------------------------------------------------------------------ 2. the table
+@pytest.mark.parametrize("T,kw", [(1000, dict(steps=10)), (1000, dict(steps=40)), (1000, dict(steps=25, spacing="uniform")),
+                                  (20, dict(steps=20)), (1000, dict(timesteps=[7])), (1000, dict(timesteps=[0, 999]))],
+                         ids=str)
+def test_order_1_equals_ddim(T, kw):
+    from tiny_diffusion_amd.schedule import ddim_schedule, dpm_solver_schedule
+
+    fp = _fp(T)
+    s = dpm_solver_schedule(fp, order=1, **kw)
+    for prediction in ("eps", "v"):
+        t = s.multistep_form(fp, prediction, dtype=torch.float64)
+        d = ddim_schedule(fp, timesteps=s.timesteps.tolist(), eta=0.0).x0_form(fp, prediction, dtype=torch.float64)
+        assert t.shape == (s.steps, 5) and t.dtype == torch.float64
+        err = (t[:, :4] - d[:, :4]).abs()
+        assert (err <= 1e-12 * d[:, :4].abs()).all(), (err / d[:, :4].abs().clamp_min(1e-300)).max().item()
+        assert not t[:, 4].any()
+
+
+@pytest.mark.parametrize("T,kw", [(1000, dict(steps=10)), (1000, dict(steps=40)), (1000, dict(steps=25, spacing="uniform")),
+                                  (20, dict(steps=20)), (1000, dict(timesteps=[7])), (1000, dict(timesteps=[0, 999])),
+                                  (1000, dict(timesteps=[0, 400, 999]))], ids=str)
+def test_order_2_row_structure(T, kw):
+    from tiny_diffusion_amd.schedule import dpm_solver_schedule
+
+    fp = _fp(T)
+    s1, s2 = dpm_solver_schedule(fp, order=1, **kw), dpm_solver_schedule(fp, order=2, **kw)
+    S = s2.steps
+    acp = fp.alphas_cumprod.double()
+    taus = s2.timesteps.tolist()
+    t1 = s1.multistep_form(fp, dtype=torch.float64)
+    t2 = s2.multistep_form(fp, dtype=torch.float64)
+    t32 = s2.multistep_form(fp)
+    assert t32.dtype == torch.float32 and t32.is_contiguous() and torch.equal(t32, t2.to(torch.float32))   # rounded once
+    assert torch.isfinite(t2).all() and torch.isfinite(t32).all()
+    assert ((t2[:, 2] + t2[:, 4] - t1[:, 2]).abs() <= 1e-12 * t1[:, 2].abs()).all()      # A + H = the order-1 A
+    assert torch.equal(t2[:, :2], t1[:, :2]) and torch.equal(t2[:, 3], t1[:, 3])
+    assert t2[0, 4].item() == 0.0 and t2[S - 1, 4].item() == 0.0
+    assert t2[0, 2:].tolist() == [1.0, 0.0, 0.0] and t32[0, 2:].tolist() == [1.0, 0.0, 0.0]
+    if S > 2:
+        assert (t2[1:S - 1, 4] < 0).all() and (t2[1:S - 1, 2] > t1[1:S - 1, 2]).all()     # a true extrapolation
+    # the closed forms, in Python doubles
+    lam = [0.5 * math.log(acp[t].item() / (1 - acp[t].item())) for t in taus]
+    for k in range(1, S):
+        a, b = math.sqrt(acp[taus[k]].item()), math.sqrt(1 - acp[taus[k]].item())
+        a1, b1 = math.sqrt(acp[taus[k - 1]].item()), math.sqrt(1 - acp[taus[k - 1]].item())
+        g = a1 - b1 * a / b
+        h = lam[k - 1] - lam[k]
+        assert abs(g - a1 * -math.expm1(-h)) <= 1e-12 * a1
+        A, H = g, 0.0
+        if k < S - 1:
+            r = (lam[k] - lam[k + 1]) / h
+            A, H = g * (1 + 1 / (2 * r)), -g / (2 * r)
+        assert abs(t2[k, 2].item() - A) <= 1e-12 * abs(A) and abs(t2[k, 4].item() - H) <= 1e-12 * abs(g)
+        assert abs(t2[k, 3].item() - b1 / b) <= 1e-15
+    # the v-model: the same A, Bx, H with (p, q) = (a, -b); the eps-model (1/a, -b/a)
+    tv = s2.multistep_form(fp, "v", dtype=torch.float64)
+    assert torch.equal(tv[:, 2:], t2[:, 2:])
+    for k in (0, S - 1):
+        a, b = math.sqrt(acp[taus[k]].item()), math.sqrt(1 - acp[taus[k]].item())
+        assert abs(tv[k, 0].item() - a) <= 1e-15 and abs(tv[k, 1].item() + b) <= 1e-15
+        assert abs(t2[k, 0].item() - 1 / a) <= 1e-15 / a and abs(t2[k, 1].item() + b / a) <= 1e-15 * b / a
+
+
+def test_multistep_form_is_cached_and_checked():
+    from tiny_diffusion_amd.schedule import dpm_solver_schedule
+
+    fp = _fp(20)
+    s = dpm_solver_schedule(fp, steps=8)
+    a = s.multistep_form(fp, "eps", device="cpu")
+    assert a is s.multistep_form(fp, "eps", device="cpu") and torch.equal(a, s.multistep_form(fp))
+    assert s.multistep_form(fp) is s.multistep_form(fp, "eps")
+    assert s.multistep_form(fp, "v", device="cpu") is not a
+    tau, coef = s.device_tables("cpu")               # the eps-form (S,3) rows live beside it
+    assert coef.shape == (s.steps, 3) and torch.equal(coef, s.coef)
+    assert s.x0_form(fp).shape == (s.steps, 5)       # still a schedule wherever a schedule works
+    for p in ("x0", None, 1):
+        with pytest.raises(ValueError, match="prediction"):
+            s.multistep_form(fp, p)
+    with pytest.raises(ValueError, match="T = 20"):
+        s.multistep_form(_fp(1000))
+    with pytest.raises(ValueError, match="fp32"):
+        s.multistep_form(fp, dtype=torch.float16)
+
+
+# ------------------------------------------------------------------ 3. convergence, in Python doubles
+MU, SD, X_START = 0.3, 0.5, 1.7
+
+
+def _chain_error(S, order, spacing="logsnr"):
+    """|x(tau_0) - exact| of the chain from x = 1.7 at tau_{S-1} down to tau_0 (steps k = S-1..1) on the fp64 table,
+    under the exact model of scalar data x0 ~ N(mu, s^2); the exact solution is the probability-flow ODE's."""
+    from tiny_diffusion_amd.schedule import dpm_solver_schedule
+
+    fp = _fp()
+    sched = dpm_solver_schedule(fp, steps=S, order=order, spacing=spacing)
+    tab = sched.multistep_form(fp, dtype=torch.float64).tolist()
+    taus = sched.timesteps.tolist()
+    acp = fp.alphas_cumprod.double()
+    ab = [(math.sqrt(acp[t].item()), math.sqrt(1 - acp[t].item())) for t in taus]
+    x, prev = X_START, 0.0
+    for k in range(len(taus) - 1, 0, -1):
+        a, b = ab[k]
+        x0_hat = MU + a * SD * SD * (x - a * MU) / (a * a * SD * SD + b * b)
+        eps = (x - a * x0_hat) / b
+        p, q, A, Bx, H = tab[k]
+        x0 = p * x + q * eps
+        x = (A * x0 + Bx * x) + H * prev
+        prev = x0
+    (a0, b0), (aT, bT) = ab[0], ab[-1]
+    exact = a0 * MU + math.sqrt(a0 * a0 * SD * SD + b0 * b0) / math.sqrt(aT * aT * SD * SD + bT * bT) * (X_START - aT * MU)
+    return abs(x - exact)
+
+
+def test_second_order_convergence():
+    e1 = {S: _chain_error(S, 1) for S in (10, 20, 40, 80)}
+    e2 = {S: _chain_error(S, 2) for S in (10, 20, 40, 80)}
+    for S in (10, 20, 40):
+        print(f"log-SNR S={S}: order-1 error {e1[S]:.3e}, order-2 error {e2[S]:.3e}, ratio {e1[S] / e2[S]:.2f}")
+        assert e1[S] / e2[S] >= 4, (S, e1[S] / e2[S])       # measured 7.4, 8.1, 15.6
+    print(f"order 2: error(S=20) / error(S=80) = {e2[20] / e2[80]:.2f}; order 1: {e1[20] / e1[80]:.2f}")
+    assert e2[20] / e2[80] >= 8                              # measured 15.0: second order over a 4x refinement
+    assert e1[20] / e1[80] <= 5                              # measured 3.9: first order - the test tells them apart
+    u100, u200 = _chain_error(100, 2, "uniform"), _chain_error(200, 2, "uniform")
+    print(f"uniform spacing, order 2: error(S=100) / error(S=200) = {u100 / u200:.2f}")
+    assert u100 / u200 >= 3                                  # measured 4.1
+
+
+# ------------------------------------------------------------------ 4. argument errors
+class _NoModel:
+    def eval(self):
+        raise AssertionError("the argument errors come before the model is touched")
+
+
+class _NoVAE:
+    def eval(self):
+        pass
+
+
+def _callers(fp):
+    """dpm_sample of every module (and the loop itself) as f(**kw) on a CPU device: the 'GPU only' error would be a
+    TdxError, not a ValueError, and must not be reached by a bad argument."""
+    from tiny_diffusion_amd import conditional_diffusion as C
+    from tiny_diffusion_amd import conditional_diffusion_laion as LA
+    from tiny_diffusion_amd import diffusion as D
+    from tiny_diffusion_amd import diffusion_transformer as DT
+    from tiny_diffusion_amd import latent_diffusion as LD
+    from tiny_diffusion_amd.schedule import dpm_sample_loop
+
+    y = torch.tensor([1, 2])
+    return {
+        "loop": lambda **kw: dpm_sample_loop(_NoModel(), fp, "cpu", 2, **kw),
+        "diffusion": lambda **kw: D.dpm_sample(_NoModel(), fp, "cpu", n_samples=2, **kw),
+        "conditional": lambda **kw: C.dpm_sample(_NoModel(), fp, "cpu", n_samples=2, y=y, **kw),
+        "laion": lambda **kw: LA.dpm_sample(_NoModel(), fp, "cpu", text_embeds=torch.zeros(2, 768), **kw),
+        "latent": lambda **kw: LD.dpm_sample(_NoVAE(), _NoModel(), fp, "cpu", n_samples=2, y=y, **kw),
+        "transformer": lambda **kw: DT.dpm_sample(_NoVAE(), _NoModel(), fp, "cpu", n_samples=2, y=y, **kw),
+    }
+
+
+BAD_ARGS = [(dict(steps=0), "steps"), (dict(steps=21), "steps"), (dict(steps=2.5), "steps"),
+            (dict(steps=0, spacing="uniform"), "steps"), (dict(order=3), "order"), (dict(order=None), "order"),
+            (dict(spacing="cosine"), "spacing"), (dict(timesteps=[4, 2]), "timesteps"),
+            (dict(timesteps=[0, 20]), "timesteps"), (dict(timesteps=[]), "timesteps"),
+            (dict(prediction="x0"), "prediction"), (dict(clip_denoised=(1, -1)), "clip_denoised"),
+            (dict(clip_denoised="yes", steps=0), "clip_denoised"),
+            (dict(noises={}), "noises"), (dict(guidance_scale=2.0), "guidance_scale")]
+
+
+@pytest.mark.parametrize("name", ["loop", "diffusion", "conditional", "laion", "latent", "transformer"])
+def test_dpm_sample_argument_errors_come_first(name):
+    from tiny_diffusion_amd import _lib
+
+    f = _callers(_fp(20))[name]
+    for kw, match in BAD_ARGS:
+        with pytest.raises(ValueError, match=match):   # _NoModel has no null condition: guidance is an error everywhere
+            f(**kw)
+    # accepted values reach the device check
+    for kw in (dict(), dict(steps=1), dict(steps=20, order=1, spacing="uniform"), dict(timesteps=[0, 5, 19]),
+               dict(clip_denoised=True, prediction="v"), dict(clip_denoised=None, philox_seed=3, use_graph=True)):
+        with pytest.raises(_lib.TdxError, match="GPU only"):
+            f(**kw)
+    assert issubclass(_lib.TdxError, RuntimeError) and not issubclass(_lib.TdxError, ValueError)
+
+
+def test_dpm_sample_keeps_the_modules_own_errors():
+    from tiny_diffusion_amd import conditional_diffusion as C
+    from tiny_diffusion_amd import conditional_diffusion_laion as LA
+    from tiny_diffusion_amd import diffusion_transformer as DT
+    from tiny_diffusion_amd import latent_diffusion as LD
+
+    fp = _fp(20)
+    with pytest.raises(ValueError, match="Class labels"):
+        C.dpm_sample(_NoModel(), fp, "cpu", n_samples=2)
+    with pytest.raises(ValueError, match="n_samples"):
+        C.dpm_sample(_NoModel(), fp, "cpu", n_samples=3, y=torch.tensor([1, 2]))
+    with pytest.raises(ValueError, match="Text embeddings"):
+        LA.dpm_sample(_NoModel(), fp, "cpu")
+    for mod in (LD, DT):
+        with pytest.raises(ValueError, match="Class labels"):
+            mod.dpm_sample(_NoVAE(), _NoModel(), fp, "cpu", n_samples=2)
+    for mod in (C, LA, LD, DT):
+        assert "dpm_sample" in mod.__all__
+
+
+def test_sample_loop_rejects_noises_with_a_multistep_schedule():
+    from tiny_diffusion_amd.schedule import dpm_solver_schedule, sample_loop
+
+    fp = _fp(20)
+    with pytest.raises(ValueError, match="noises"):
+        sample_loop(_NoModel(), fp, "cpu", 2, schedule=dpm_solver_schedule(fp, steps=5), noises={})
+
+
+# ------------------------------------------------------------------ 5. ABI
+def test_new_symbols_declared_listed_and_exported():
+    import tiny_diffusion_amd._lib as L
+
+    hdr = open(os.path.join(ROOT, "include", "tdx.h")).read()
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\b" + name + r"\s*\(", hdr), name
+        assert name in L.EXPORTS, name
+        assert getattr(L.lib, name).argtypes is not None, name   # bound: the library exports it
+    assert L.lib.tdx_version() == 400   # the ABI only grows

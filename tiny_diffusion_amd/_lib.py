@@ -198,6 +198,11 @@ _SIGS = {
     "tdx_unet_eval_step_x0": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, _ptr, _ptr, _ptr,
                                         _ptr, C.c_int64, _ptr, C.c_size_t, C.c_int, C.c_uint64, C.c_int, C.c_float,
                                         C.c_float, C.c_float, _ptr]),
+    "tdx_p_sample_step_ms": (C.c_int, [_ptr] * 6 + [C.c_int64, C.c_float, C.c_float, _ptr, _ptr]),
+    "tdx_p_sample_step_ms_guided": (C.c_int, [_ptr] * 5 + [C.c_int64, C.c_float, C.c_float, C.c_float, _ptr, _ptr]),
+    "tdx_unet_eval_step_ms": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, _ptr, _ptr, _ptr, _ptr,
+                                        C.c_int64, _ptr, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
+                                        _ptr, _ptr]),
     "tdx_cond_drop_labels": (C.c_int, [_ptr, _ptr, C.c_int, C.c_float, C.c_uint64, C.c_uint64, _ptr]),
     "tdx_cond_drop_rows": (C.c_int, [_ptr, _ptr, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, _ptr]),
     "tdx_timestep_embedding": (C.c_int, [_ptr, _ptr, C.c_int, C.c_int, _ptr]),

@@ -8,10 +8,10 @@ from typing import Optional
 
 import torch
 
-from .schedule import ForwardProcess, ddim_sample_loop, sample_loop
+from .schedule import ForwardProcess, ddim_sample_loop, dpm_sample_loop, sample_loop
 from .unet import NoiseModelBase, TIME_DIM
 
-__all__ = ["NoiseModel", "ForwardProcess", "sample", "ddim_sample"]
+__all__ = ["NoiseModel", "ForwardProcess", "sample", "ddim_sample", "dpm_sample"]
 
 
 class NoiseModel(NoiseModelBase):
@@ -46,6 +46,18 @@ def ddim_sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_sa
     _check_labels(y, n_samples)
     return ddim_sample_loop(noise_model, diffusion, device, n_samples, y, steps=steps, eta=eta, timesteps=timesteps,
                             guidance_scale=guidance_scale, **kw)
+
+
+@torch.no_grad()
+def dpm_sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples=16, y=None, steps=20, order=2,
+               spacing="logsnr", timesteps=None, guidance_scale: Optional[float] = None, **kw):
+    """DPM-Solver++(2M) sampling (Lu et al. 2022): ``sample()``'s contract and argument errors over ``steps`` timesteps uniform in
+    log-SNR (``spacing="uniform"``: DDIM's spacing) or the explicit list ``timesteps``, deterministic, second order
+    (``order=1``: deterministic DDIM), no retraining and one network evaluation per step (schedule.dpm_solver_schedule).
+    ``guidance_scale`` as in ``sample()``."""
+    _check_labels(y, n_samples)
+    return dpm_sample_loop(noise_model, diffusion, device, n_samples, y, steps=steps, order=order, spacing=spacing,
+                           timesteps=timesteps, guidance_scale=guidance_scale, **kw)
 
 
 def _check_labels(y, n_samples):

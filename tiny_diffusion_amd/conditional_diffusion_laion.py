@@ -14,10 +14,10 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .schedule import ForwardProcess as _ForwardProcess, ddim_sample_loop, sample_loop
+from .schedule import ForwardProcess as _ForwardProcess, ddim_sample_loop, dpm_sample_loop, sample_loop
 from .unet import ARCH_LAION, NoiseModelBase
 
-__all__ = ["NoiseModel", "ForwardProcess", "get_timestep_embedding", "sample", "ddim_sample", "postprocess_images"]
+__all__ = ["NoiseModel", "ForwardProcess", "get_timestep_embedding", "sample", "ddim_sample", "dpm_sample", "postprocess_images"]
 
 TIME_DIM = ARCH_LAION.time_dim
 
@@ -94,6 +94,22 @@ def ddim_sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, text
     n_samples = text_embeds.shape[0]
     x = ddim_sample_loop(noise_model, diffusion, device, n_samples, text_embeds, steps=steps, eta=eta,
                          timesteps=timesteps, guidance_scale=guidance_scale, **kw)
+    return _decode(x, vae, scaling_factor)
+
+
+@torch.no_grad()
+def dpm_sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, text_embeds=None, vae=None,
+               scaling_factor=1.0, steps=20, order=2, spacing="logsnr", timesteps=None,
+               guidance_scale: Optional[float] = None, **kw):
+    """DPM-Solver++(2M) sampling (Lu et al. 2022): ``sample()``'s contract, argument errors and decode over ``steps`` timesteps uniform in
+    log-SNR (``spacing="uniform"``: DDIM's spacing) or the explicit list ``timesteps``, deterministic, second order
+    (``order=1``: deterministic DDIM), no retraining and one network evaluation per step (schedule.dpm_solver_schedule).
+    ``guidance_scale`` as in ``sample()``."""
+    if text_embeds is None:
+        raise ValueError("Text embeddings must be provided for conditional generation.")
+    n_samples = text_embeds.shape[0]
+    x = dpm_sample_loop(noise_model, diffusion, device, n_samples, text_embeds, steps=steps, order=order,
+                        spacing=spacing, timesteps=timesteps, guidance_scale=guidance_scale, **kw)
     return _decode(x, vae, scaling_factor)
 
 

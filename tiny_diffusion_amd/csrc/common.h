@@ -78,6 +78,23 @@ __device__ static inline float p_step_x0(float x, float o, float z, float p, flo
   return __fadd_rn(__fadd_rn(__fmul_rn(A, x0c), __fmul_rn(Bx, x)), __fmul_rn(sg, z));
 }
 
+// The second-order multistep update (DPM-Solver++(2M), Lu et al. 2022) in the same x0 form, with the clamped x0 of the
+// step before as history:
+//   x0 = p*x + q*out;  x0c = min(max(x0, lo), hi);  x' = (A*x0c + Bx*x) + H*hprev
+// from a (p, q, A, Bx, H) row (schedule.py multistep_form); rounded operation by operation, in this order, like
+// p_step_x0.  H == 0 (the first and the last step, every step of order 1): the history term is not added and the
+// callers do not load hprev (H is uniform over a launch), so an uninitialised history buffer is harmless there.
+// *x0c_out is what the caller stores as the next step's history.
+__device__ static inline float p_step_ms(float x, float o, float hprev, float p, float q, float A, float Bx,
+                                         float H, float lo, float hi, float* x0c_out) {
+  const float x0 = __fadd_rn(__fmul_rn(p, x), __fmul_rn(q, o));
+  const float x0c = fminf(fmaxf(x0, lo), hi);
+  *x0c_out = x0c;
+  float r = __fadd_rn(__fmul_rn(A, x0c), __fmul_rn(Bx, x));
+  if (H != 0.0f) r = __fadd_rn(r, __fmul_rn(H, hprev));
+  return r;
+}
+
 // classifier-free guidance (Ho & Salimans 2021): eps_u + w (eps_c - eps_u), each operation rounded separately - the
 // one expression both guided updates evaluate (elementwise.hip, the epilogue of final_conv in edge_conv.hip)
 __device__ static inline float cfg_eps(float e_c, float e_u, float w) {

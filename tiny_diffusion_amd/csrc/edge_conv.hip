@@ -132,16 +132,22 @@ thin_to_fat_conv_kernel(const float* __restrict__ thin, const float* __restrict_
 // X0 = true (with PS; clipped-x0 sampling): the update is p_step_x0 from a (S,5) row (p, q, A, Bx, sigma) and the bounds
 // lo / hi - the arithmetic of p_sample_x0_kernel / p_sample_x0_guided_kernel, bit for bit.  A template parameter: the
 // X0 = false instantiations carry no trace of it.
+// MS = true (with PS; the multistep sampler): the update is p_step_ms from a (S,5) row (p, q, A, Bx, H) against the
+// history ps.hist (the clamped x0 of the step before, one value per element of the unguided batch / the first half),
+// which the same lane overwrites with this step's clamped x0; no noise.  The arithmetic of p_sample_ms_kernel /
+// p_sample_ms_guided_kernel, bit for bit; again a template parameter that the other instantiations do not see.
 struct PSampleOps {
   float* x; const float* z; const float* coef; const int32_t* t_idx; uint64_t seed; int philox; int64_t* counter_dec;
   int64_t elem0;   // index of this launch's first element in the whole batch (a half-batch launch keeps the batch's Philox stream)
   const int64_t* tau;   // timestep schedule (DDIM): *t_idx is the step index k, the Philox stream tau[k]; null: identity
   float w;              // GD: guidance scale
   int64_t half;         // GD: elements of one half of x / out (the twin of element idx is idx + half)
-  int x0;               // table kind: 0 = (S,3) rows (c1, c2, sigma) of p_step, 1 = (S,5) rows of p_step_x0 (the X0 kernels)
-  float lo, hi;         // X0: the clamp of the implied x0
+  int x0;               // table kind: 0 = (S,3) rows (c1, c2, sigma) of p_step, 1 = (S,5) rows of p_step_x0 (the X0 kernels),
+                        // 2 = (S,5) rows (p, q, A, Bx, H) of p_step_ms (the MS kernels)
+  float lo, hi;         // X0 / MS: the clamp of the implied x0
+  float* hist;          // MS: the history, indexed by the element's index in the whole batch (idx + elem0)
 };
-template <int CO, bool DGRAD, bool PS, typename TF, bool GD = false, bool X0 = false>
+template <int CO, bool DGRAD, bool PS, typename TF, bool GD = false, bool X0 = false, bool MS = false>
 __global__ void __launch_bounds__(256)
 fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
                         const float* __restrict__ bias, float* __restrict__ out, int B, int H, int W, int cor,
@@ -169,11 +175,11 @@ fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
   int ps_t = 0;
   uint64_t ps_nt = 0;
   float ps_c1 = 0.f, ps_c2 = 0.f, ps_sg = 0.f;
-  float ps_p = 0.f, ps_q = 0.f;   // X0: the row is (p, q, A = ps_c1, Bx = ps_c2, sigma)
+  float ps_p = 0.f, ps_q = 0.f;   // X0: the row is (p, q, A = ps_c1, Bx = ps_c2, sigma); MS: (p, q, A, Bx, H = ps_sg)
   if (PS) {
     ps_t = *ps.t_idx;
     ps_nt = ps.tau ? (uint64_t)ps.tau[ps_t] : (uint64_t)ps_t;
-    if (X0) {
+    if (X0 || MS) {
       ps_p = ps.coef[5 * ps_t + 0]; ps_q = ps.coef[5 * ps_t + 1];
       ps_c1 = ps.coef[5 * ps_t + 2]; ps_c2 = ps.coef[5 * ps_t + 3]; ps_sg = ps.coef[5 * ps_t + 4];
     } else {
@@ -243,7 +249,7 @@ fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
         out[idx] = e;
         if (PS) {
           float zv = 0.f;   // diffusion.py:267-270: no noise on the last step
-          if (ps_t > 0) {
+          if (!MS && ps_t > 0) {
             if (ps.philox) {   // element idx = component idx % 4 of block idx / 4 (p_sample_kernel<true>)
               const int64_t gidx = idx + ps.elem0;
               const float4 z4 = philox_normal4((uint64_t)(gidx >> 2), ps_nt, ps.seed);
@@ -253,7 +259,20 @@ fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
               zv = ps.z[idx];
             }
           }
-          if (GD) {
+          if (MS) {   // deterministic: the history in the place of the noise
+            float eg = e, x0c;
+            if (GD) {
+              const float eu = s2[co] + bv[co];
+              out[idx + ps.half] = eu;
+              eg = cfg_eps(e, eu, ps.w);
+            }
+            float* hp = ps.hist + idx + ps.elem0;
+            const float hv = ps_sg != 0.0f ? *hp : 0.f;
+            const float xn = p_step_ms(ps.x[idx], eg, hv, ps_p, ps_q, ps_c1, ps_c2, ps_sg, ps.lo, ps.hi, &x0c);
+            ps.x[idx] = xn;
+            if (GD) ps.x[idx + ps.half] = xn;
+            *hp = x0c;
+          } else if (GD) {
             const float eu = s2[co] + bv[co];
             out[idx + ps.half] = eu;
             const float eg = cfg_eps(e, eu, ps.w);
@@ -549,14 +568,28 @@ int tdx_initial_conv_dgrad(const void* g_x0, const float* w, float* g_x, int B, 
 int tdx_final_conv_fwd_psample(const void* in, const float* w, const float* bias, float* eps_out, int B, int H, int W,
                                int cout, float* x, const float* z, const float* coef, const int32_t* t_idx,
                                uint64_t seed, int philox, int64_t* counter_dec, hipStream_t st, int io16, int64_t elem0,
-                               const int64_t* tau, int guided, float gw, int x0, float lo, float hi) {
+                               const int64_t* tau, int guided, float gw, int x0, float lo, float hi, float* hist) {
   if (!x || !coef || !t_idx || (elem0 & 3)) return TDX_E_BADARG;
   if (x0 && !(lo < hi)) return TDX_E_BADARG;
+  if (x0 < 0 || x0 > 2 || (x0 == 2 && !hist)) return TDX_E_BADARG;
   if (guided && ((B & 1) || elem0)) return TDX_E_BADARG;   // two equal halves, the whole batch in one launch
   const int64_t M = (int64_t)(guided ? B / 2 : B) * H * W;
   const int grid = (int)std::min<int64_t>((M + 15) / 16, 8192);
-  const PSampleOps ps{x, z, coef, t_idx, seed, philox, counter_dec, elem0, tau, gw, guided ? M * cout : 0, x0, lo, hi};
+  const PSampleOps ps{x, z, coef, t_idx, seed, philox, counter_dec, elem0, tau, gw, guided ? M * cout : 0, x0, lo, hi, hist};
   if (cout != 1 && cout != 4) return TDX_E_SHAPE;
+  if (x0 == 2) {   // the multistep variants: the (S,5) table (p, q, A, Bx, H) and the history
+    if (guided) {
+      TDX_IO_DISPATCH(io16, T,
+        if (cout == 1) fat_to_thin_conv_kernel<1, false, true, T, true, false, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps);
+        else fat_to_thin_conv_kernel<4, false, true, T, true, false, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps));
+    } else {
+      TDX_IO_DISPATCH(io16, T,
+        if (cout == 1) fat_to_thin_conv_kernel<1, false, true, T, false, false, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps);
+        else fat_to_thin_conv_kernel<4, false, true, T, false, false, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps));
+    }
+    TDX_CHECK_LAUNCH();
+    return 0;
+  }
   if (x0) {   // the clipped-x0 variants: the (S,5) table
     if (guided) {
       TDX_IO_DISPATCH(io16, T,

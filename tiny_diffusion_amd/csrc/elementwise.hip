@@ -392,6 +392,85 @@ extern "C" int tdx_p_sample_step_x0_guided(float* x, const float* out, const flo
   return 0;
 }
 
+// ------------------------------------------------------------- p_sample step, multistep (DPM-Solver++(2M))
+// x' = p_step_ms(x, out, hist, row t of the (S,5) table (p, q, A, Bx, H), lo, hi) and hist <- the clamped x0, in one
+// pass (common.h; the boundary convolution fuses the same update into its epilogue).  Deterministic: no noise, so no
+// tau.  H is uniform over the launch: at H == 0 the history is not loaded at all (the first step's buffer may hold
+// anything).  An element's history is read and written by the same thread, as x is when xo aliases it.
+__device__ __forceinline__ float4 p_step_ms_4(const float4 x, const float4 o, const float4 h, float p, float q, float A,
+                                              float Bx, float H, float lo, float hi, float4* x0c) {
+  float4 r;
+  r.x = p_step_ms(x.x, o.x, h.x, p, q, A, Bx, H, lo, hi, &x0c->x);
+  r.y = p_step_ms(x.y, o.y, h.y, p, q, A, Bx, H, lo, hi, &x0c->y);
+  r.z = p_step_ms(x.z, o.z, h.z, p, q, A, Bx, H, lo, hi, &x0c->z);
+  r.w = p_step_ms(x.w, o.w, h.w, p, q, A, Bx, H, lo, hi, &x0c->w);
+  return r;
+}
+
+__global__ void p_sample_ms_kernel(float4* xo, const float4* x,  // may alias: in-place update
+                                   const float4* __restrict__ out, float4* hist, const float* __restrict__ coef,
+                                   const int32_t* __restrict__ t_idx, int64_t n4, float lo, float hi,
+                                   int64_t* counter_dec) {
+  const int t = *t_idx;
+  if (counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *counter_dec = (int64_t)t - 1;
+  const float p = coef[5 * t + 0], q = coef[5 * t + 1], A = coef[5 * t + 2], Bx = coef[5 * t + 3], H = coef[5 * t + 4];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 xv = x[i], ov = out[i];
+    float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), x0c;
+    if (H != 0.0f) hv = hist[i];
+    xo[i] = p_step_ms_4(xv, ov, hv, p, q, A, Bx, H, lo, hi, &x0c);
+    hist[i] = x0c;
+  }
+}
+
+// Guided: the layout of p_sample_guided_kernel; the two outputs are combined first (cfg_eps), the multistep update is
+// applied to the combination against ONE history of n4 float4 (the two halves of x are equal), written to both halves.
+__global__ void p_sample_ms_guided_kernel(float4* x, const float4* __restrict__ out, float4* hist,
+                                          const float* __restrict__ coef, const int32_t* __restrict__ t_idx,
+                                          int64_t n4, float w, float lo, float hi, int64_t* counter_dec) {
+  const int t = *t_idx;
+  if (counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *counter_dec = (int64_t)t - 1;
+  const float p = coef[5 * t + 0], q = coef[5 * t + 1], A = coef[5 * t + 2], Bx = coef[5 * t + 3], H = coef[5 * t + 4];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 xv = x[i], oc = out[i], ou = out[i + n4];
+    float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), x0c, e;
+    if (H != 0.0f) hv = hist[i];
+    e.x = cfg_eps(oc.x, ou.x, w);
+    e.y = cfg_eps(oc.y, ou.y, w);
+    e.z = cfg_eps(oc.z, ou.z, w);
+    e.w = cfg_eps(oc.w, ou.w, w);
+    const float4 o = p_step_ms_4(xv, e, hv, p, q, A, Bx, H, lo, hi, &x0c);
+    x[i] = o;
+    x[i + n4] = o;
+    hist[i] = x0c;
+  }
+}
+
+// counter_dec null or the table-mode step counter.  !(lo < hi) - a NaN included - is a bad argument; infinite bounds
+// never bind (no clipping).  hist: n floats, read only when the row's H != 0, always written.
+extern "C" int tdx_p_sample_step_ms(float* x_out, const float* x, const float* out, float* hist, const float* coef5,
+                                    const int32_t* t_idx, int64_t n, float lo, float hi, int64_t* counter_dec,
+                                    tdx_stream_t stream) {
+  if (!x_out || !x || !out || !hist || !coef5 || !t_idx || n <= 0 || (n % 4) || !(lo < hi)) return TDX_E_BADARG;
+  p_sample_ms_kernel<<<ew_grid(n / 4, 256), 256, 0, to_stream(stream)>>>(
+      (float4*)x_out, (const float4*)x, (const float4*)out, (float4*)hist, coef5, t_idx, n / 4, lo, hi, counter_dec);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tdx_p_sample_step_ms_guided(float* x, const float* out, float* hist, const float* coef5,
+                                           const int32_t* t_idx, int64_t n_half_elems, float w, float lo, float hi,
+                                           int64_t* counter_dec, tdx_stream_t stream) {
+  if (!x || !out || !hist || !coef5 || !t_idx || n_half_elems <= 0 || (n_half_elems % 4) || !(lo < hi))
+    return TDX_E_BADARG;
+  p_sample_ms_guided_kernel<<<ew_grid(n_half_elems / 4, 256), 256, 0, to_stream(stream)>>>(
+      (float4*)x, (const float4*)out, (float4*)hist, coef5, t_idx, n_half_elems / 4, w, lo, hi, counter_dec);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
 // Device-side step counter for graph-captured sampling: t = *counter; t_idx = t; t_vec[:] = t;
 // *counter = t - 1.  One block; lets a HIP graph hold several consecutive reverse steps with no
 // host work between them (diffusion.py:259-260 builds the same t tensor on the host each step).

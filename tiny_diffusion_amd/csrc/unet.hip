@@ -229,7 +229,7 @@ struct tdx_unet {
   const int64_t* tab_tau;   // timestep schedule the T rows were built at (tdx_unet_prepare_sampling_sched); null: t = 0..T-1
   bool skip_time_path;   // set by tdx_unet_eval_step around its forward: the projections are already in the workspace
   // set by tdx_unet_eval_step around its forward: final_conv applies the reverse-process update in its epilogue
-  struct PS { float* x; const float* z; const float* coef; const int32_t* t_idx; uint64_t seed; int philox; int64_t* counter_dec; int64_t elem0; const int64_t* tau; int guided; float w; int x0; float lo, hi; } ps;   // x0: coef is the (S,5) table of the clipped-x0 update, lo / hi its clamp
+  struct PS { float* x; const float* z; const float* coef; const int32_t* t_idx; uint64_t seed; int philox; int64_t* counter_dec; int64_t elem0; const int64_t* tau; int guided; float w; int x0; float lo, hi; float* hist; } ps;   // x0: 1 = coef is the (S,5) table of the clipped-x0 update, lo / hi its clamp; 2 = the multistep table, hist its history
   bool whole_batch;      // set by a guided eval step around its forward: the two halves of a guided batch are not the halves of "sample_halves"
   // half-batch inference (tdx_unet_forward, INFER mode): the second half runs on this stream, forked from / joined to the caller's
   hipStream_t half_own;
@@ -931,7 +931,7 @@ static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const
   if (infer && ps.x)
     RC(tdx_final_conv_fwd_psample(ws + L.d1a, P[TDX_P_FINAL_W], P[TDX_P_FINAL_B], out, B, S.out_hw, S.out_hw, S.in_ch,
                                   ps.x, ps.z, ps.coef, ps.t_idx, ps.seed, ps.philox, ps.counter_dec, st, io16, ps.elem0,
-                                  ps.tau, ps.guided, ps.w, ps.x0, ps.lo, ps.hi));
+                                  ps.tau, ps.guided, ps.w, ps.x0, ps.lo, ps.hi, ps.hist));
   else
     RC(tdx_final_conv_fwd(ws + L.d1a, P[TDX_P_FINAL_W], P[TDX_P_FINAL_B], out, B, S.out_hw, S.out_hw, S.in_ch, st, io16));
 
@@ -1289,15 +1289,18 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
 // guided (tdx_unet_eval_step_guided): batch = 2n rows of x, the second half under the null condition, n_elems the first
 // half's; the update combines the two predictions with scale w and writes both halves (z: n rows).
 // x0 (tdx_unet_eval_step_x0): coef is the (S,5) table of the clipped-x0 update and lo / hi its clamp; the head, the
-// counter and the half-batch logic do not know the difference.
+// counter and the half-batch logic do not know the difference.  x0 == 2 (tdx_unet_eval_step_ms): the (S,5) table of
+// the multistep update and its history hist (z is null: the chain is deterministic); a half-batch launch indexes the
+// one history by the element's place in the whole batch (PS::elem0).
 static int eval_step_impl(tdx_unet* u, const void* const* params, void* const* buffers, float* x, const void* cond,
                           const float* z, const float* coef, const int64_t* tau, int n_steps, int64_t* counter, int32_t* t_idx,
                           int64_t* t_vec, float* eps, int64_t n_elems, void* workspace, size_t workspace_bytes,
                           int batch, uint64_t philox_seed, tdx_stream_t stream, bool guided = false, float w = 0.f,
-                          bool x0 = false, float lo = 0.f, float hi = 0.f) {
+                          int x0 = 0, float lo = 0.f, float hi = 0.f, float* hist = nullptr) {
   if (!u || !x || !coef || !counter || !t_idx || !t_vec || !eps || batch <= 0 || n_elems <= 0)
     return TDX_E_BADARG;
   if (x0 && !(lo < hi)) return TDX_E_BADARG;
+  if (x0 == 2 && (!hist || z)) return TDX_E_BADARG;
   if (guided) {
     if (!u->spec) return TDX_E_SHAPE;   // the UNets only
     if ((batch & 1) || 2 * n_elems != (int64_t)batch * u->spec->in_ch * u->spec->out_hw * u->spec->out_hw) return TDX_E_BADARG;
@@ -1341,7 +1344,7 @@ static int eval_step_impl(tdx_unet* u, const void* const* params, void* const* b
   // the UNets apply the update in final_conv's epilogue (one launch less); the latent MLP keeps the separate kernel
   const bool fuse_ps = u->spec && (g_tdx_sample_fuse & 4) &&
                        (guided ? 2 : 1) * n_elems == (int64_t)batch * u->spec->in_ch * u->spec->out_hw * u->spec->out_hw;
-  if (fuse_ps) u->ps = {x, z, coef, t_idx, philox_seed, z ? 0 : 1, tab ? counter : nullptr, 0, tau, guided, w, x0, lo, hi};
+  if (fuse_ps) u->ps = {x, z, coef, t_idx, philox_seed, z ? 0 : 1, tab ? counter : nullptr, 0, tau, guided, w, x0, lo, hi, hist};
   const int rc = tdx_unet_forward(u, params, buffers, x, t_vec, cond, eps, workspace, workspace_bytes, batch,
                                   TDX_MODE_INFER, stream);
   u->skip_time_path = false;
@@ -1349,6 +1352,11 @@ static int eval_step_impl(tdx_unet* u, const void* const* params, void* const* b
   u->ps = {};
   if (rc) return rc;
   if (fuse_ps) return 0;
+  if (x0 == 2) {
+    if (guided)
+      return tdx_p_sample_step_ms_guided(x, eps, hist, coef, t_idx, n_elems, w, lo, hi, tab ? counter : nullptr, stream);
+    return tdx_p_sample_step_ms(x, x, eps, hist, coef, t_idx, n_elems, lo, hi, tab ? counter : nullptr, stream);
+  }
   if (x0) {
     if (guided)
       return tdx_p_sample_step_x0_guided(x, eps, z, coef, tau, t_idx, n_elems, w, lo, hi, z ? 0 : 1, philox_seed,
@@ -1412,7 +1420,21 @@ extern "C" int tdx_unet_eval_step_x0(tdx_unet* u, const void* const* params, voi
                                      int guided, float w, float lo, float hi, tdx_stream_t stream) {
   if (tau && S <= 0) return TDX_E_BADARG;
   return eval_step_impl(u, params, buffers, x, cond, z, coef5, tau, tau ? S : 0, counter, t_idx, t_vec, eps, n_elems,
-                        workspace, workspace_bytes, batch, philox_seed, stream, guided != 0, w, true, lo, hi);
+                        workspace, workspace_bytes, batch, philox_seed, stream, guided != 0, w, 1, lo, hi);
+}
+
+// The multistep step (DPM-Solver++(2M), see tdx_p_sample_step_ms): tdx_unet_eval_step_x0's arguments without the noise
+// (no z, no seed: the chain is deterministic) plus the history hist - n_elems floats that the caller keeps from step to
+// step, read only when the row's H != 0.  coef5 is the (S,5) table (p, q, A, Bx, H).  The update runs in final_conv's
+// epilogue, or in tdx_p_sample_step_ms{,_guided} when the epilogue is switched off and for the latent MLP.
+extern "C" int tdx_unet_eval_step_ms(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
+                                     const void* cond, const float* coef5, const int64_t* tau, int S, int64_t* counter,
+                                     int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems, void* workspace,
+                                     size_t workspace_bytes, int batch, int guided, float w, float lo, float hi,
+                                     float* hist, tdx_stream_t stream) {
+  if ((tau && S <= 0) || !hist) return TDX_E_BADARG;
+  return eval_step_impl(u, params, buffers, x, cond, nullptr, coef5, tau, tau ? S : 0, counter, t_idx, t_vec, eps,
+                        n_elems, workspace, workspace_bytes, batch, 0, stream, guided != 0, w, 2, lo, hi, hist);
 }
 
 // Build the sampling tables for the CURRENT INFER pack (call after tdx_unet_pack / the first INFER forward, once

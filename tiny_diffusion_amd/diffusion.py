@@ -5,10 +5,10 @@ from __future__ import annotations
 
 import torch
 
-from .schedule import ForwardProcess, ddim_sample_loop, sample_loop
+from .schedule import ForwardProcess, ddim_sample_loop, dpm_sample_loop, sample_loop
 from .unet import NoiseModelBase, TIME_DIM
 
-__all__ = ["NoiseModel", "ForwardProcess", "sample", "ddim_sample"]
+__all__ = ["NoiseModel", "ForwardProcess", "sample", "ddim_sample", "dpm_sample"]
 
 
 class NoiseModel(NoiseModelBase):
@@ -38,3 +38,14 @@ def ddim_sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_sa
     The same extension keywords as ``sample()``."""
     return ddim_sample_loop(noise_model, diffusion, device, n_samples, None, steps=steps, eta=eta,
                             timesteps=timesteps, **kw)
+
+
+@torch.no_grad()
+def dpm_sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples=16, steps=20, order=2,
+               spacing="logsnr", timesteps=None, **kw):
+    """DPM-Solver++(2M) sampling (Lu et al. 2022): ``sample()``'s contract over ``steps`` timesteps uniform in
+    log-SNR (``spacing="uniform"``: DDIM's spacing) or the explicit list ``timesteps``, deterministic, second order
+    (``order=1``: deterministic DDIM), no retraining and one network evaluation per step (schedule.dpm_solver_schedule).
+    The extension keywords of ``sample()`` except ``noises``; ``philox_seed`` only selects the graph mode."""
+    return dpm_sample_loop(noise_model, diffusion, device, n_samples, None, steps=steps, order=order, spacing=spacing,
+                           timesteps=timesteps, **kw)

@@ -16,10 +16,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .schedule import ForwardProcess, ddim_sample_loop, sample_loop
+from .schedule import ForwardProcess, ddim_sample_loop, dpm_sample_loop, sample_loop
 from .vae import VAE, VAEConfig
 
-__all__ = ["TransformerBlock", "NoiseModel", "ForwardProcess", "sample", "ddim_sample", "VAE", "VAEConfig"]
+__all__ = ["TransformerBlock", "NoiseModel", "ForwardProcess", "sample", "ddim_sample", "dpm_sample", "VAE", "VAEConfig"]
 
 
 class TransformerBlock(nn.Module):
@@ -133,6 +133,20 @@ def ddim_sample(vae: VAE, noise_model: NoiseModel, diffusion: ForwardProcess, de
     _check_labels(y, n_samples)
     vae.eval()
     z = ddim_sample_loop(noise_model, diffusion, device, n_samples, y, steps=steps, eta=eta, timesteps=timesteps, **kw)
+    return vae.decode(z).view(-1, 1, 28, 28)
+
+
+@torch.no_grad()
+def dpm_sample(vae: VAE, noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples=16, y=None, steps=20,
+               order=2, spacing="logsnr", timesteps=None, **kw):
+    """DPM-Solver++(2M) sampling (Lu et al. 2022): ``sample()``'s contract, argument errors and VAE decode over ``steps`` timesteps uniform in
+    log-SNR (``spacing="uniform"``: DDIM's spacing) or the explicit list ``timesteps``, deterministic, second order
+    (``order=1``: deterministic DDIM), no retraining and one network evaluation per step (schedule.dpm_solver_schedule).
+    The extension keywords of ``sample()`` except ``noises``."""
+    _check_labels(y, n_samples)
+    vae.eval()
+    z = dpm_sample_loop(noise_model, diffusion, device, n_samples, y, steps=steps, order=order, spacing=spacing,
+                        timesteps=timesteps, **kw)
     return vae.decode(z).view(-1, 1, 28, 28)
 
 

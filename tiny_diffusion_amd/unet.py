@@ -551,18 +551,26 @@ class NoiseModelBase(nn.Module):
         return plan, pptr, bptr, st
 
     def _run_eval_step(self, x, y, coef, counter, t_idx, t_vec, eps, z=None, philox_seed: int = 0, tau=None,
-                       S: int = 0, guidance_scale: Optional[float] = None, clip=None):
+                       S: int = 0, guidance_scale: Optional[float] = None, clip=None, hist=None):
         """One reverse step of sample() in place on ``x`` (tdx_unet_eval_step): the step index is
         read from and decremented in device memory, so the call can sit in a HIP graph.  ``tau``: the
         device timesteps of a schedule of ``S`` steps (tdx_unet_eval_step_sched; ``coef`` is then (S,3)).
         ``guidance_scale``: the guided step (tdx_unet_eval_step_guided) - ``x``, ``y`` and ``eps`` hold 2n rows, the
         second half under the null condition, ``z`` n rows.  ``clip=(lo, hi)``: the clipped-x0 step
-        (tdx_unet_eval_step_x0), guided or not - ``coef`` is then the (S,5) table of ``TimestepSchedule.x0_form``."""
+        (tdx_unet_eval_step_x0), guided or not - ``coef`` is then the (S,5) table of ``TimestepSchedule.x0_form``.
+        ``hist`` (with ``clip``, infinite bounds for none): the multistep step (tdx_unet_eval_step_ms) against that
+        history buffer - ``coef`` is the (S,5) table of ``MultistepSchedule.multistep_form``; no ``z``, no seed."""
         plan, pptr, bptr, st = self._plan_ptrs(x)
         head = (plan.handle, pptr, bptr, x.data_ptr(), _dptr(y), _dptr(z), coef.data_ptr())
         rest = (counter.data_ptr(), t_idx.data_ptr(), t_vec.data_ptr(), eps.data_ptr(), x.numel(),
                 plan.workspace.data_ptr(), plan.ws_bytes, x.shape[0], philox_seed, st)
-        if clip is not None:
+        if hist is not None:
+            g = guidance_scale is not None
+            check(lib.tdx_unet_eval_step_ms(*head[:5], coef.data_ptr(), _dptr(tau), int(S), *rest[:4],
+                                            x.numel() // 2 if g else x.numel(), *rest[5:8], int(g),
+                                            float(guidance_scale) if g else 0.0, float(clip[0]), float(clip[1]),
+                                            hist.data_ptr(), st), "tdx_unet_eval_step_ms")
+        elif clip is not None:
             g = guidance_scale is not None
             rest = rest[:4] + (x.numel() // 2 if g else x.numel(),) + rest[5:-1] \
                 + (int(g), float(guidance_scale) if g else 0.0, float(clip[0]), float(clip[1]), st)
