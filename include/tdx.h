@@ -518,6 +518,36 @@ int tdx_vae_reparameterize(const float* mu, const float* logvar, const float* ep
  * sigmoid output (B,input_dim). */
 int tdx_vae_decode(const float* z, const void* const* params, float* out, float* workspace,
                    int batch, int input_dim, int hidden_dim, int latent_dim, tdx_stream_t stream);
+/* VAE training (vae.py:70-76, 104-115).  Both loss sums are deterministic: a fixed element -> block map, double
+ * partials, one finish launch (scratch: tdx_vae_loss_scratch_bytes() bytes, 8-byte aligned).
+ * BCE from the decoder's LOGITS (fc4 without its sigmoid) against target = (x + 1) / 2, x in [-1, 1], sum-reduced:
+ *   BCE_i = max(a, 0) - a target + log1p(exp(-|a|));  d_logits_i = gscale (sigmoid(a) - target);  recon_i = sigmoid(a)
+ * d_logits and recon may be null.  Equals F.binary_cross_entropy(sigmoid(a), target, reduction="sum") wherever
+ * torch's clamp log >= -100 does not bind, and stays exact where the fp32 sigmoid saturates. */
+size_t tdx_vae_loss_scratch_bytes(void);
+int tdx_vae_bce_logits_grad(const float* logits, const float* x, float* loss_out, float* d_logits, float* recon,
+                            float gscale, int64_t n, void* scratch, tdx_stream_t stream);
+/* kld_out = -0.5 sum (1 + logvar - mu^2 - exp(logvar)) (unweighted) and, when g_z (the decoder's gradient w.r.t. z =
+ * mu + eps exp(0.5 logvar)) is given:  g_mu = g_z + kld_weight mu,
+ * g_logvar = 0.5 g_z eps exp(0.5 logvar) + 0.5 kld_weight (exp(logvar) - 1).  g_z == NULL: the sum only. */
+int tdx_vae_kld_reparam_bwd(const float* mu, const float* logvar, const float* eps, const float* g_z, float* kld_out,
+                            float* g_mu, float* g_logvar, float kld_weight, int64_t n, void* scratch,
+                            tdx_stream_t stream);
+/* tdx_vae_reparameterize with eps drawn in the kernel: element i takes lane i % 4 of the Philox block
+ * (counter i / 4, stream `offset`, key `seed`); the drawn eps is written to eps_out. */
+int tdx_vae_reparameterize_philox(const float* mu, const float* logvar, float* z, float* eps_out, int64_t n,
+                                  uint64_t seed, uint64_t offset, tdx_stream_t stream);
+/* One call = VAE.forward + loss_function + loss.backward() (vae.py:111-113).  params / grads: {fc1.w, fc1.b, fc21.w,
+ * fc21.b, fc22.w, fc22.b, fc3.w, fc3.b, fc4.w, fc4.b}; every gradient is written, not accumulated; grads == NULL:
+ * forward and losses only.  eps (B,latent_dim), or NULL: drawn from Philox (seed, offset).  out3 (device) =
+ * {BCE + kld_weight KLD, BCE, KLD}; the gradients are those of gscale * out3[0].  workspace:
+ * tdx_vae_train_workspace_floats() floats, at least 8-byte aligned (it holds the loss scratch: double partials at an
+ * offset that is a multiple of 256 bytes; TDX_E_BADARG otherwise - 16-byte alignment lets every kernel use its
+ * vector loads).  No allocation, no host sync: capturable. */
+size_t tdx_vae_train_workspace_floats(int batch, int input_dim, int hidden_dim, int latent_dim);
+int tdx_vae_loss_grads(const float* x, const void* const* params, void* const* grads, const float* eps, uint64_t seed,
+                       uint64_t offset, float kld_weight, float gscale, float* out3, float* workspace, int batch,
+                       int input_dim, int hidden_dim, int latent_dim, tdx_stream_t stream);
 
 /* ---- row / elementwise blocks of the "transformer" noise model (diffusion_transformer.py:16-107;
  * its attention runs on a length-1 sequence, i.e. it is out_proj(v_proj(x))) -------------------

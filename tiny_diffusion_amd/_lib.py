@@ -148,6 +148,13 @@ _SIGS = {
     "tdx_vae_encode": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, C.c_int, C.c_int, C.c_int, _ptr]),
     "tdx_vae_reparameterize": (C.c_int, [_ptr, _ptr, _ptr, _ptr, C.c_int64, _ptr]),
     "tdx_vae_decode": (C.c_int, [_ptr, _ptr, _ptr, _ptr, C.c_int, C.c_int, C.c_int, C.c_int, _ptr]),
+    "tdx_vae_loss_scratch_bytes": (C.c_size_t, []),
+    "tdx_vae_bce_logits_grad": (C.c_int, [_ptr] * 5 + [C.c_float, C.c_int64, _ptr, _ptr]),
+    "tdx_vae_kld_reparam_bwd": (C.c_int, [_ptr] * 7 + [C.c_float, C.c_int64, _ptr, _ptr]),
+    "tdx_vae_reparameterize_philox": (C.c_int, [_ptr] * 4 + [C.c_int64, C.c_uint64, C.c_uint64, _ptr]),
+    "tdx_vae_train_workspace_floats": (C.c_size_t, [C.c_int] * 4),
+    "tdx_vae_loss_grads": (C.c_int, [_ptr] * 4 + [C.c_uint64, C.c_uint64, C.c_float, C.c_float, _ptr, _ptr]
+                           + [C.c_int] * 4 + [_ptr]),
     "tdx_layernorm_fwd": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, C.c_int, C.c_float, _ptr]),
     "tdx_layernorm_bwd": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, C.c_int, _ptr]),
     "tdx_act_fwd": (C.c_int, [_ptr, _ptr, C.c_int64, C.c_int, _ptr]),

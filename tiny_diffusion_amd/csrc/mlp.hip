@@ -834,6 +834,322 @@ extern "C" int tdx_vae_decode(const float* z, const void* const* params, float* 
 }
 
 // ------------------------------------------------------------------------------------------
+// VAE training (vae.py:70-76, 104-115): the sum-reduced BCE + KLD loss, its gradient and the backward of
+// the five Linear layers.  Elementwise / reduction kernels on at most B x 784 floats; like everything in
+// this file the cost is the length of the launch chain.  Both loss sums use the reduction of
+// mse_loss_grad_kernel (elementwise.hip): a fixed grid, a fixed element -> block map, one double partial per
+// block and a one-block finish that adds them in a fixed order, so the loss is bit-reproducible.
+namespace {
+
+constexpr int VAE_LOSS_BLOCKS = 512;   // double partials per loss term
+
+__device__ inline void block_dsum_store(double s, double* red, double* dst) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    long long v = __double_as_longlong(s);
+    int lo = __shfl_xor((int)(v & 0xffffffffll), o, 64);
+    int hi = __shfl_xor((int)(v >> 32), o, 64);
+    s += __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+  }
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) *dst = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// One element of the BCE from the logit a and the image value x in [-1, 1] (target t = (x + 1) / 2, vae.py:73):
+//   BCE = max(a, 0) - a t + log1p(exp(-|a|)),   dBCE/da = sigmoid(a) - t
+// exp / log1p / the division are fp32; the target, the product a t and the two differences are formed in double
+// from the fp32 operands (exact), because a t cancels against max(a, 0) where the decoder is confident.
+struct BceElem { double term; float d, r; };
+__device__ inline BceElem bce_elem(float a, float x, float gscale) {
+  const float e = expf(-fabsf(a));
+  const float r = 1.0f / (1.0f + e);
+  const float s = a >= 0.f ? r : e * r;            // sigmoid(a) without overflow on either side
+  const double t = ((double)x + 1.0) * 0.5;
+  BceElem o;
+  o.r = s;
+  o.d = gscale * (float)((double)s - t);
+  o.term = ((double)fmaxf(a, 0.f) - (double)a * t) + (double)log1pf(e);
+  return o;
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+vae_bce_logits_grad_kernel(const float* __restrict__ a, const float* __restrict__ x, float* __restrict__ d_a,
+                           float* __restrict__ recon, float gscale, int64_t n, double* __restrict__ partials) {
+  __shared__ double red[4];
+  const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t n4 = VEC ? n >> 2 : 0;   // float4 body, then the scalar tail (n need not be a multiple of 4)
+  double s = 0.0;
+  for (int64_t i = gtid; i < n4; i += stride) {
+    const float4 av = reinterpret_cast<const float4*>(a)[i], xv = reinterpret_cast<const float4*>(x)[i];
+    const BceElem e0 = bce_elem(av.x, xv.x, gscale), e1 = bce_elem(av.y, xv.y, gscale);
+    const BceElem e2 = bce_elem(av.z, xv.z, gscale), e3 = bce_elem(av.w, xv.w, gscale);
+    s += e0.term;
+    s += e1.term;
+    s += e2.term;
+    s += e3.term;
+    if (d_a) reinterpret_cast<float4*>(d_a)[i] = make_float4(e0.d, e1.d, e2.d, e3.d);
+    if (recon) reinterpret_cast<float4*>(recon)[i] = make_float4(e0.r, e1.r, e2.r, e3.r);
+  }
+  for (int64_t i = 4 * n4 + gtid; i < n; i += stride) {
+    const BceElem e = bce_elem(a[i], x[i], gscale);
+    s += e.term;
+    if (d_a) d_a[i] = e.d;
+    if (recon) recon[i] = e.r;
+  }
+  block_dsum_store(s, red, partials + blockIdx.x);
+}
+
+// KLD = -0.5 sum (1 + logvar - mu^2 - exp(logvar)) and, with the decoder's input gradient g_z, the backward of
+// z = mu + eps exp(0.5 logvar) together with beta * dKLD:
+//   g_mu = g_z + beta mu,   g_logvar = 0.5 g_z eps exp(0.5 logvar) + 0.5 beta (exp(logvar) - 1)
+// B x latent_dim elements (2560 at B = 128): evaluated in double and rounded once - the two terms of g_logvar
+// cancel where the reconstruction pulls against the prior, and 1 + logvar - exp(logvar) cancels near logvar = 0.
+__global__ void __launch_bounds__(256)
+vae_kld_reparam_bwd_kernel(const float* __restrict__ mu, const float* __restrict__ logvar,
+                           const float* __restrict__ eps, const float* __restrict__ g_z, float* __restrict__ g_mu,
+                           float* __restrict__ g_logvar, float beta, int64_t n, double* __restrict__ partials) {
+  __shared__ double red[4];
+  double s = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const double m = mu[i], lv = logvar[i], ev = exp(lv);
+    s += -0.5 * (((1.0 + lv) - m * m) - ev);
+    if (g_z) {
+      const double gz = g_z[i];
+      g_mu[i] = (float)(gz + (double)beta * m);
+      g_logvar[i] = (float)(0.5 * gz * (double)eps[i] * exp(0.5 * lv) + 0.5 * (double)beta * (ev - 1.0));
+    }
+  }
+  block_dsum_store(s, red, partials + blockIdx.x);
+}
+
+// out = {BCE + beta KLD, BCE, KLD} (p_kld null: out[0] = the one sum).  One block, fixed order.
+__global__ void __launch_bounds__(256)
+vae_loss_finish_kernel(const double* __restrict__ p_bce, int nb_bce, const double* __restrict__ p_kld, int nb_kld,
+                       float beta, float* __restrict__ out) {
+  __shared__ double red[2][256];
+  double s0 = 0.0, s1 = 0.0;
+  for (int k = threadIdx.x; k < nb_bce; k += 256) s0 += p_bce[k];
+  if (p_kld)
+    for (int k = threadIdx.x; k < nb_kld; k += 256) s1 += p_kld[k];
+  red[0][threadIdx.x] = s0;
+  red[1][threadIdx.x] = s1;
+  __syncthreads();
+  for (int half = 128; half > 0; half >>= 1) {
+    if ((int)threadIdx.x < half) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + half];
+      red[1][threadIdx.x] += red[1][threadIdx.x + half];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    if (p_kld) {
+      out[0] = (float)(red[0][0] + (double)beta * red[1][0]);
+      out[1] = (float)red[0][0];
+      out[2] = (float)red[1][0];
+    } else {
+      out[0] = (float)red[0][0];
+    }
+  }
+}
+
+// reparam_kernel with the noise drawn in the kernel (one Philox block per 4 elements, as q_sample_philox_kernel);
+// the drawn eps is written out for the backward pass
+__global__ void __launch_bounds__(256)
+reparam_philox_kernel(const float* __restrict__ mu, const float* __restrict__ logvar, float* __restrict__ z,
+                      float* __restrict__ eps_out, int64_t n, uint64_t seed, uint64_t offset) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q * 4 >= n) return;
+  const float4 e4 = philox_normal4((uint64_t)q, offset, seed);
+  const float e[4] = {e4.x, e4.y, e4.z, e4.w};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int64_t i = q * 4 + k;
+    if (i < n) {
+      z[i] = mu[i] + e[k] * expf(0.5f * logvar[i]);
+      eps_out[i] = e[k];
+    }
+  }
+}
+
+// ReLU backward in place with the bias gradient of the layer below: g = h > 0 ? g : 0, db[n] = sum_m g[m][n]
+// (h is the post-activation output, dense M x N like g).  colsum_kernel's block shape and order.
+__global__ void __launch_bounds__(256)
+relu_bwd_colsum_kernel(float* __restrict__ g, const float* __restrict__ h, int M, int N, float* __restrict__ db) {
+  __shared__ float red[8][32];
+  const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5, n = blockIdx.x * 32 + cl;
+  float s = 0.f;
+  if (n < N)
+    for (int m = sl; m < M; m += 8) {
+      const size_t i = (size_t)m * N + n;
+      const float v = h[i] > 0.f ? g[i] : 0.f;
+      g[i] = v;
+      s += v;
+    }
+  red[sl][cl] = s;
+  __syncthreads();
+  if (sl == 0 && n < N) {
+    float v = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v += red[k][cl];
+    db[n] = v;
+  }
+}
+
+inline int vae_loss_grid(int64_t n) {
+  const int64_t g = (n + 1023) / 1024;
+  return (int)(g > VAE_LOSS_BLOCKS ? VAE_LOSS_BLOCKS : g);
+}
+
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+int vae_bce_launch(const float* a, const float* x, float* d_a, float* recon, float gscale, int64_t n, double* partials,
+                   int grid, hipStream_t st) {
+  if (al16(a) && al16(x) && al16(d_a) && al16(recon))
+    vae_bce_logits_grad_kernel<true><<<grid, 256, 0, st>>>(a, x, d_a, recon, gscale, n, partials);
+  else
+    vae_bce_logits_grad_kernel<false><<<grid, 256, 0, st>>>(a, x, d_a, recon, gscale, n, partials);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+struct VaeLayout {
+  size_t h1, mu, logvar, eps, z, h3, a, d_a, g_h3, g_z, g_mu, g_logvar, g_h1, partials, total;
+};
+
+VaeLayout vae_train_layout(int B, int D, int H, int L) {
+  VaeLayout V;
+  size_t o = 0;
+  auto take = [&](size_t n) { size_t r = o; o += al64(n); return r; };
+  const size_t b = (size_t)B;
+  V.h1 = take(b * H); V.mu = take(b * L); V.logvar = take(b * L); V.eps = take(b * L); V.z = take(b * L);
+  V.h3 = take(b * H); V.a = take(b * D); V.d_a = take(b * D); V.g_h3 = take(b * H); V.g_z = take(b * L);
+  V.g_mu = take(b * L); V.g_logvar = take(b * L); V.g_h1 = take(b * H);
+  V.partials = take(2 * VAE_LOSS_BLOCKS * (sizeof(double) / sizeof(float)));   // BCE | KLD double partials
+  V.total = o;
+  return V;
+}
+
+}  // namespace
+
+extern "C" size_t tdx_vae_loss_scratch_bytes(void) { return VAE_LOSS_BLOCKS * sizeof(double); }
+
+extern "C" int tdx_vae_bce_logits_grad(const float* logits, const float* x, float* loss_out, float* d_logits,
+                                       float* recon, float gscale, int64_t n, void* scratch, tdx_stream_t stream) {
+  if (!logits || !x || !loss_out || !scratch || n <= 0 || (reinterpret_cast<uintptr_t>(scratch) & 7)) return TDX_E_BADARG;
+  hipStream_t st = to_stream(stream);
+  double* partials = static_cast<double*>(scratch);
+  const int grid = vae_loss_grid(n);
+  RC(vae_bce_launch(logits, x, d_logits, recon, gscale, n, partials, grid, st));
+  vae_loss_finish_kernel<<<1, 256, 0, st>>>(partials, grid, nullptr, 0, 0.f, loss_out);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tdx_vae_kld_reparam_bwd(const float* mu, const float* logvar, const float* eps, const float* g_z,
+                                       float* kld_out, float* g_mu, float* g_logvar, float kld_weight, int64_t n,
+                                       void* scratch, tdx_stream_t stream) {
+  if (!mu || !logvar || !kld_out || !scratch || n <= 0 || (reinterpret_cast<uintptr_t>(scratch) & 7)) return TDX_E_BADARG;
+  if (g_z && (!eps || !g_mu || !g_logvar)) return TDX_E_BADARG;
+  hipStream_t st = to_stream(stream);
+  double* partials = static_cast<double*>(scratch);
+  const int grid = vae_loss_grid(n);
+  vae_kld_reparam_bwd_kernel<<<grid, 256, 0, st>>>(mu, logvar, eps, g_z, g_mu, g_logvar, kld_weight, n, partials);
+  TDX_CHECK_LAUNCH();
+  vae_loss_finish_kernel<<<1, 256, 0, st>>>(partials, grid, nullptr, 0, 0.f, kld_out);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tdx_vae_reparameterize_philox(const float* mu, const float* logvar, float* z, float* eps_out,
+                                             int64_t n, uint64_t seed, uint64_t offset, tdx_stream_t stream) {
+  if (!mu || !logvar || !z || !eps_out || n <= 0) return TDX_E_BADARG;
+  reparam_philox_kernel<<<cdiv(cdiv(n, 4), 256), 256, 0, to_stream(stream)>>>(mu, logvar, z, eps_out, n, seed, offset);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" size_t tdx_vae_train_workspace_floats(int batch, int input_dim, int hidden_dim, int latent_dim) {
+  if (batch <= 0 || input_dim <= 0 || hidden_dim <= 0 || latent_dim <= 0) return 0;
+  return vae_train_layout(batch, input_dim, hidden_dim, latent_dim).total;
+}
+
+// vae.py:64-76 and loss.backward() in one call.  params / grads: fc1.w fc1.b fc21.w fc21.b fc22.w fc22.b fc3.w
+// fc3.b fc4.w fc4.b; grads == NULL: forward and losses only.  eps == NULL: drawn from Philox (seed, offset).
+// out3 = {BCE + kld_weight KLD, BCE, KLD}; the gradients are those of gscale * out3[0].
+extern "C" int tdx_vae_loss_grads(const float* x, const void* const* params, void* const* grads, const float* eps,
+                                  uint64_t seed, uint64_t offset, float kld_weight, float gscale, float* out3,
+                                  float* workspace, int batch, int input_dim, int hidden_dim, int latent_dim,
+                                  tdx_stream_t stream) {
+  if (!x || !params || !out3 || !workspace || batch <= 0 || input_dim <= 0 || hidden_dim <= 0 || latent_dim <= 0)
+    return TDX_E_BADARG;
+  if (!(kld_weight >= 0.f)) return TDX_E_BADARG;
+  if (reinterpret_cast<uintptr_t>(workspace) & 7) return TDX_E_BADARG;   // the double partials live inside it
+  const float* const* P = reinterpret_cast<const float* const*>(params);
+  float* const* G = reinterpret_cast<float* const*>(grads);
+  for (int i = 0; i < 10; ++i)
+    if (!P[i] || (G && !G[i])) return TDX_E_BADARG;
+  hipStream_t st = to_stream(stream);
+  const int B = batch, D = input_dim, H = hidden_dim, L = latent_dim;
+  const VaeLayout V = vae_train_layout(B, D, H, L);
+  float* ws = workspace;
+  double* p_bce = reinterpret_cast<double*>(ws + V.partials);
+  double* p_kld = p_bce + VAE_LOSS_BLOCKS;
+  const int64_t nz = (int64_t)B * L;
+  // forward (vae.py:51-67; the last layer without its sigmoid: the loss works on the logit)
+  RC(linear_fwd(x, D, P[0], P[1], ws + V.h1, H, B, H, D, 1, nullptr, nullptr, nullptr, 0, st));
+  RC(linear_fwd(ws + V.h1, H, P[2], P[3], ws + V.mu, L, B, L, H, 0, nullptr, nullptr, nullptr, 0, st));
+  RC(linear_fwd(ws + V.h1, H, P[4], P[5], ws + V.logvar, L, B, L, H, 0, nullptr, nullptr, nullptr, 0, st));
+  if (eps) {
+    reparam_kernel<<<cdiv(nz, 256), 256, 0, st>>>(ws + V.mu, ws + V.logvar, eps, ws + V.z, nz);
+  } else {
+    reparam_philox_kernel<<<cdiv(cdiv(nz, 4), 256), 256, 0, st>>>(ws + V.mu, ws + V.logvar, ws + V.z, ws + V.eps, nz,
+                                                                   seed, offset);
+    eps = ws + V.eps;
+  }
+  TDX_CHECK_LAUNCH();
+  RC(linear_fwd(ws + V.z, L, P[6], P[7], ws + V.h3, H, B, H, L, 1, nullptr, nullptr, nullptr, 0, st));
+  RC(linear_fwd(ws + V.h3, H, P[8], P[9], ws + V.a, D, B, D, H, 0, nullptr, nullptr, nullptr, 0, st));
+  // vae.py:71-76
+  const int g_bce = vae_loss_grid((int64_t)B * D), g_kld = vae_loss_grid(nz);
+  RC(vae_bce_launch(ws + V.a, x, G ? ws + V.d_a : nullptr, nullptr, gscale, (int64_t)B * D, p_bce, g_bce, st));
+  if (!G) {
+    vae_kld_reparam_bwd_kernel<<<g_kld, 256, 0, st>>>(ws + V.mu, ws + V.logvar, nullptr, nullptr, nullptr, nullptr,
+                                                      0.f, nz, p_kld);
+    TDX_CHECK_LAUNCH();
+    vae_loss_finish_kernel<<<1, 256, 0, st>>>(p_bce, g_bce, p_kld, g_kld, kld_weight, out3);
+    TDX_CHECK_LAUNCH();
+    return 0;
+  }
+  // backward: fc4, fc3
+  RC(linear_wgrad(ws + V.d_a, D, ws + V.h3, H, G[8], B, D, H, st));
+  RC(colsum(ws + V.d_a, D, B, D, G[9], st));
+  RC(linear_dgrad(ws + V.d_a, D, P[8], ws + V.g_h3, H, B, D, H, 0, st));
+  relu_bwd_colsum_kernel<<<cdiv(H, 32), 256, 0, st>>>(ws + V.g_h3, ws + V.h3, B, H, G[7]);
+  TDX_CHECK_LAUNCH();
+  RC(linear_wgrad(ws + V.g_h3, H, ws + V.z, L, G[6], B, H, L, st));
+  RC(linear_dgrad(ws + V.g_h3, H, P[6], ws + V.g_z, L, B, H, L, 0, st));
+  // KLD and the reparameterisation
+  vae_kld_reparam_bwd_kernel<<<g_kld, 256, 0, st>>>(ws + V.mu, ws + V.logvar, eps, ws + V.g_z, ws + V.g_mu,
+                                                    ws + V.g_logvar, kld_weight * gscale, nz, p_kld);
+  TDX_CHECK_LAUNCH();
+  vae_loss_finish_kernel<<<1, 256, 0, st>>>(p_bce, g_bce, p_kld, g_kld, kld_weight, out3);
+  TDX_CHECK_LAUNCH();
+  // fc21, fc22: the encoder-side input gradient is one accumulate chain
+  RC(linear_wgrad(ws + V.g_mu, L, ws + V.h1, H, G[2], B, L, H, st));
+  RC(colsum(ws + V.g_mu, L, B, L, G[3], st));
+  RC(linear_wgrad(ws + V.g_logvar, L, ws + V.h1, H, G[4], B, L, H, st));
+  RC(colsum(ws + V.g_logvar, L, B, L, G[5], st));
+  RC(linear_dgrad(ws + V.g_mu, L, P[2], ws + V.g_h1, H, B, L, H, 0, st));
+  RC(linear_dgrad(ws + V.g_logvar, L, P[4], ws + V.g_h1, H, B, L, H, 1, st));
+  relu_bwd_colsum_kernel<<<cdiv(H, 32), 256, 0, st>>>(ws + V.g_h1, ws + V.h1, B, H, G[1]);
+  TDX_CHECK_LAUNCH();
+  // fc1 (no input gradient of x)
+  return linear_wgrad(ws + V.g_h1, H, x, D, G[0], B, H, D, st);
+}
+
+// ------------------------------------------------------------------------------------------
 // Building blocks of the "transformer" noise model of diffusion_transformer.py:16-107 (sequence
 // length 1: attention(x) == out_proj(v_proj(x)); LayerNorm, GELU, SiLU, dropout, residual adds).
 // All latency-bound elementwise / row kernels on (B, 256..1024) activations.

@@ -9,9 +9,10 @@ import torch
 
 from .schedule import ForwardProcess, ddim_sample_loop, dpm_sample_loop, sample_loop
 from .unet import ARCH_LATENT, NoiseModelBase
-from .vae import VAE, VAEConfig
+from .vae import VAE, VAEConfig, VAETrainStep
 
-__all__ = ["NoiseModel", "ForwardProcess", "sample", "ddim_sample", "dpm_sample", "VAE", "VAEConfig"]
+__all__ = ["NoiseModel", "ForwardProcess", "sample", "ddim_sample", "dpm_sample", "VAE", "VAEConfig",
+           "VAETrainStep"]
 
 
 class NoiseModel(NoiseModelBase):
