@@ -52,74 +52,110 @@ def golden(golden_dir):
     return np.load(os.path.join(golden_dir, "latent_B32.npz"))
 
 
-@pytest.mark.parametrize("M,N,K,act", [(1, 20, 512, 0), (37, 400, 784, 1), (130, 784, 400, 2), (16, 512, 20, 1),
-                                       (128, 64, 64, 0)])
-def test_linear_fwd_bwd_vs_torch(M, N, K, act):
-    """tdx_linear_fwd / tdx_linear_bwd with row strides, ragged tiles and K tails."""
+def _lin_cases(extra=()):
+    """(M, N, K, act, ldx, ldo, off).  The first block keeps its ids: ldx = K + 12, ldo = N + 8 and torch-aligned bases
+    (every operand on the 16-byte load of stage_load / load4, K tails at chunk ends only).  The second block is the rest
+    of load4's dispatch: ld % 4 != 0 (four guarded scalar loads, rows that start at every alignment), a K tail INSIDE a
+    4-group of the vector path (c + 3 < C fails next to random padding), and ld % 4 == 0 with every base one float into
+    its allocation (off = 1: scalar path by the pointer test alone)."""
+    old = [(1, 20, 512, 0), (37, 400, 784, 1), (130, 784, 400, 2), (16, 512, 20, 1), (128, 64, 64, 0)] + list(extra)
+    cases = [pytest.param(M, N, K, act, K + 12, N + 8, 0, id=f"{M}-{N}-{K}-{act}") for M, N, K, act in old]
+    new = [(3, 36, 50, 1, 50, 37, 0), (33, 5, 36, 0, 39, 7, 0), (130, 130, 130, 2, 131, 133, 0),
+           (16, 64, 258, 1, 258, 66, 0), (8, 32, 130, 0, 132, 36, 0), (16, 64, 256, 2, 260, 72, 1)]
+    return cases + [pytest.param(*c, id="-".join(map(str, c[:4])) + f"-ld{c[4]}-{c[5]}-off{c[6]}") for c in new]
+
+
+class _Block:
+    """A (rows, ld) matrix that starts `off` floats into a CUDA allocation of its own, with `off` guard floats before
+    and one behind it.  Outputs (src None) are filled with 7.0, guards included; inputs carry NaN guards, so a kernel
+    that reads one float outside the block poisons its result."""
+
+    def __init__(self, rows, ld, off, src=None):
+        n = rows * ld
+        flat = torch.full((off + n + 1,), 7.0 if src is None else float("nan"))
+        if src is not None:
+            flat[off:off + n] = src.reshape(-1)
+        self.flat = flat.cuda()
+        self.m = self.flat[off:off + n].view(rows, ld)
+        self.off, self.n = off, n
+        assert self.m.data_ptr() % 16 == (4 * off) % 16
+
+    def ptr(self):
+        return self.m.data_ptr()
+
+    def guards_untouched(self):
+        return bool((self.flat[:self.off] == 7.0).all()) and float(self.flat[self.off + self.n]) == 7.0
+
+
+@pytest.mark.parametrize("M,N,K,act,ldx,ldo,off", _lin_cases())
+def test_linear_fwd_bwd_vs_torch(M, N, K, act, ldx, ldo, off):
+    """tdx_linear_fwd / tdx_linear_bwd with row strides, ragged tiles and K tails; both load paths of the GEMM (see
+    _lin_cases); nothing outside the M x N / M x K / N x K / N results is written."""
     from tiny_diffusion_amd._lib import lib, check
 
     g = torch.Generator().manual_seed(M * 7 + N)
-    ldx, ldo = K + 12, N + 8
-    xb = torch.randn(M, ldx, generator=g).cuda()
-    w = (torch.randn(N, K, generator=g) / K**0.5).cuda()
+    xb = _Block(M, ldx, off, torch.randn(M, ldx, generator=g))
+    w = _Block(N, K, off, torch.randn(N, K, generator=g) / K**0.5)
     b = torch.randn(N, generator=g).cuda()
-    ob = torch.full((M, ldo), 7.0).cuda()
-    check(lib.tdx_linear_fwd(xb.data_ptr(), ldx, w.data_ptr(), b.data_ptr(), ob.data_ptr(), ldo, M, N, K, act, None), "fwd")
-    x = xb[:, :K]
-    ref = F.linear(x.double(), w.double(), b.double())
+    ob = _Block(M, ldo, off)
+    check(lib.tdx_linear_fwd(xb.ptr(), ldx, w.ptr(), b.data_ptr(), ob.ptr(), ldo, M, N, K, act, None), "fwd")
+    x = xb.m[:, :K]
+    ref = F.linear(x.double(), w.m.double(), b.double())
     ref = torch.relu(ref) if act == 1 else torch.sigmoid(ref) if act == 2 else ref
-    assert torch.allclose(ob[:, :N].double(), ref, rtol=2e-5, atol=2e-5)
-    assert bool((ob[:, N:] == 7.0).all())  # the padding columns are not touched
-    gyb = torch.randn(M, ldo, generator=g).cuda()
-    gx = torch.empty(M, ldx).cuda()
-    dw, db = torch.empty(N, K).cuda(), torch.empty(N).cuda()
-    check(lib.tdx_linear_bwd(gyb.data_ptr(), ldo, xb.data_ptr(), ldx, w.data_ptr(), gx.data_ptr(), ldx, dw.data_ptr(),
-                             db.data_ptr(), M, N, K, None), "bwd")
-    gy = gyb[:, :N].double()
-    assert torch.allclose(dw.double(), gy.t() @ x.double(), rtol=2e-5, atol=2e-5)
-    assert torch.allclose(db.double(), gy.sum(0), rtol=2e-5, atol=2e-5)
-    assert torch.allclose(gx[:, :K].double(), gy @ w.double(), rtol=2e-5, atol=2e-5)
+    assert torch.allclose(ob.m[:, :N].double(), ref, rtol=2e-5, atol=2e-5)
+    assert bool((ob.m[:, N:] == 7.0).all())  # the padding columns are not touched
+    assert ob.guards_untouched()
+    gyb = _Block(M, ldo, off, torch.randn(M, ldo, generator=g))
+    gx, dw, db = _Block(M, ldx, off), _Block(N, K, off), _Block(1, N, 0)
+    check(lib.tdx_linear_bwd(gyb.ptr(), ldo, xb.ptr(), ldx, w.ptr(), gx.ptr(), ldx, dw.ptr(),
+                             db.ptr(), M, N, K, None), "bwd")
+    gy = gyb.m[:, :N].double()
+    assert torch.allclose(dw.m.double(), gy.t() @ x.double(), rtol=2e-5, atol=2e-5)
+    assert torch.allclose(db.m[0].double(), gy.sum(0), rtol=2e-5, atol=2e-5)
+    assert torch.allclose(gx.m[:, :K].double(), gy @ w.m.double(), rtol=2e-5, atol=2e-5)
+    assert bool((gx.m[:, K:] == 7.0).all())
+    assert gx.guards_untouched() and dw.guards_untouched() and db.guards_untouched()
 
 
-@pytest.mark.parametrize("M,N,K,act", [(1, 20, 512, 0), (37, 400, 784, 1), (130, 784, 400, 2), (16, 512, 20, 1),
-                                       (128, 64, 64, 0), (32, 512, 512, 1)])
-def test_linear_bf16_mode_same_arithmetic_on_the_host(M, N, K, act):
+@pytest.mark.parametrize("M,N,K,act,ldx,ldo,off", _lin_cases(extra=[(32, 512, 512, 1)]))
+def test_linear_bf16_mode_same_arithmetic_on_the_host(M, N, K, act, ldx, ldo, off):
     """tdx_linear_{fwd,bwd}_prec with TDX_PREC_BF16 (gemm_bf16_kernel: operands rounded to bf16, v_mfma_f32_32x32x16_bf16,
     fp32 accumulation) against the SAME arithmetic on the host - operands rounded to bf16 (nearest even), exact
-    products, fp64 sums: what is left is fp32 accumulation order (<= 2e-5); row strides, ragged tiles and K tails as in
-    the fp32 test; TDX_PREC_F32 through the same entry equals tdx_linear_fwd bit for bit."""
+    products, fp64 sums: what is left is fp32 accumulation order (<= 2e-5); row strides, ragged tiles, K tails and both
+    load paths as in the fp32 test (_lin_cases); TDX_PREC_F32 through the same entry equals tdx_linear_fwd bit for bit."""
     from tiny_diffusion_amd._lib import lib, check
 
     r16 = lambda v: v.to(torch.bfloat16).double()   # noqa: E731
     g = torch.Generator().manual_seed(M * 11 + N)
-    ldx, ldo = K + 12, N + 8
-    xb = torch.randn(M, ldx, generator=g).cuda()
-    w = (torch.randn(N, K, generator=g) / K**0.5).cuda()
+    xb = _Block(M, ldx, off, torch.randn(M, ldx, generator=g))
+    w = _Block(N, K, off, torch.randn(N, K, generator=g) / K**0.5)
     b = torch.randn(N, generator=g).cuda()
-    ob = torch.full((M, ldo), 7.0).cuda()
-    check(lib.tdx_linear_fwd_prec(xb.data_ptr(), ldx, w.data_ptr(), b.data_ptr(), ob.data_ptr(), ldo, M, N, K, act, 1, None))
-    x = xb[:, :K]
-    ref = r16(x) @ r16(w).t() + b.double()
+    ob = _Block(M, ldo, off)
+    check(lib.tdx_linear_fwd_prec(xb.ptr(), ldx, w.ptr(), b.data_ptr(), ob.ptr(), ldo, M, N, K, act, 1, None))
+    x = xb.m[:, :K]
+    ref = r16(x) @ r16(w.m).t() + b.double()
     ref = torch.relu(ref) if act == 1 else torch.sigmoid(ref) if act == 2 else ref
-    assert torch.allclose(ob[:, :N].double(), ref, rtol=2e-5, atol=2e-5)
-    assert bool((ob[:, N:] == 7.0).all())
-    exact = F.linear(x.double(), w.double(), b.double())   # and it IS a different arithmetic from fp32
+    assert torch.allclose(ob.m[:, :N].double(), ref, rtol=2e-5, atol=2e-5)
+    assert bool((ob.m[:, N:] == 7.0).all())
+    assert ob.guards_untouched()
+    exact = F.linear(x.double(), w.m.double(), b.double())   # and it IS a different arithmetic from fp32
     exact = torch.relu(exact) if act == 1 else torch.sigmoid(exact) if act == 2 else exact
     if K >= 64:
-        assert (ob[:, :N].double() - exact).abs().max() > 1e-4
-    gyb = torch.randn(M, ldo, generator=g).cuda()
-    gx = torch.empty(M, ldx).cuda()
-    dw, db = torch.empty(N, K).cuda(), torch.empty(N).cuda()
-    check(lib.tdx_linear_bwd_prec(gyb.data_ptr(), ldo, xb.data_ptr(), ldx, w.data_ptr(), gx.data_ptr(), ldx, dw.data_ptr(),
-                                  db.data_ptr(), M, N, K, 1, None))
-    gy = gyb[:, :N]
-    assert torch.allclose(dw.double(), r16(gy).t() @ r16(x), rtol=2e-5, atol=2e-5)
-    assert torch.allclose(db.double(), gy.double().sum(0), rtol=2e-5, atol=2e-5)      # bias gradient: plain fp32 sum
-    assert torch.allclose(gx[:, :K].double(), r16(gy) @ r16(w), rtol=2e-5, atol=2e-5)
-    o32a, o32b = torch.empty(M, ldo).cuda(), torch.empty(M, ldo).cuda()
-    check(lib.tdx_linear_fwd_prec(xb.data_ptr(), ldx, w.data_ptr(), b.data_ptr(), o32a.data_ptr(), ldo, M, N, K, act, 0, None))
-    check(lib.tdx_linear_fwd(xb.data_ptr(), ldx, w.data_ptr(), b.data_ptr(), o32b.data_ptr(), ldo, M, N, K, act, None))
-    assert torch.equal(o32a[:, :N], o32b[:, :N])
+        assert (ob.m[:, :N].double() - exact).abs().max() > 1e-4
+    gyb = _Block(M, ldo, off, torch.randn(M, ldo, generator=g))
+    gx, dw, db = _Block(M, ldx, off), _Block(N, K, off), _Block(1, N, 0)
+    check(lib.tdx_linear_bwd_prec(gyb.ptr(), ldo, xb.ptr(), ldx, w.ptr(), gx.ptr(), ldx, dw.ptr(),
+                                  db.ptr(), M, N, K, 1, None))
+    gy = gyb.m[:, :N]
+    assert torch.allclose(dw.m.double(), r16(gy).t() @ r16(x), rtol=2e-5, atol=2e-5)
+    assert torch.allclose(db.m[0].double(), gy.double().sum(0), rtol=2e-5, atol=2e-5)      # bias gradient: plain fp32 sum
+    assert torch.allclose(gx.m[:, :K].double(), r16(gy) @ r16(w.m), rtol=2e-5, atol=2e-5)
+    assert bool((gx.m[:, K:] == 7.0).all())
+    assert gx.guards_untouched() and dw.guards_untouched() and db.guards_untouched()
+    o32a, o32b = _Block(M, ldo, off), _Block(M, ldo, off)
+    check(lib.tdx_linear_fwd_prec(xb.ptr(), ldx, w.ptr(), b.data_ptr(), o32a.ptr(), ldo, M, N, K, act, 0, None))
+    check(lib.tdx_linear_fwd(xb.ptr(), ldx, w.ptr(), b.data_ptr(), o32b.ptr(), ldo, M, N, K, act, None))
+    assert torch.equal(o32a.m[:, :N], o32b.m[:, :N])
 
 
 def test_latent_bf16_mode_against_reference_autocast_yardstick(golden_dir):

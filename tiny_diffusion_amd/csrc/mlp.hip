@@ -746,6 +746,11 @@ int tdx_latent_tensor(int B, const char* name, size_t* off, size_t* numel) {
       {"t3", L.tp[2], b * 256}, {"cat3", L.cat[0], b * 128}, {"cat2", L.cat[1], b * 256}, {"cat1", L.cat[2], b * 512}};
   for (auto& f : fixed)
     if (n == f.nm) { *off = f.off; *numel = f.cnt; return 0; }
+  if (n.size() >= 3 && n.rfind("ss", 0) == 0) {  // scale | shift | mean | rstd of unit i, as tdx_unet_tensor's "ssN"
+    const int i = atoi(n.c_str() + 2);
+    if (i < 0 || i > 12) return TDX_E_BADARG;
+    *off = L.ss[i]; *numel = 4 * (size_t)LU[i].cout; return 0;
+  }
   if (n.size() >= 2 && n[0] == 'Y') {
     const int i = atoi(n.c_str() + 1);
     if (i < 0 || i > 12) return TDX_E_BADARG;
@@ -1292,13 +1297,19 @@ __global__ void embedding_bwd_kernel(const float* __restrict__ g, const int64_t*
 
 }  // namespace
 
+// every N % 64 == 0, N <= 1024 (the contract of include/tdx.h): one instantiation per N / 64
+#define TDX_LN_CASE(KERNEL, P_, ...) \
+  case P_: KERNEL<P_><<<cdiv(M, 4), 256, 0, st>>>(__VA_ARGS__); break;
 #define TDX_LN_DISPATCH(KERNEL, ...)                                              \
   switch (N / 64) {                                                               \
-    case 1: KERNEL<1><<<cdiv(M, 4), 256, 0, st>>>(__VA_ARGS__); break;            \
-    case 2: KERNEL<2><<<cdiv(M, 4), 256, 0, st>>>(__VA_ARGS__); break;            \
-    case 4: KERNEL<4><<<cdiv(M, 4), 256, 0, st>>>(__VA_ARGS__); break;            \
-    case 8: KERNEL<8><<<cdiv(M, 4), 256, 0, st>>>(__VA_ARGS__); break;            \
-    case 16: KERNEL<16><<<cdiv(M, 4), 256, 0, st>>>(__VA_ARGS__); break;          \
+    TDX_LN_CASE(KERNEL, 1, __VA_ARGS__) TDX_LN_CASE(KERNEL, 2, __VA_ARGS__)       \
+    TDX_LN_CASE(KERNEL, 3, __VA_ARGS__) TDX_LN_CASE(KERNEL, 4, __VA_ARGS__)       \
+    TDX_LN_CASE(KERNEL, 5, __VA_ARGS__) TDX_LN_CASE(KERNEL, 6, __VA_ARGS__)       \
+    TDX_LN_CASE(KERNEL, 7, __VA_ARGS__) TDX_LN_CASE(KERNEL, 8, __VA_ARGS__)       \
+    TDX_LN_CASE(KERNEL, 9, __VA_ARGS__) TDX_LN_CASE(KERNEL, 10, __VA_ARGS__)      \
+    TDX_LN_CASE(KERNEL, 11, __VA_ARGS__) TDX_LN_CASE(KERNEL, 12, __VA_ARGS__)     \
+    TDX_LN_CASE(KERNEL, 13, __VA_ARGS__) TDX_LN_CASE(KERNEL, 14, __VA_ARGS__)     \
+    TDX_LN_CASE(KERNEL, 15, __VA_ARGS__) TDX_LN_CASE(KERNEL, 16, __VA_ARGS__)     \
     default: return TDX_E_SHAPE;                                                  \
   }
 
