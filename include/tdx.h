@@ -158,6 +158,30 @@ int tdx_p_sample_step_ms_guided(float* x, const float* out, float* hist, const f
                                 int64_t n_half_elems, float w, float lo, float hi, int64_t* counter_dec,
                                 tdx_stream_t stream);
 
+/* Inpainting (masked sampling with a known region; Song et al. 2021 I.2, Lugmayr et al. 2022): the two updates above
+ * with the clamped prediction blended with the caller's data before the step,
+ *   x0m = (1 - mask)*x0c + mask*known          mask = 1 keeps the known value, 0 generates, a fraction is a soft edge
+ *   x_out = (A*x0m + Bx*x) + sigma*z           (x0 form; tdx_p_sample_step_x0's arguments)
+ *   x_out = (A*x0m + Bx*x) + H*hist; hist = x0m   (multistep form; tdx_p_sample_step_ms's arguments)
+ * every operation rounded separately, in this order; known is not clamped.  known, mask: n floats each (guided:
+ * n_half_elems, indexed like hist), finite, mask in [0, 1] (the caller checks).  The noise, the Philox indexing, tau,
+ * counter_dec, in-place use and the H == 0 rule are the unmasked entries'.  On row 0 (A = 1, Bx = 0, no noise) the result
+ * is known wherever mask == 1, bit for bit.  TDX_E_BADARG: the cases of the unmasked entry, or a null known / mask. */
+int tdx_p_sample_step_x0_masked(float* x_out, const float* x, const float* out, const float* z, const float* known,
+                                const float* mask, const float* coef5, const int64_t* tau, const int32_t* t_idx,
+                                int64_t n, float lo, float hi, int use_philox, uint64_t philox_seed,
+                                int64_t* counter_dec, tdx_stream_t stream);
+int tdx_p_sample_step_x0_guided_masked(float* x, const float* out, const float* z, const float* known,
+                                       const float* mask, const float* coef5, const int64_t* tau, const int32_t* t_idx,
+                                       int64_t n_half_elems, float w, float lo, float hi, int use_philox,
+                                       uint64_t philox_seed, int64_t* counter_dec, tdx_stream_t stream);
+int tdx_p_sample_step_ms_masked(float* x_out, const float* x, const float* out, float* hist, const float* known,
+                                const float* mask, const float* coef5, const int32_t* t_idx, int64_t n, float lo,
+                                float hi, int64_t* counter_dec, tdx_stream_t stream);
+int tdx_p_sample_step_ms_guided_masked(float* x, const float* out, float* hist, const float* known, const float* mask,
+                                       const float* coef5, const int32_t* t_idx, int64_t n_half_elems, float w,
+                                       float lo, float hi, int64_t* counter_dec, tdx_stream_t stream);
+
 /* Condition dropout for training the unconditional branch: sample b is dropped iff a Philox uniform in [0,1) keyed by
  * (seed, offset, b) is < p (p == 0: exact copy, p == 1: every sample).  A dropped sample gets label -1 / a zeroed row.
  * The two entries draw the same mask for the same key.  In place (y_out == y, c_out == c) is allowed. */
@@ -714,6 +738,10 @@ int tdx_unet_eval_step(tdx_unet* u, const void* const* params, void* const* buff
 int tdx_unet_prepare_sampling(tdx_unet* u, const void* const* params, const void* cond, int batch, int T,
                               tdx_stream_t stream);
 
+/* Invalidate the tables of tdx_unet_prepare_sampling{,_sched}: later eval steps take the direct path, which computes
+ * what an eager forward computes bit for bit, until tables are prepared again.  No launch, no allocation. */
+int tdx_unet_drop_sampling_tables(tdx_unet* u);
+
 /* The same two entries for a timestep schedule of S steps (tau: device int64 [S], see tdx_step_begin_sched):
  * prepare builds S table rows at the timesteps tau[0..S) (rebuilt on every call), and the scheduled eval step
  * runs eps_theta(x, tau[k]) and the update of coefficient row k (coef: (S,3)); the counter holds k.  A table built
@@ -753,6 +781,21 @@ int tdx_unet_eval_step_ms(tdx_unet* u, const void* const* params, void* const* b
                           const float* coef5, const int64_t* tau, int S, int64_t* counter, int32_t* t_idx,
                           int64_t* t_vec, float* eps, int64_t n_elems, void* workspace, size_t workspace_bytes,
                           int batch, int guided, float w, float lo, float hi, float* hist, tdx_stream_t stream);
+
+/* The masked reverse steps (inpainting; see tdx_p_sample_step_x0_masked): the arguments of tdx_unet_eval_step_x0 /
+ * tdx_unet_eval_step_ms plus known and mask, n_elems floats each (a half-batch forward indexes them by the element's
+ * place in the whole batch, as it does the history).  TDX_E_BADARG also for a null known or mask. */
+int tdx_unet_eval_step_x0_masked(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
+                                 const void* cond, const float* z, const float* coef5, const int64_t* tau, int S,
+                                 int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
+                                 void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed, int guided,
+                                 float w, float lo, float hi, const float* known, const float* mask,
+                                 tdx_stream_t stream);
+int tdx_unet_eval_step_ms_masked(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
+                                 const void* cond, const float* coef5, const int64_t* tau, int S, int64_t* counter,
+                                 int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems, void* workspace,
+                                 size_t workspace_bytes, int batch, int guided, float w, float lo, float hi,
+                                 float* hist, const float* known, const float* mask, tdx_stream_t stream);
 
 /* Testing aid: offset (in floats) and element count of a named intermediate inside the
  * workspace after a forward: "x0", "Y0".."Y12", "ss0".."ss12", "e1p", "cat1", "d1a", ... */

@@ -189,6 +189,7 @@ _SIGS = {
     "tdx_unet_backward_sync_mark": (C.c_int, [_ptr, C.c_int]),
     "tdx_unet_request_input_grad": (C.c_int, [_ptr, _ptr]),
     "tdx_unet_prepare_sampling": (C.c_int, [_ptr, _ptr, _ptr, C.c_int, C.c_int, _ptr]),
+    "tdx_unet_drop_sampling_tables": (C.c_int, [_ptr]),
     "tdx_unet_prepare_sampling_sched": (C.c_int, [_ptr, _ptr, _ptr, C.c_int, _ptr, C.c_int, _ptr]),
     "tdx_initial_conv_input_grad": (C.c_int, [_ptr, _ptr, _ptr] + [C.c_int] * 5 + [_ptr]),
     "tdx_unet_eval_step": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int64,
@@ -210,6 +211,19 @@ _SIGS = {
     "tdx_unet_eval_step_ms": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, _ptr, _ptr, _ptr, _ptr,
                                         C.c_int64, _ptr, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                         _ptr, _ptr]),
+    "tdx_p_sample_step_x0_masked": (C.c_int, [_ptr] * 9 + [C.c_int64, C.c_float, C.c_float, C.c_int, C.c_uint64, _ptr,
+                                                           _ptr]),
+    "tdx_p_sample_step_x0_guided_masked": (C.c_int, [_ptr] * 8 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int,
+                                                                  C.c_uint64, _ptr, _ptr]),
+    "tdx_p_sample_step_ms_masked": (C.c_int, [_ptr] * 8 + [C.c_int64, C.c_float, C.c_float, _ptr, _ptr]),
+    "tdx_p_sample_step_ms_guided_masked": (C.c_int, [_ptr] * 7 + [C.c_int64, C.c_float, C.c_float, C.c_float, _ptr,
+                                                                  _ptr]),
+    "tdx_unet_eval_step_x0_masked": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, _ptr, _ptr,
+                                               _ptr, _ptr, C.c_int64, _ptr, C.c_size_t, C.c_int, C.c_uint64, C.c_int,
+                                               C.c_float, C.c_float, C.c_float, _ptr, _ptr, _ptr]),
+    "tdx_unet_eval_step_ms_masked": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, _ptr, _ptr, _ptr,
+                                               _ptr, C.c_int64, _ptr, C.c_size_t, C.c_int, C.c_int, C.c_float,
+                                               C.c_float, C.c_float, _ptr, _ptr, _ptr, _ptr]),
     "tdx_cond_drop_labels": (C.c_int, [_ptr, _ptr, C.c_int, C.c_float, C.c_uint64, C.c_uint64, _ptr]),
     "tdx_cond_drop_rows": (C.c_int, [_ptr, _ptr, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, _ptr]),
     "tdx_timestep_embedding": (C.c_int, [_ptr, _ptr, C.c_int, C.c_int, _ptr]),

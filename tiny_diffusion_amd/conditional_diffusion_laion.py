@@ -75,7 +75,11 @@ def sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, text_embe
     ``vae=None`` the latents are returned (the decoder is an external pretrained model).
     ``guidance_scale=w``: classifier-free guidance ``eps_u + w (eps_c - eps_u)`` against the all-zero text
     embedding (schedule.sample_loop); ``None``: none.  ``clip_denoised=(lo, hi)`` (through ``**kw``): clipped-x0
-    sampling with the latents' own range (``True`` is [-1, 1], the range of pixel data)."""
+    sampling with the latents' own range (``True`` is [-1, 1], the range of pixel data).  ``known=x, mask=m`` (through ``**kw``; both or neither, broadcast to
+    ``(n_samples, *(4, H, W))``): inpainting - every step blends the implied latent x_0 with ``known`` where ``mask`` is 1 (a
+    fraction: a soft edge) and the latent the loop returns (before the decode) equals ``known`` there exactly; ``x_T`` stays pure noise - an
+    image-to-image start composes from the existing ``x_T=`` and ``timesteps=`` arguments and is not part of this
+    (schedule.sample_loop).  ``ddim_sample`` and ``dpm_sample`` take the two keywords too."""
     if text_embeds is None:
         raise ValueError("Text embeddings must be provided for conditional generation.")
     n_samples = text_embeds.shape[0]

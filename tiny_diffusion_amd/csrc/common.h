@@ -95,6 +95,39 @@ __device__ static inline float p_step_ms(float x, float o, float hprev, float p,
   return r;
 }
 
+// Inpainting (masked sampling with a known region): the blend of the clamped prediction with the caller's data between
+// the clamp and the step,  x0m = (1 - m)*x0c + m*known,  each operation rounded separately.  m == 1 gives `known` and
+// m == 0 gives x0c bit for bit ((1-1)*x0c = +-0, 1*known = known; 1*x0c = x0c, 0*known = +-0: for finite operands); a
+// fractional m is a soft edge.  `known` is the user's data: it is not clamped.
+__device__ static inline float x0_blend(float x0c, float known, float m) {
+  return __fadd_rn(__fmul_rn(__fsub_rn(1.0f, m), x0c), __fmul_rn(m, known));
+}
+
+// p_step_x0 with the blend:  x0 = p*x + q*out;  x0c = min(max(x0, lo), hi);  x0m = x0_blend(x0c, known, m);
+// x' = (A*x0m + Bx*x) + sigma*z.  The known region steps from x0 = known with the chain's own x and z - the posterior
+// step of the forward process given x_0 = known; on row 0 (A = 1, Bx = 0, sigma*z = 0) it returns x0m itself.
+__device__ static inline float p_step_x0_masked(float x, float o, float z, float known, float m, float p, float q,
+                                                float A, float Bx, float sg, float lo, float hi) {
+  const float x0 = __fadd_rn(__fmul_rn(p, x), __fmul_rn(q, o));
+  const float x0c = fminf(fmaxf(x0, lo), hi);
+  const float x0m = x0_blend(x0c, known, m);
+  return __fadd_rn(__fadd_rn(__fmul_rn(A, x0m), __fmul_rn(Bx, x)), __fmul_rn(sg, z));
+}
+
+// p_step_ms with the blend:  x' = (A*x0m + Bx*x) + H*hprev, and *x0c_out is x0m - the history holds the BLENDED
+// prediction, which keeps the known region on the forward marginal of the deterministic chain (with the clamped
+// prediction as history it leaves it).  The H == 0 rule is p_step_ms's.
+__device__ static inline float p_step_ms_masked(float x, float o, float hprev, float known, float m, float p, float q,
+                                                float A, float Bx, float H, float lo, float hi, float* x0c_out) {
+  const float x0 = __fadd_rn(__fmul_rn(p, x), __fmul_rn(q, o));
+  const float x0c = fminf(fmaxf(x0, lo), hi);
+  const float x0m = x0_blend(x0c, known, m);
+  *x0c_out = x0m;
+  float r = __fadd_rn(__fmul_rn(A, x0m), __fmul_rn(Bx, x));
+  if (H != 0.0f) r = __fadd_rn(r, __fmul_rn(H, hprev));
+  return r;
+}
+
 // classifier-free guidance (Ho & Salimans 2021): eps_u + w (eps_c - eps_u), each operation rounded separately - the
 // one expression both guided updates evaluate (elementwise.hip, the epilogue of final_conv in edge_conv.hip)
 __device__ static inline float cfg_eps(float e_c, float e_u, float w) {

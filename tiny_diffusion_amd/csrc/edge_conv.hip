@@ -136,6 +136,10 @@ thin_to_fat_conv_kernel(const float* __restrict__ thin, const float* __restrict_
 // history ps.hist (the clamped x0 of the step before, one value per element of the unguided batch / the first half),
 // which the same lane overwrites with this step's clamped x0; no noise.  The arithmetic of p_sample_ms_kernel /
 // p_sample_ms_guided_kernel, bit for bit; again a template parameter that the other instantiations do not see.
+// MK = true (with X0 or MS; inpainting): the clamped prediction is blended with ps.known under ps.mask before the step
+// (p_step_x0_masked / p_step_ms_masked) - the arithmetic of p_sample_x0_masked_kernel / p_sample_ms_masked_kernel, bit
+// for bit.  The two loads belong to the lane that already loads x and are indexed like hist (idx + elem0).  A template
+// parameter that only X0 / MS instantiations take.
 struct PSampleOps {
   float* x; const float* z; const float* coef; const int32_t* t_idx; uint64_t seed; int philox; int64_t* counter_dec;
   int64_t elem0;   // index of this launch's first element in the whole batch (a half-batch launch keeps the batch's Philox stream)
@@ -146,8 +150,10 @@ struct PSampleOps {
                         // 2 = (S,5) rows (p, q, A, Bx, H) of p_step_ms (the MS kernels)
   float lo, hi;         // X0 / MS: the clamp of the implied x0
   float* hist;          // MS: the history, indexed by the element's index in the whole batch (idx + elem0)
+  const float* known;   // MK: the known data and its mask, one value per element of the unguided batch / the first half,
+  const float* mask;    //     indexed like hist
 };
-template <int CO, bool DGRAD, bool PS, typename TF, bool GD = false, bool X0 = false, bool MS = false>
+template <int CO, bool DGRAD, bool PS, typename TF, bool GD = false, bool X0 = false, bool MS = false, bool MK = false>
 __global__ void __launch_bounds__(256)
 fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
                         const float* __restrict__ bias, float* __restrict__ out, int B, int H, int W, int cor,
@@ -268,7 +274,9 @@ fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
             }
             float* hp = ps.hist + idx + ps.elem0;
             const float hv = ps_sg != 0.0f ? *hp : 0.f;
-            const float xn = p_step_ms(ps.x[idx], eg, hv, ps_p, ps_q, ps_c1, ps_c2, ps_sg, ps.lo, ps.hi, &x0c);
+            const float xn = MK ? p_step_ms_masked(ps.x[idx], eg, hv, ps.known[idx + ps.elem0], ps.mask[idx + ps.elem0],
+                                                   ps_p, ps_q, ps_c1, ps_c2, ps_sg, ps.lo, ps.hi, &x0c)
+                                : p_step_ms(ps.x[idx], eg, hv, ps_p, ps_q, ps_c1, ps_c2, ps_sg, ps.lo, ps.hi, &x0c);
             ps.x[idx] = xn;
             if (GD) ps.x[idx + ps.half] = xn;
             *hp = x0c;
@@ -276,10 +284,15 @@ fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
             const float eu = s2[co] + bv[co];
             out[idx + ps.half] = eu;
             const float eg = cfg_eps(e, eu, ps.w);
-            const float xn = X0 ? p_step_x0(ps.x[idx], eg, zv, ps_p, ps_q, ps_c1, ps_c2, ps_sg, ps.lo, ps.hi)
+            const float xn = MK ? p_step_x0_masked(ps.x[idx], eg, zv, ps.known[idx], ps.mask[idx], ps_p, ps_q, ps_c1,
+                                                   ps_c2, ps_sg, ps.lo, ps.hi)   // guided: one launch, elem0 == 0
+                           : X0 ? p_step_x0(ps.x[idx], eg, zv, ps_p, ps_q, ps_c1, ps_c2, ps_sg, ps.lo, ps.hi)
                                 : p_step(ps.x[idx], eg, zv, ps_c1, ps_c2, ps_sg);
             ps.x[idx] = xn;
             ps.x[idx + ps.half] = xn;
+          } else if (MK) {
+            ps.x[idx] = p_step_x0_masked(ps.x[idx], e, zv, ps.known[idx + ps.elem0], ps.mask[idx + ps.elem0], ps_p, ps_q,
+                                         ps_c1, ps_c2, ps_sg, ps.lo, ps.hi);
           } else if (X0) {
             ps.x[idx] = p_step_x0(ps.x[idx], e, zv, ps_p, ps_q, ps_c1, ps_c2, ps_sg, ps.lo, ps.hi);
           } else {
@@ -568,15 +581,31 @@ int tdx_initial_conv_dgrad(const void* g_x0, const float* w, float* g_x, int B, 
 int tdx_final_conv_fwd_psample(const void* in, const float* w, const float* bias, float* eps_out, int B, int H, int W,
                                int cout, float* x, const float* z, const float* coef, const int32_t* t_idx,
                                uint64_t seed, int philox, int64_t* counter_dec, hipStream_t st, int io16, int64_t elem0,
-                               const int64_t* tau, int guided, float gw, int x0, float lo, float hi, float* hist) {
+                               const int64_t* tau, int guided, float gw, int x0, float lo, float hi, float* hist,
+                               const float* known, const float* mask) {
   if (!x || !coef || !t_idx || (elem0 & 3)) return TDX_E_BADARG;
   if (x0 && !(lo < hi)) return TDX_E_BADARG;
   if (x0 < 0 || x0 > 2 || (x0 == 2 && !hist)) return TDX_E_BADARG;
+  if ((known != nullptr) != (mask != nullptr) || (known && !x0)) return TDX_E_BADARG;   // the masked update is an x0-form one
   if (guided && ((B & 1) || elem0)) return TDX_E_BADARG;   // two equal halves, the whole batch in one launch
   const int64_t M = (int64_t)(guided ? B / 2 : B) * H * W;
   const int grid = (int)std::min<int64_t>((M + 15) / 16, 8192);
-  const PSampleOps ps{x, z, coef, t_idx, seed, philox, counter_dec, elem0, tau, gw, guided ? M * cout : 0, x0, lo, hi, hist};
+  const PSampleOps ps{x, z, coef, t_idx, seed, philox, counter_dec, elem0, tau, gw, guided ? M * cout : 0, x0, lo, hi, hist, known, mask};
   if (cout != 1 && cout != 4) return TDX_E_SHAPE;
+  if (known) {   // the inpainting variants of the two x0-form families
+#define TDX_PS_MASKED(GD_, X0_, MS_)                                                                                   \
+    TDX_IO_DISPATCH(io16, T,                                                                                            \
+      if (cout == 1) fat_to_thin_conv_kernel<1, false, true, T, GD_, X0_, MS_, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps); \
+      else fat_to_thin_conv_kernel<4, false, true, T, GD_, X0_, MS_, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps))
+    if (x0 == 2) {
+      if (guided) { TDX_PS_MASKED(true, false, true); } else { TDX_PS_MASKED(false, false, true); }
+    } else {
+      if (guided) { TDX_PS_MASKED(true, true, false); } else { TDX_PS_MASKED(false, true, false); }
+    }
+#undef TDX_PS_MASKED
+    TDX_CHECK_LAUNCH();
+    return 0;
+  }
   if (x0 == 2) {   // the multistep variants: the (S,5) table (p, q, A, Bx, H) and the history
     if (guided) {
       TDX_IO_DISPATCH(io16, T,

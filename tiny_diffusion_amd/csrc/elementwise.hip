@@ -471,6 +471,154 @@ extern "C" int tdx_p_sample_step_ms_guided(float* x, const float* out, float* hi
   return 0;
 }
 
+// ------------------------------------------------------------- p_sample step, masked (inpainting)
+// The x0-form and the multistep update with a known region (common.h: x0_blend, p_step_x0_masked, p_step_ms_masked):
+// the clamped prediction is blended with `known` under `mask` before the step.  known / mask hold one value per element
+// of the n samples (guided: of the first half, indexed like hist).  Everything else - t, tau, counter_dec, the noise,
+// the Philox indexing, in-place use, the H == 0 rule - is the unmasked kernel's, which these stand beside.
+__device__ __forceinline__ float4 p_step_x0_masked_4(const float4 x, const float4 o, const float4 z, const float4 kn,
+                                                     const float4 m, float p, float q, float A, float Bx, float sg,
+                                                     float lo, float hi) {
+  float4 r;
+  r.x = p_step_x0_masked(x.x, o.x, z.x, kn.x, m.x, p, q, A, Bx, sg, lo, hi);
+  r.y = p_step_x0_masked(x.y, o.y, z.y, kn.y, m.y, p, q, A, Bx, sg, lo, hi);
+  r.z = p_step_x0_masked(x.z, o.z, z.z, kn.z, m.z, p, q, A, Bx, sg, lo, hi);
+  r.w = p_step_x0_masked(x.w, o.w, z.w, kn.w, m.w, p, q, A, Bx, sg, lo, hi);
+  return r;
+}
+
+__device__ __forceinline__ float4 p_step_ms_masked_4(const float4 x, const float4 o, const float4 h, const float4 kn,
+                                                     const float4 m, float p, float q, float A, float Bx, float H,
+                                                     float lo, float hi, float4* x0m) {
+  float4 r;
+  r.x = p_step_ms_masked(x.x, o.x, h.x, kn.x, m.x, p, q, A, Bx, H, lo, hi, &x0m->x);
+  r.y = p_step_ms_masked(x.y, o.y, h.y, kn.y, m.y, p, q, A, Bx, H, lo, hi, &x0m->y);
+  r.z = p_step_ms_masked(x.z, o.z, h.z, kn.z, m.z, p, q, A, Bx, H, lo, hi, &x0m->z);
+  r.w = p_step_ms_masked(x.w, o.w, h.w, kn.w, m.w, p, q, A, Bx, H, lo, hi, &x0m->w);
+  return r;
+}
+
+// GD = false: p_sample_x0_kernel's layout (xo may alias x).  GD = true: p_sample_x0_guided_kernel's (xo == x holds
+// 2 n4 float4, out likewise; the two outputs are combined first and the one update is written to both halves).
+template <bool GD>
+__global__ void p_sample_x0_masked_kernel(float4* xo, const float4* x, const float4* __restrict__ out,
+                                          const float4* __restrict__ z, const float4* __restrict__ known,
+                                          const float4* __restrict__ mask, const float* __restrict__ coef,
+                                          const int32_t* __restrict__ t_idx, int64_t n4, float w, float lo, float hi,
+                                          int philox, uint64_t seed, int64_t* counter_dec,
+                                          const int64_t* __restrict__ tau) {
+  const int t = *t_idx;
+  const uint64_t nt = tau ? (uint64_t)tau[t] : (uint64_t)t;
+  if (counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *counter_dec = (int64_t)t - 1;
+  const float p = coef[5 * t + 0], q = coef[5 * t + 1], A = coef[5 * t + 2], Bx = coef[5 * t + 3], sg = coef[5 * t + 4];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 xv = x[i], kn = known[i], mv = mask[i];
+    float4 e = out[i];
+    float4 zv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (t > 0) {
+      if (philox) zv = philox_normal4((uint64_t)i, nt, seed);
+      else if (z) zv = z[i];
+    }
+    if (GD) {
+      const float4 ou = out[i + n4];
+      e.x = cfg_eps(e.x, ou.x, w);
+      e.y = cfg_eps(e.y, ou.y, w);
+      e.z = cfg_eps(e.z, ou.z, w);
+      e.w = cfg_eps(e.w, ou.w, w);
+    }
+    const float4 o = p_step_x0_masked_4(xv, e, zv, kn, mv, p, q, A, Bx, sg, lo, hi);
+    xo[i] = o;
+    if (GD) xo[i + n4] = o;
+  }
+}
+
+template <bool GD>
+__global__ void p_sample_ms_masked_kernel(float4* xo, const float4* x, const float4* __restrict__ out, float4* hist,
+                                          const float4* __restrict__ known, const float4* __restrict__ mask,
+                                          const float* __restrict__ coef, const int32_t* __restrict__ t_idx,
+                                          int64_t n4, float w, float lo, float hi, int64_t* counter_dec) {
+  const int t = *t_idx;
+  if (counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *counter_dec = (int64_t)t - 1;
+  const float p = coef[5 * t + 0], q = coef[5 * t + 1], A = coef[5 * t + 2], Bx = coef[5 * t + 3], H = coef[5 * t + 4];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 xv = x[i], kn = known[i], mv = mask[i];
+    float4 e = out[i];
+    float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), x0m;
+    if (H != 0.0f) hv = hist[i];
+    if (GD) {
+      const float4 ou = out[i + n4];
+      e.x = cfg_eps(e.x, ou.x, w);
+      e.y = cfg_eps(e.y, ou.y, w);
+      e.z = cfg_eps(e.z, ou.z, w);
+      e.w = cfg_eps(e.w, ou.w, w);
+    }
+    const float4 o = p_step_ms_masked_4(xv, e, hv, kn, mv, p, q, A, Bx, H, lo, hi, &x0m);
+    xo[i] = o;
+    if (GD) xo[i + n4] = o;
+    hist[i] = x0m;
+  }
+}
+
+// The arguments of tdx_p_sample_step_x0 plus known / mask (n floats each); TDX_E_BADARG in its cases and for a null
+// known or mask.
+extern "C" int tdx_p_sample_step_x0_masked(float* x_out, const float* x, const float* out, const float* z,
+                                           const float* known, const float* mask, const float* coef5,
+                                           const int64_t* tau, const int32_t* t_idx, int64_t n, float lo, float hi,
+                                           int use_philox, uint64_t philox_seed, int64_t* counter_dec,
+                                           tdx_stream_t stream) {
+  if (!x_out || !x || !out || !known || !mask || !coef5 || !t_idx || n <= 0 || (n % 4) || !(lo < hi))
+    return TDX_E_BADARG;
+  p_sample_x0_masked_kernel<false><<<ew_grid(n / 4, 256), 256, 0, to_stream(stream)>>>(
+      (float4*)x_out, (const float4*)x, (const float4*)out, (const float4*)z, (const float4*)known, (const float4*)mask,
+      coef5, t_idx, n / 4, 0.f, lo, hi, use_philox != 0, philox_seed, counter_dec, tau);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tdx_p_sample_step_x0_guided_masked(float* x, const float* out, const float* z, const float* known,
+                                                  const float* mask, const float* coef5, const int64_t* tau,
+                                                  const int32_t* t_idx, int64_t n_half_elems, float w, float lo,
+                                                  float hi, int use_philox, uint64_t philox_seed, int64_t* counter_dec,
+                                                  tdx_stream_t stream) {
+  if (!x || !out || !known || !mask || !coef5 || !t_idx || n_half_elems <= 0 || (n_half_elems % 4) || !(lo < hi))
+    return TDX_E_BADARG;
+  p_sample_x0_masked_kernel<true><<<ew_grid(n_half_elems / 4, 256), 256, 0, to_stream(stream)>>>(
+      (float4*)x, (const float4*)x, (const float4*)out, (const float4*)z, (const float4*)known, (const float4*)mask,
+      coef5, t_idx, n_half_elems / 4, w, lo, hi, use_philox != 0, philox_seed, counter_dec, tau);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+// The arguments of tdx_p_sample_step_ms plus known / mask; hist receives the blended prediction.
+extern "C" int tdx_p_sample_step_ms_masked(float* x_out, const float* x, const float* out, float* hist,
+                                           const float* known, const float* mask, const float* coef5,
+                                           const int32_t* t_idx, int64_t n, float lo, float hi, int64_t* counter_dec,
+                                           tdx_stream_t stream) {
+  if (!x_out || !x || !out || !hist || !known || !mask || !coef5 || !t_idx || n <= 0 || (n % 4) || !(lo < hi))
+    return TDX_E_BADARG;
+  p_sample_ms_masked_kernel<false><<<ew_grid(n / 4, 256), 256, 0, to_stream(stream)>>>(
+      (float4*)x_out, (const float4*)x, (const float4*)out, (float4*)hist, (const float4*)known, (const float4*)mask,
+      coef5, t_idx, n / 4, 0.f, lo, hi, counter_dec);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tdx_p_sample_step_ms_guided_masked(float* x, const float* out, float* hist, const float* known,
+                                                  const float* mask, const float* coef5, const int32_t* t_idx,
+                                                  int64_t n_half_elems, float w, float lo, float hi,
+                                                  int64_t* counter_dec, tdx_stream_t stream) {
+  if (!x || !out || !hist || !known || !mask || !coef5 || !t_idx || n_half_elems <= 0 || (n_half_elems % 4) ||
+      !(lo < hi))
+    return TDX_E_BADARG;
+  p_sample_ms_masked_kernel<true><<<ew_grid(n_half_elems / 4, 256), 256, 0, to_stream(stream)>>>(
+      (float4*)x, (const float4*)x, (const float4*)out, (float4*)hist, (const float4*)known, (const float4*)mask, coef5,
+      t_idx, n_half_elems / 4, w, lo, hi, counter_dec);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
 // Device-side step counter for graph-captured sampling: t = *counter; t_idx = t; t_vec[:] = t;
 // *counter = t - 1.  One block; lets a HIP graph hold several consecutive reverse steps with no
 // host work between them (diffusion.py:259-260 builds the same t tensor on the host each step).

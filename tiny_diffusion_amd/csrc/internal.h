@@ -23,7 +23,8 @@ int tdx_final_conv_fwd_psample(const void* in, const float* w, const float* bias
                                uint64_t seed, int philox, int64_t* counter_dec, hipStream_t st, int io16 = 0,
                                int64_t elem0 = 0, const int64_t* tau = nullptr, int guided = 0, float gw = 0.f,
                                int x0 = 0, float lo = 0.f, float hi = 0.f,   // x0 = 1: the (S,5) table and the clamp of p_step_x0
-                               float* hist = nullptr);   // x0 = 2: the (S,5) table of p_step_ms, its clamp and its history
+                               float* hist = nullptr,   // x0 = 2: the (S,5) table of p_step_ms, its clamp and its history
+                               const float* known = nullptr, const float* mask = nullptr);   // x0 != 0, both or neither: the masked update (inpainting)
 int tdx_final_conv_dgrad(const float* g_out, const float* w, void* g_in, int B, int H, int W,
                          int cout, hipStream_t st, int io16 = 0);
 int tdx_final_conv_wgrad(const void* in, const float* g_out, float* partial, float* dw, float* db,

@@ -229,7 +229,7 @@ struct tdx_unet {
   const int64_t* tab_tau;   // timestep schedule the T rows were built at (tdx_unet_prepare_sampling_sched); null: t = 0..T-1
   bool skip_time_path;   // set by tdx_unet_eval_step around its forward: the projections are already in the workspace
   // set by tdx_unet_eval_step around its forward: final_conv applies the reverse-process update in its epilogue
-  struct PS { float* x; const float* z; const float* coef; const int32_t* t_idx; uint64_t seed; int philox; int64_t* counter_dec; int64_t elem0; const int64_t* tau; int guided; float w; int x0; float lo, hi; float* hist; } ps;   // x0: 1 = coef is the (S,5) table of the clipped-x0 update, lo / hi its clamp; 2 = the multistep table, hist its history
+  struct PS { float* x; const float* z; const float* coef; const int32_t* t_idx; uint64_t seed; int philox; int64_t* counter_dec; int64_t elem0; const int64_t* tau; int guided; float w; int x0; float lo, hi; float* hist; const float* known; const float* mask; } ps;   // x0: 1 = coef is the (S,5) table of the clipped-x0 update, lo / hi its clamp; 2 = the multistep table, hist its history; known / mask (x0 != 0): the masked update, indexed like hist
   bool whole_batch;      // set by a guided eval step around its forward: the two halves of a guided batch are not the halves of "sample_halves"
   // half-batch inference (tdx_unet_forward, INFER mode): the second half runs on this stream, forked from / joined to the caller's
   hipStream_t half_own;
@@ -931,7 +931,7 @@ static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const
   if (infer && ps.x)
     RC(tdx_final_conv_fwd_psample(ws + L.d1a, P[TDX_P_FINAL_W], P[TDX_P_FINAL_B], out, B, S.out_hw, S.out_hw, S.in_ch,
                                   ps.x, ps.z, ps.coef, ps.t_idx, ps.seed, ps.philox, ps.counter_dec, st, io16, ps.elem0,
-                                  ps.tau, ps.guided, ps.w, ps.x0, ps.lo, ps.hi, ps.hist));
+                                  ps.tau, ps.guided, ps.w, ps.x0, ps.lo, ps.hi, ps.hist, ps.known, ps.mask));
   else
     RC(tdx_final_conv_fwd(ws + L.d1a, P[TDX_P_FINAL_W], P[TDX_P_FINAL_B], out, B, S.out_hw, S.out_hw, S.in_ch, st, io16));
 
@@ -1291,16 +1291,19 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
 // x0 (tdx_unet_eval_step_x0): coef is the (S,5) table of the clipped-x0 update and lo / hi its clamp; the head, the
 // counter and the half-batch logic do not know the difference.  x0 == 2 (tdx_unet_eval_step_ms): the (S,5) table of
 // the multistep update and its history hist (z is null: the chain is deterministic); a half-batch launch indexes the
-// one history by the element's place in the whole batch (PS::elem0).
+// one history by the element's place in the whole batch (PS::elem0).  known / mask (tdx_unet_eval_step_{x0,ms}_masked;
+// x0 != 0, both or neither): the masked update, n_elems floats each, indexed like the history.
 static int eval_step_impl(tdx_unet* u, const void* const* params, void* const* buffers, float* x, const void* cond,
                           const float* z, const float* coef, const int64_t* tau, int n_steps, int64_t* counter, int32_t* t_idx,
                           int64_t* t_vec, float* eps, int64_t n_elems, void* workspace, size_t workspace_bytes,
                           int batch, uint64_t philox_seed, tdx_stream_t stream, bool guided = false, float w = 0.f,
-                          int x0 = 0, float lo = 0.f, float hi = 0.f, float* hist = nullptr) {
+                          int x0 = 0, float lo = 0.f, float hi = 0.f, float* hist = nullptr,
+                          const float* known = nullptr, const float* mask = nullptr) {
   if (!u || !x || !coef || !counter || !t_idx || !t_vec || !eps || batch <= 0 || n_elems <= 0)
     return TDX_E_BADARG;
   if (x0 && !(lo < hi)) return TDX_E_BADARG;
   if (x0 == 2 && (!hist || z)) return TDX_E_BADARG;
+  if ((known != nullptr) != (mask != nullptr) || (known && !x0)) return TDX_E_BADARG;
   if (guided) {
     if (!u->spec) return TDX_E_SHAPE;   // the UNets only
     if ((batch & 1) || 2 * n_elems != (int64_t)batch * u->spec->in_ch * u->spec->out_hw * u->spec->out_hw) return TDX_E_BADARG;
@@ -1344,7 +1347,7 @@ static int eval_step_impl(tdx_unet* u, const void* const* params, void* const* b
   // the UNets apply the update in final_conv's epilogue (one launch less); the latent MLP keeps the separate kernel
   const bool fuse_ps = u->spec && (g_tdx_sample_fuse & 4) &&
                        (guided ? 2 : 1) * n_elems == (int64_t)batch * u->spec->in_ch * u->spec->out_hw * u->spec->out_hw;
-  if (fuse_ps) u->ps = {x, z, coef, t_idx, philox_seed, z ? 0 : 1, tab ? counter : nullptr, 0, tau, guided, w, x0, lo, hi, hist};
+  if (fuse_ps) u->ps = {x, z, coef, t_idx, philox_seed, z ? 0 : 1, tab ? counter : nullptr, 0, tau, guided, w, x0, lo, hi, hist, known, mask};
   const int rc = tdx_unet_forward(u, params, buffers, x, t_vec, cond, eps, workspace, workspace_bytes, batch,
                                   TDX_MODE_INFER, stream);
   u->skip_time_path = false;
@@ -1352,6 +1355,20 @@ static int eval_step_impl(tdx_unet* u, const void* const* params, void* const* b
   u->ps = {};
   if (rc) return rc;
   if (fuse_ps) return 0;
+  if (known) {   // the separate masked kernels, exactly where the unmasked step falls back to the separate ones
+    if (x0 == 2) {
+      if (guided)
+        return tdx_p_sample_step_ms_guided_masked(x, eps, hist, known, mask, coef, t_idx, n_elems, w, lo, hi,
+                                                  tab ? counter : nullptr, stream);
+      return tdx_p_sample_step_ms_masked(x, x, eps, hist, known, mask, coef, t_idx, n_elems, lo, hi,
+                                         tab ? counter : nullptr, stream);
+    }
+    if (guided)
+      return tdx_p_sample_step_x0_guided_masked(x, eps, z, known, mask, coef, tau, t_idx, n_elems, w, lo, hi, z ? 0 : 1,
+                                                philox_seed, tab ? counter : nullptr, stream);
+    return tdx_p_sample_step_x0_masked(x, x, eps, z, known, mask, coef, tau, t_idx, n_elems, lo, hi, z ? 0 : 1,
+                                       philox_seed, tab ? counter : nullptr, stream);
+  }
   if (x0 == 2) {
     if (guided)
       return tdx_p_sample_step_ms_guided(x, eps, hist, coef, t_idx, n_elems, w, lo, hi, tab ? counter : nullptr, stream);
@@ -1437,6 +1454,33 @@ extern "C" int tdx_unet_eval_step_ms(tdx_unet* u, const void* const* params, voi
                         n_elems, workspace, workspace_bytes, batch, 0, stream, guided != 0, w, 2, lo, hi, hist);
 }
 
+// The masked steps (inpainting; see tdx_p_sample_step_x0_masked / tdx_p_sample_step_ms_masked): the arguments of
+// tdx_unet_eval_step_x0 / tdx_unet_eval_step_ms plus known / mask, n_elems floats each.  The update runs in final_conv's
+// epilogue, or in the separate masked kernels wherever the unmasked step uses the separate ones.
+extern "C" int tdx_unet_eval_step_x0_masked(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
+                                            const void* cond, const float* z, const float* coef5, const int64_t* tau,
+                                            int S, int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps,
+                                            int64_t n_elems, void* workspace, size_t workspace_bytes, int batch,
+                                            uint64_t philox_seed, int guided, float w, float lo, float hi,
+                                            const float* known, const float* mask, tdx_stream_t stream) {
+  if ((tau && S <= 0) || !known || !mask) return TDX_E_BADARG;
+  return eval_step_impl(u, params, buffers, x, cond, z, coef5, tau, tau ? S : 0, counter, t_idx, t_vec, eps, n_elems,
+                        workspace, workspace_bytes, batch, philox_seed, stream, guided != 0, w, 1, lo, hi, nullptr,
+                        known, mask);
+}
+
+extern "C" int tdx_unet_eval_step_ms_masked(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
+                                            const void* cond, const float* coef5, const int64_t* tau, int S,
+                                            int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps,
+                                            int64_t n_elems, void* workspace, size_t workspace_bytes, int batch,
+                                            int guided, float w, float lo, float hi, float* hist, const float* known,
+                                            const float* mask, tdx_stream_t stream) {
+  if ((tau && S <= 0) || !hist || !known || !mask) return TDX_E_BADARG;
+  return eval_step_impl(u, params, buffers, x, cond, nullptr, coef5, tau, tau ? S : 0, counter, t_idx, t_vec, eps,
+                        n_elems, workspace, workspace_bytes, batch, 0, stream, guided != 0, w, 2, lo, hi, hist, known,
+                        mask);
+}
+
 // Build the sampling tables for the CURRENT INFER pack (call after tdx_unet_pack / the first INFER forward, once
 // per sample() call, outside any stream capture: it may allocate).  T = number of diffusion steps (the counter
 // handed to tdx_unet_eval_step must stay below it); cond = the labels / text embeddings the eval steps will be
@@ -1495,6 +1539,15 @@ extern "C" int tdx_unet_prepare_sampling_sched(tdx_unet* u, const void* const* p
                                                const int64_t* tau, int S, tdx_stream_t stream) {
   if (!tau) return TDX_E_BADARG;
   return prepare_sampling_impl(u, params, cond, batch, S, tau, stream);
+}
+
+// Forget the sampling tables: the eval steps that follow take the direct time path (step counter, time MLP and
+// projections as launches of their own), whose results are the eager forward's bit for bit - the table look-up
+// reassociates one sum of a conditional network.  The next tdx_unet_prepare_sampling builds them again.
+extern "C" int tdx_unet_drop_sampling_tables(tdx_unet* u) {
+  if (!u) return TDX_E_BADARG;
+  u->tab_gen = -1;
+  return 0;
 }
 
 extern "C" int tdx_unet_request_input_grad(tdx_unet* u, float* g_x) {

@@ -26,7 +26,10 @@ def sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples
     """diffusion.py:254-276: leaves the model in eval mode, returns x_0 in ~[-1, 1].
     Extra keyword arguments (x_T, noises, use_graph, philox_seed, prediction, clip_denoised) are extensions;
     ``clip_denoised=True | (lo, hi)`` clamps the implied x_0 at every step (schedule.sample_loop) and returns x_0 in
-    [-1, 1] / [lo, hi] exactly."""
+    [-1, 1] / [lo, hi] exactly.  ``known=x, mask=m`` (both or neither, broadcast to ``(n_samples, *input shape)``) is
+    inpainting: every step blends the implied x_0 with ``known`` where ``mask`` is 1 (a fraction: a soft edge) and the
+    returned sample equals ``known`` there exactly; ``x_T`` stays pure noise - an image-to-image start composes from the
+    existing ``x_T=`` and ``timesteps=`` arguments and is not part of this (schedule.sample_loop)."""
     return sample_loop(noise_model, diffusion, device, n_samples, None, **kw)
 
 
@@ -35,7 +38,7 @@ def ddim_sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_sa
                 timesteps=None, **kw):
     """DDIM sampling (Song et al. 2021) of a model trained with ``diffusion``: ``sample()``'s contract over
     ``steps`` timesteps (or the explicit list ``timesteps``) with stochasticity ``eta`` (schedule.ddim_schedule).
-    The same extension keywords as ``sample()``."""
+    The same extension keywords as ``sample()``, ``known`` / ``mask`` among them."""
     return ddim_sample_loop(noise_model, diffusion, device, n_samples, None, steps=steps, eta=eta,
                             timesteps=timesteps, **kw)
 
@@ -46,6 +49,7 @@ def dpm_sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_sam
     """DPM-Solver++(2M) sampling (Lu et al. 2022): ``sample()``'s contract over ``steps`` timesteps uniform in
     log-SNR (``spacing="uniform"``: DDIM's spacing) or the explicit list ``timesteps``, deterministic, second order
     (``order=1``: deterministic DDIM), no retraining and one network evaluation per step (schedule.dpm_solver_schedule).
-    The extension keywords of ``sample()`` except ``noises``; ``philox_seed`` only selects the graph mode."""
+    The extension keywords of ``sample()`` except ``noises`` (``known`` / ``mask``: the history holds the blended
+    prediction); ``philox_seed`` only selects the graph mode."""
     return dpm_sample_loop(noise_model, diffusion, device, n_samples, None, steps=steps, order=order, spacing=spacing,
                            timesteps=timesteps, **kw)

@@ -118,7 +118,11 @@ class NoiseModel(nn.Module):
 
 @torch.no_grad()
 def sample(vae: VAE, noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples=16, y=None, **kw):
-    """diffusion_transformer.py:284-323 (identical to latent_diffusion.sample, ``clip_denoised`` included)."""
+    """diffusion_transformer.py:284-323 (identical to latent_diffusion.sample, ``clip_denoised`` included).  ``known=x, mask=m`` (through ``**kw``; both or neither, broadcast to
+    ``(n_samples, *(20,))``): inpainting - every step blends the implied z_0 with ``known`` where ``mask`` is 1 (a
+    fraction: a soft edge) and the latent z handed to the decoder equals ``known`` there exactly; ``x_T`` stays pure noise - an
+    image-to-image start composes from the existing ``x_T=`` and ``timesteps=`` arguments and is not part of this
+    (schedule.sample_loop).  ``ddim_sample`` and ``dpm_sample`` take the two keywords too."""
     _check_labels(y, n_samples)
     vae.eval()
     z = sample_loop(noise_model, diffusion, device, n_samples, y, **kw)

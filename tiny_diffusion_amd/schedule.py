@@ -529,6 +529,39 @@ def dpm_solver_schedule(diffusion: ForwardProcess, steps: Optional[int] = None, 
     return MultistepSchedule(base.num_timesteps, base.timesteps, base.coef64, order=int(order), spacing=spacing)
 
 
+def _known_mask(known, mask, n_samples: int, shape):
+    """The checked ``known`` / ``mask`` of a masked chain (inpainting): ``None`` (neither given) or the two as fp32 CPU
+    or device tensors that broadcast to ``(n_samples, *shape)`` - still unexpanded, so the check touches no device the
+    caller's tensors are not already on.  ``ValueError`` for one without the other, anything but real numbers, a shape
+    that does not broadcast, a non-finite ``known``, a ``mask`` outside [0, 1] or NaN."""
+    if known is None and mask is None:
+        return None
+    if known is None or mask is None:
+        raise ValueError("known and mask go together: give both (inpainting) or neither")
+    full = (int(n_samples),) + tuple(int(d) for d in shape)
+    out = []
+    for name, v in (("known", known), ("mask", mask)):
+        if isinstance(v, np.ndarray):
+            v = torch.from_numpy(v)
+        if not isinstance(v, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor that broadcasts to {full}, got {type(v).__name__}")
+        if v.is_complex():
+            raise ValueError(f"{name} must hold real numbers")
+        try:
+            ok = tuple(torch.broadcast_shapes(tuple(v.shape), full)) == full
+        except RuntimeError:
+            ok = False
+        if not ok:
+            raise ValueError(f"{name} of shape {tuple(v.shape)} does not broadcast to {full}")
+        out.append(v.detach().to(torch.float32))
+    kn, mk = out
+    if kn.numel() and not bool(torch.isfinite(kn).all()):
+        raise ValueError("known must be finite")
+    if mk.numel() and not bool(((mk >= 0) & (mk <= 1)).all()):   # a NaN fails both comparisons
+        raise ValueError("mask must lie in [0, 1] (1 keeps the known value, 0 generates; NaN is not allowed)")
+    return kn, mk
+
+
 def _guidance_scale(noise_model, guidance_scale, y) -> float:
     """The checked scale w of a guided chain: a finite number, on a conditional UNet, with a condition."""
     arch = getattr(noise_model, "_arch", None)
@@ -544,15 +577,20 @@ def _guidance_scale(noise_model, guidance_scale, y) -> float:
     return float(guidance_scale)
 
 
+def _in_shape(noise_model):
+    return tuple(getattr(getattr(noise_model, "_arch", None), "in_shape", (1, 28, 28)))
+
+
 def ddim_sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, y=None, steps: int = 50,
                      eta: float = 0.0, timesteps=None, **kw):
     """``sample_loop`` on ``ddim_schedule(diffusion, steps | timesteps, eta)``: ``timesteps``, when given,
     replaces ``steps``.  The drop-in modules' ``ddim_sample`` functions call this (``guidance_scale`` and the other
-    keywords of ``sample_loop`` pass through, ``prediction`` among them)."""
+    keywords of ``sample_loop`` pass through, ``prediction`` and ``known`` / ``mask`` among them)."""
     _prediction(kw.get("prediction", "eps"))
     _clip_denoised(kw.get("clip_denoised"))
     if kw.get("guidance_scale") is not None:
         _guidance_scale(noise_model, kw["guidance_scale"], y)   # an argument error comes before the schedule's
+    _known_mask(kw.get("known"), kw.get("mask"), n_samples, _in_shape(noise_model))
     sched = ddim_schedule(diffusion, steps=None if timesteps is not None else steps, timesteps=timesteps, eta=eta)
     return sample_loop(noise_model, diffusion, device, n_samples, y, schedule=sched, **kw)
 
@@ -561,9 +599,9 @@ def dpm_sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: i
                     order: int = 2, spacing: str = "logsnr", timesteps=None, **kw):
     """``sample_loop`` on ``dpm_solver_schedule(diffusion, steps | timesteps, order, spacing)``: the deterministic
     DPM-Solver++(2M) chain; ``timesteps``, when given, replaces ``steps``.  The drop-in modules' ``dpm_sample``
-    functions call this; ``guidance_scale``, ``prediction``, ``clip_denoised``, ``x_T``, ``use_graph`` and
-    ``philox_seed`` (which only selects the device-counter graph mode: there is no noise) pass through.  Every
-    argument error comes before any GPU work."""
+    functions call this; ``guidance_scale``, ``prediction``, ``clip_denoised``, ``known`` / ``mask``, ``x_T``,
+    ``use_graph`` and ``philox_seed`` (which only selects the device-counter graph mode: there is no noise) pass
+    through.  Every argument error comes before any GPU work."""
     _prediction(kw.get("prediction", "eps"))
     _clip_denoised(kw.get("clip_denoised"))
     if kw.get("guidance_scale") is not None:
@@ -572,6 +610,7 @@ def dpm_sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: i
         raise ValueError("a multistep chain is deterministic: it takes no noises")
     if "schedule" in kw:
         raise ValueError("dpm_sample builds its own schedule: give steps or timesteps")
+    _known_mask(kw.get("known"), kw.get("mask"), n_samples, _in_shape(noise_model))
     sched = dpm_solver_schedule(diffusion, steps=None if timesteps is not None else steps, timesteps=timesteps,
                                 order=order, spacing=spacing)
     return sample_loop(noise_model, diffusion, device, n_samples, y, schedule=sched, **kw)
@@ -581,7 +620,8 @@ def dpm_sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: i
 def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, y=None,
                 x_T: Optional[torch.Tensor] = None, noises=None, use_graph: bool = False,
                 philox_seed: Optional[int] = None, schedule: Optional[TimestepSchedule] = None,
-                guidance_scale: Optional[float] = None, prediction: str = "eps", clip_denoised=None):
+                guidance_scale: Optional[float] = None, prediction: str = "eps", clip_denoised=None,
+                known=None, mask=None):
     """Reverse process, diffusion.py:254-276.
 
     Default (``x_T is None and noises is None``): the reference's RNG consumption -
@@ -616,6 +656,21 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
     clamped x0 of the step before), in the same three modes, guided or not, for either ``prediction``.  No noise is
     drawn or read: ``noises`` raises ``ValueError`` and ``philox_seed`` only selects the device-counter mode.
     ``clip_denoised=None`` passes infinite bounds (they never bind).
+    ``known`` / ``mask``: ``None`` (both: the code paths above, unchanged - every launch, table and allocation) or
+    two tensors that broadcast to ``(n_samples, *input shape)`` - inpainting with the unchanged model (Song et al. 2021
+    I.2; Lugmayr et al. 2022): ``mask = 1`` keeps ``known``, ``0`` generates, a fraction in between is a soft edge.
+    Every step blends the (clamped) implied x0, ``x0m = (1 - mask) x0c + mask known``, and steps from the blend, on the
+    x0 form (``clip_denoised=None``: infinite bounds; ``schedule=None``: ``ddpm_schedule(diffusion)``) or the multistep
+    form (whose history is the blend) and the masked kernels, in the same three modes, guided (``known`` / ``mask`` have
+    n rows, not 2n) or not, for either ``prediction``.  The known region steps from ``x0 = known`` with the chain's own
+    ``x`` and noise - no second noise stream - and on a deterministic chain stays on the forward marginal
+    ``a_k known + b_k eps0``; the returned sample equals ``known`` bit for bit wherever ``mask == 1``.  ``x_T`` stays
+    pure noise: an image-to-image start composes from the existing ``x_T=`` and ``timesteps=`` arguments and is not part
+    of this.  Both are expanded once per call to contiguous fp32 device tensors, outside every graph capture.  The three
+    modes of a masked chain return the same bits under one ``philox_seed``; for that the device-counter mode of a
+    conditional UNet runs its time path as launches instead of the table look-up (which reassociates one sum).
+    ``ValueError``, before any GPU work of the chain, for one without the other, a shape that does not broadcast, a
+    non-finite ``known``, a ``mask`` outside [0, 1] or NaN.
     """
     prediction = _prediction(prediction)
     clip = _clip_denoised(clip_denoised)
@@ -624,6 +679,8 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
         raise ValueError("a multistep chain is deterministic: it takes no noises")
     guided = guidance_scale is not None
     w = _guidance_scale(noise_model, guidance_scale, y) if guided else None
+    shape = _in_shape(noise_model)
+    km = _known_mask(known, mask, n_samples, shape)
     device = torch.device(device)
     if device.type != "cuda":
         raise _lib.TdxError("sampling runs on the GPU only (no CPU fallback)")
@@ -632,12 +689,14 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
                          f"T = {diffusion.num_timesteps}")
     if ms:   # the multistep form takes the prediction itself, and "no clipping" is a clamp that never binds
         clip = (-math.inf, math.inf) if clip is None else clip
+    elif km is not None:   # a masked chain runs in x0 form, like the multistep chain: no clipping is infinite bounds
+        clip = (-math.inf, math.inf) if clip is None else clip
+        schedule = ddpm_schedule(diffusion) if schedule is None else schedule
     elif clip is not None:   # the x0 form takes the eps-form rows and the prediction itself: no for_prediction
         schedule = ddpm_schedule(diffusion) if schedule is None else schedule
     elif prediction != "eps":
         schedule = (ddpm_schedule(diffusion) if schedule is None else schedule).for_prediction(diffusion, prediction)
     noise_model.eval()
-    shape = tuple(getattr(getattr(noise_model, "_arch", None), "in_shape", (1, 28, 28)))
     x = (torch.randn(n_samples, *shape) if x_T is None else x_T).to(device).float().contiguous()
     if y is not None:
         y = y.to(device)
@@ -672,11 +731,31 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
     # the chain: the chain's own first step overwrites it without reading it.  The buffer is allocated here, outside
     # every capture, so it lives across graph replays and the tail graph.
     hist = torch.empty_like(x[:n_samples]) if ms else None
+    # Inpainting: one fp32 value per element of the n samples (guided or not), expanded once, outside every capture.
+    kn, mk = (None, None) if km is None else tuple(
+        v.to(device).expand(n_samples, *shape).contiguous() for v in km)
 
     def update(eps, z):
         """x <- c1 (x - c2 eps) + sigma z, elementwise and in place; Philox noise in the kernel under a seed."""
         xp, ep, cp, kp, n = x.data_ptr(), eps.data_ptr(), coef.data_ptr(), t_idx.data_ptr(), x.numel()
-        if ms:   # x <- A clamp(p x + q out) + Bx x + H hist, hist <- the clamped x0
+        if kn is not None and ms:   # the multistep update from the blend x0m = (1 - mask) x0c + mask known; hist <- x0m
+            if guided:
+                check(lib.tdx_p_sample_step_ms_guided_masked(xp, ep, hist.data_ptr(), kn.data_ptr(), mk.data_ptr(), cp,
+                                                             kp, half, w, lo, hi, None, st()),
+                      "tdx_p_sample_step_ms_guided_masked")
+            else:
+                check(lib.tdx_p_sample_step_ms_masked(xp, xp, ep, hist.data_ptr(), kn.data_ptr(), mk.data_ptr(), cp, kp,
+                                                      n, lo, hi, None, st()), "tdx_p_sample_step_ms_masked")
+        elif kn is not None:   # the x0-form update from the blend
+            ph = (int(philox_seed is not None), philox_seed or 0, None, st())
+            if guided:
+                check(lib.tdx_p_sample_step_x0_guided_masked(xp, ep, z, kn.data_ptr(), mk.data_ptr(), cp,
+                                                             tau.data_ptr(), kp, half, w, lo, hi, *ph),
+                      "tdx_p_sample_step_x0_guided_masked")
+            else:
+                check(lib.tdx_p_sample_step_x0_masked(xp, xp, ep, z, kn.data_ptr(), mk.data_ptr(), cp, tau.data_ptr(),
+                                                      kp, n, lo, hi, *ph), "tdx_p_sample_step_x0_masked")
+        elif ms:   # x <- A clamp(p x + q out) + Bx x + H hist, hist <- the clamped x0
             if guided:
                 check(lib.tdx_p_sample_step_ms_guided(xp, ep, hist.data_ptr(), cp, kp, half, w, lo, hi, None, st()),
                       "tdx_p_sample_step_ms_guided")
@@ -747,9 +826,11 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
             def run():
                 for _ in range(k):
                     if one_call:  # step counter + eps_theta + update behind one C-ABI entry
+                        # (the two keywords only on a masked chain: an unmasked one makes the call it always made)
+                        mkw = {} if kn is None else {"known": kn, "mask": mk}
                         noise_model._run_eval_step(x, y_dev, coef, counter, t_idx, t_vec, eps_buf,
                                                    philox_seed=philox_seed, tau=tau, S=S, guidance_scale=w,
-                                                   clip=clip, hist=hist)
+                                                   clip=clip, hist=hist, **mkw)
                     else:
                         step_begin(counter)
                         step_kernels(False)
@@ -758,7 +839,13 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
         if one_call and hasattr(noise_model, "_prepare_sampling"):
             # per-t / per-sample tables of the (linear) time projections: one look-up kernel per reverse step in
             # place of the step counter, the time MLP and the projections (tdx_unet_prepare_sampling)
-            noise_model._prepare_sampling(x, y_dev, S, tau=tau)
+            # A masked chain under a condition stays on the direct time path: the look-up adds the time and the condition
+            # projection in another order than the forward does (one fp32 sum reassociated), and a masked chain is
+            # promised to return the same bits in every mode.  Without a condition the look-up is exact.
+            if kn is not None and y_dev is not None and hasattr(noise_model, "_drop_sampling_tables"):
+                noise_model._drop_sampling_tables(x)
+            else:
+                noise_model._prepare_sampling(x, y_dev, S, tau=tau)
         unroll = min(GRAPH_STEPS, S)
         counter.fill_(S - 1)
         graph = capture(steps(unroll), steps(1), counter)
