@@ -446,7 +446,8 @@ int tdx_conv3x3_wgrad_bf16(const float* in, const float* dy, float* dw_slabs,
  * with Chan's parallel-variance formula in double precision.
  *   training != 0: batch statistics (biased var to normalise, unbiased into
  *                  running_var, momentum 0.1, num_batches_tracked += 1)
- *   training == 0: scale/shift from the running statistics. */
+ *   training == 0: scale/shift from the running statistics.
+ * C % 4 == 0 (the kernel reads four channels of a tile at once); TDX_E_SHAPE otherwise, nothing is written. */
 int tdx_bn_finalize(const float* stats_partial, int tiles, int tile_rows, int64_t count, int C,
                     const float* gamma, const float* beta,
                     float* running_mean, float* running_var, int64_t* num_batches_tracked,
@@ -462,7 +463,10 @@ int tdx_bn_apply_relu_fwd(const float* y, float* out, int64_t rows, int C, const
 /* BN+ReLU backward, in place on g (B*H*W, C):
  *   gz = g * [y*scale+shift > 0];  dgamma = sum gz*xhat;  dbeta = sum gz
  *   training: g <- gamma*rstd*(gz - dbeta/N - xhat*dgamma/N)   else g <- gz*scale
- * Also returns dbias = column sums of the result (gradient of the conv bias). */
+ * Also returns dbias = column sums of the result (gradient of the conv bias).
+ * Widths: C in {4, 8, 16, 32, 64, 128, 256, 512, 1024} (C % 4 == 0, C <= 1024, 256 % (C / 4) == 0: a workgroup of 256
+ * threads holds whole rows).  Any other C: TDX_E_SHAPE, and tdx_bn_relu_bwd_scratch_floats returns 0.
+ * scratch: tdx_bn_relu_bwd_scratch_floats(rows, C) floats. */
 int tdx_bn_relu_bwd(float* g, const float* y, int64_t rows, int C,
                     const float* scale, const float* shift, const float* save_mean,
                     const float* save_rstd, const float* gamma,
@@ -487,7 +491,13 @@ int tdx_bilinear_ac_fwd(const float* in, const float* scale, const float* shift,
                         const float* addend, float* out,
                         int B, int Hi, int Wi, int Ho, int Wo, int C,
                         int out_cstride, int out_coff, tdx_stream_t stream);
-/* Transposed resize: g_in (B,Hi,Wi,C) from g_out slice (B,Ho,Wo,[coff:coff+C]). */
+/* Transposed resize: g_in (B,Hi,Wi,C) from g_out slice (B,Ho,Wo,[coff:coff+C]).
+ * Contributor limit: an input index may receive from at most 8 contributing outputs per axis.  It is decided per axis on
+ * the candidate window of every input index i, [floor((i-1)/s) - 1, ceil((i+1)/s) + 1] clipped to the output, with
+ * s = (n_in-1)/(n_out-1) in fp32 (s == 0, i.e. n_in == 1 or n_out == 1: the whole output): more than 8 candidates for any
+ * i returns TDX_E_SHAPE and leaves g_in untouched.  n_out <= 2 n_in always passes (every resize of the networks);
+ * 2 -> 9, 1 -> 9, 3 -> 9 and 4 -> 14 are among the smallest that do not.  tdx_bilinear_ac_fwd has no such limit.
+ * Both entries: C, cstride and coff multiples of 4, coff + C <= cstride; TDX_E_SHAPE otherwise. */
 int tdx_bilinear_ac_bwd(const float* g_out, float* g_in,
                         int B, int Hi, int Wi, int Ho, int Wo, int C,
                         int g_cstride, int g_coff, tdx_stream_t stream);

@@ -106,7 +106,8 @@ extern "C" int tdx_bn_finalize(const float* stats_partial, int tiles, int tile_r
   if (training && ((int64_t)tiles * tile_rows < count || (int64_t)(tiles - 1) * tile_rows >= count))
     return TDX_E_BADARG;
   if (!training && (!running_mean || !running_var)) return TDX_E_BADARG;
-  bn_finalize_kernel<<<cdiv(C, 4), 256, 0, to_stream(stream)>>>(
+  if (C % 4) return TDX_E_SHAPE;   // the kernel reads float4 = 4 channels of a tile
+  bn_finalize_kernel<<<C / 4, 256, 0, to_stream(stream)>>>(
       stats_partial, tiles, tile_rows, count, C, gamma, beta, running_mean, running_var,
       num_batches_tracked, scale, shift, save_mean, save_rstd, training);
   TDX_CHECK_LAUNCH();
