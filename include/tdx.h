@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define TDX_VERSION 400 /* 0.4.0: additions: tdx_step_begin_sched, tdx_p_sample_step_sched{,_philox}, tdx_unet_prepare_sampling_sched, tdx_unet_eval_step_sched (timestep schedules: DDIM sampling); tdx_pack_conv3x3_tiled, tdx_conv3x3_fwd_infer, tdx_conv3x3_infer_scratch_floats (the inference convolution of the reverse process), tdx_linear_{fwd,bwd}_prec; tdx_unet_set_precision accepts TDX_PREC_BF16 for the latent MLP.  0.3.0: tdx_diag_set_buffer takes the buffer size (incompatible); additions: tdx_timestep_embedding_f32, tdx_initial_conv_input_grad, tdx_unet_request_input_grad; time_dim of any width */
+#define TDX_VERSION 400 /* 0.4.0: additions: tdx_step_begin_sched, tdx_p_sample_step_sched{,_philox}, tdx_unet_prepare_sampling_sched, tdx_unet_eval_step_update (timestep schedules: DDIM sampling); tdx_pack_conv3x3_tiled, tdx_conv3x3_fwd_infer, tdx_conv3x3_infer_scratch_floats (the inference convolution of the reverse process), tdx_linear_{fwd,bwd}_prec; tdx_unet_set_precision accepts TDX_PREC_BF16 for the latent MLP.  0.3.0: tdx_diag_set_buffer takes the buffer size (incompatible); additions: tdx_timestep_embedding_f32, tdx_initial_conv_input_grad, tdx_unet_request_input_grad; time_dim of any width */
 
 #define TDX_E_BADARG (-1)   /* null pointer, size <= 0, batch > plan capacity ... */
 #define TDX_E_SHAPE (-2)    /* shape the kernel family does not cover */
@@ -181,6 +181,19 @@ int tdx_p_sample_step_ms_masked(float* x_out, const float* x, const float* out, 
 int tdx_p_sample_step_ms_guided_masked(float* x, const float* out, float* hist, const float* known, const float* mask,
                                        const float* coef5, const int32_t* t_idx, int64_t n_half_elems, float w,
                                        float lo, float hi, int64_t* counter_dec, tdx_stream_t stream);
+
+/* Every update above behind one entry.  form: the table's rows and the update - TDX_STEP_EPS (S,3) rows (c1, c2, sigma),
+ * TDX_STEP_X0 (S,5) rows (p, q, A, Bx, sigma), TDX_STEP_MS (S,5) rows (p, q, A, Bx, H).  n: the elements of x_out / z /
+ * hist / known / mask; guided != 0: x and out hold 2n (x_out == x).  Nullable: tau (identity chain), z (no noise; ignored
+ * when use_philox), hist (required by MS, which takes no z), known / mask (both or neither, X0 / MS only), counter_dec.
+ * lo < hi is required by X0 / MS.  Anything else - a null pointer, n <= 0, n % 4 - is TDX_E_BADARG; nothing is written. */
+#define TDX_STEP_EPS 0
+#define TDX_STEP_X0 1
+#define TDX_STEP_MS 2
+int tdx_p_sample_update(float* x_out, const float* x, const float* out, int64_t n, int form, const float* coef,
+                        const int32_t* t_idx, const int64_t* tau, const float* z, int use_philox, uint64_t philox_seed,
+                        int guided, float w, float lo, float hi, float* hist, const float* known, const float* mask,
+                        int64_t* counter_dec, tdx_stream_t stream);
 
 /* Condition dropout for training the unconditional branch: sample b is dropped iff a Philox uniform in [0,1) keyed by
  * (seed, offset, b) is < p (p == 0: exact copy, p == 1: every sample).  A dropped sample gets label -1 / a zeroed row.
@@ -752,60 +765,31 @@ int tdx_unet_prepare_sampling(tdx_unet* u, const void* const* params, const void
  * what an eager forward computes bit for bit, until tables are prepared again.  No launch, no allocation. */
 int tdx_unet_drop_sampling_tables(tdx_unet* u);
 
-/* The same two entries for a timestep schedule of S steps (tau: device int64 [S], see tdx_step_begin_sched):
- * prepare builds S table rows at the timesteps tau[0..S) (rebuilt on every call), and the scheduled eval step
- * runs eps_theta(x, tau[k]) and the update of coefficient row k (coef: (S,3)); the counter holds k.  A table built
+/* The tables of a timestep schedule of S steps (tau: device int64 [S], see tdx_step_begin_sched): S table rows at
+ * the timesteps tau[0..S) (rebuilt on every call); a scheduled eval step (tdx_unet_eval_step_update with tau) runs
+ * eps_theta(x, tau[k]) and the update of coefficient row k; the counter holds k.  A table built
  * for one schedule (or for none) serves only eval steps with the same tau pointer and S: otherwise the step takes
  * the direct path. */
 int tdx_unet_prepare_sampling_sched(tdx_unet* u, const void* const* params, const void* cond, int batch,
                                     const int64_t* tau, int S, tdx_stream_t stream);
-int tdx_unet_eval_step_sched(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
-                             const void* cond, const float* z, const float* coef, const int64_t* tau, int S,
-                             int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
-                             void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed,
-                             tdx_stream_t stream);
-/* The guided reverse step (see tdx_p_sample_step_guided): batch = 2n rows of x / cond / eps whose second half carries
- * the null condition, n_elems = the FIRST half's elements, z = n rows or NULL (Philox).  tau == NULL: the identity
- * chain of tdx_unet_eval_step (S ignored).  Tables are prepared at batch 2n with the 2n-row cond.  The UNets only
- * (the latent MLP returns TDX_E_SHAPE); the "sample_halves" knob does not apply. */
-int tdx_unet_eval_step_guided(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
+/* The reverse step with any update of tdx_p_sample_update: tdx_unet_eval_step's arguments plus
+ *   tau, S    the schedule (tau == NULL: the identity chain, S ignored; tau != NULL needs S > 0),
+ *   form      TDX_STEP_EPS | TDX_STEP_X0 | TDX_STEP_MS, the kind of table coef is,
+ *   guided, w classifier-free guidance: batch = 2n rows of x / cond / eps whose second half carries the null condition,
+ *             n_elems = the FIRST half's elements, z = n rows or NULL (Philox); tables are prepared at batch 2n with
+ *             the 2n-row cond; the UNets only (the latent MLP returns TDX_E_SHAPE), no half-batch forward,
+ *   lo, hi    the clamp of X0 / MS,
+ *   hist      MS: the history, n_elems floats kept by the caller from step to step (MS takes no z),
+ *   known, mask   X0 / MS, both or neither: inpainting, n_elems floats each (a half-batch forward indexes them, like
+ *             the history, by the element's place in the whole batch).
+ * Sampling tables, the counter and the half-batch forward as in tdx_unet_eval_step.  The update runs in final_conv's
+ * epilogue, or as tdx_p_sample_update when the epilogue is switched off (knob "sample_fuse") and for the latent MLP. */
+int tdx_unet_eval_step_update(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
                               const void* cond, const float* z, const float* coef, const int64_t* tau, int S,
                               int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
-                              void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed, float w,
-                              tdx_stream_t stream);
-
-/* The clipped-x0 reverse step (see tdx_p_sample_step_x0): the arguments of tdx_unet_eval_step_guided with coef5 the
- * (S,5) table and the clamp [lo, hi].  guided == 0: an unguided step of any model (w ignored, n_elems = all of x);
- * guided != 0: batch = 2n, n_elems = the first half's (the UNets only).  tau == NULL: the identity chain (S ignored).
- * Sampling tables, the counter and the half-batch forward as in the other eval steps. */
-int tdx_unet_eval_step_x0(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
-                          const void* cond, const float* z, const float* coef5, const int64_t* tau, int S,
-                          int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
-                          void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed, int guided, float w,
-                          float lo, float hi, tdx_stream_t stream);
-
-/* The multistep reverse step (see tdx_p_sample_step_ms): the arguments of tdx_unet_eval_step_x0 without z and
- * philox_seed (the chain is deterministic) plus the history hist (n_elems floats, kept by the caller from step to
- * step).  coef5 is the (S,5) table (p, q, A, Bx, H). */
-int tdx_unet_eval_step_ms(tdx_unet* u, const void* const* params, void* const* buffers, float* x, const void* cond,
-                          const float* coef5, const int64_t* tau, int S, int64_t* counter, int32_t* t_idx,
-                          int64_t* t_vec, float* eps, int64_t n_elems, void* workspace, size_t workspace_bytes,
-                          int batch, int guided, float w, float lo, float hi, float* hist, tdx_stream_t stream);
-
-/* The masked reverse steps (inpainting; see tdx_p_sample_step_x0_masked): the arguments of tdx_unet_eval_step_x0 /
- * tdx_unet_eval_step_ms plus known and mask, n_elems floats each (a half-batch forward indexes them by the element's
- * place in the whole batch, as it does the history).  TDX_E_BADARG also for a null known or mask. */
-int tdx_unet_eval_step_x0_masked(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
-                                 const void* cond, const float* z, const float* coef5, const int64_t* tau, int S,
-                                 int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
-                                 void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed, int guided,
-                                 float w, float lo, float hi, const float* known, const float* mask,
-                                 tdx_stream_t stream);
-int tdx_unet_eval_step_ms_masked(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
-                                 const void* cond, const float* coef5, const int64_t* tau, int S, int64_t* counter,
-                                 int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems, void* workspace,
-                                 size_t workspace_bytes, int batch, int guided, float w, float lo, float hi,
-                                 float* hist, const float* known, const float* mask, tdx_stream_t stream);
+                              void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed, int form,
+                              int guided, float w, float lo, float hi, float* hist, const float* known,
+                              const float* mask, tdx_stream_t stream);
 
 /* Testing aid: offset (in floats) and element count of a named intermediate inside the
  * workspace after a forward: "x0", "Y0".."Y12", "ss0".."ss12", "e1p", "cat1", "d1a", ... */

@@ -11,7 +11,7 @@ NUM_CLASSES = 10
 SHAPES = {"uncond": (1, 28, 28), "cond": (1, 28, 28), "laion": (4, 32, 32), "latent": (20,), "transformer": (20,)}
 
 
-# ---------------------------------------------------------------- the blend and the two updates, fp32 on the CPU
+# ---------------------------------------------------------------- the blend and the x0-form updates, fp32 on the CPU
 def blend32(x0c, known, m):
     """x0_blend of csrc/common.h: (1 - m) * x0c + m * known, each operation rounded separately in fp32."""
     one = torch.tensor(1.0, dtype=torch.float32)
@@ -26,8 +26,32 @@ def clamp32(x0, lo, hi):
     return torch.minimum(torch.maximum(x0, torch.tensor(lo)), torch.tensor(hi))
 
 
+def cpu_x0_step(x, out, z, row, lo, hi, k, w=None):
+    """The x0-form update (pstep_elem, TDX_STEP_X0), every product and sum a separate torch op in the kernel's order:
+    returns (x', x0)."""
+    p, q, A, Bx, sg = row.unbind()
+    if w is not None:
+        n = x.shape[0]
+        out = cfg32(out[:n], out[n:], w)
+    x0 = p * x + q * out
+    zz = z if (z is not None and k > 0) else torch.zeros_like(x)
+    return (A * clamp32(x0, lo, hi) + Bx * x) + sg * zz, x0
+
+
+def cpu_ms_step(x, out, hist, row, lo, hi):
+    """The multistep update (pstep_elem, TDX_STEP_MS) likewise; the H term only when H != 0.  Returns (x', the clamped
+    x0, x0)."""
+    p, q, A, Bx, H = row.unbind()
+    x0 = p * x + q * out
+    x0c = clamp32(x0, lo, hi)
+    r = A * x0c + Bx * x
+    if H.item() != 0.0:
+        r = r + H * hist
+    return r, x0c, x0
+
+
 def cpu_x0_masked_step(x, out, z, known, m, row, lo, hi, k, w=None):
-    """p_step_x0_masked: returns (x', x0, x0m)."""
+    """cpu_x0_step with the blend between the clamp and the step: returns (x', x0, x0m)."""
     p, q, A, Bx, sg = row.unbind()
     if w is not None:
         n = x.shape[0]
@@ -39,7 +63,7 @@ def cpu_x0_masked_step(x, out, z, known, m, row, lo, hi, k, w=None):
 
 
 def cpu_ms_masked_step(x, out, hist, known, m, row, lo, hi, w=None):
-    """p_step_ms_masked: returns (x', x0, x0m); the history term only at H != 0."""
+    """cpu_ms_step with the blend: returns (x', x0, x0m); the history term only at H != 0."""
     p, q, A, Bx, H = row.unbind()
     if w is not None:
         n = x.shape[0]
@@ -50,6 +74,27 @@ def cpu_ms_masked_step(x, out, hist, known, m, row, lo, hi, w=None):
     if H.item() != 0.0:
         r = r + H * hist
     return r, x0, x0m
+
+
+# ---------------------------------------------------------------- which update a sampler asked for
+def spy_entries(monkeypatch, lib, names, calls):
+    """Append the name of every call of the C entries ``names`` to ``calls``.  The two entries that take every update
+    are recorded with the update the call asks for - its form, ``sched`` under a timestep schedule, ``guided``,
+    ``masked`` - as in ``tdx_p_sample_update[x0,sched,guided,masked]``."""
+    where = {"tdx_p_sample_update": (4, 7, 11, 16), "tdx_unet_eval_step_update": (18, 7, 19, 24)}   # form, tau, guided, known
+
+    def spy(real, name):
+        def call(*a):
+            tag = name
+            if name in where:
+                f, t, g, k = where[name]
+                tag += "[" + ",".join([("eps", "x0", "ms")[a[f]]] + ["sched"] * (a[t] is not None) + ["guided"] * bool(a[g])
+                                      + ["masked"] * (a[k] is not None)) + "]"
+            calls.append(tag)
+            return real(*a)
+        return call
+    for name in names:
+        monkeypatch.setattr(lib, name, spy(getattr(lib, name), name))
 
 
 # ---------------------------------------------------------------- masks and known data

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ("tdx_p_sample_step_guided", "tdx_unet_eval_step_guided", "tdx_cond_drop_labels", "tdx_cond_drop_rows")
+NEW_SYMBOLS = ("tdx_p_sample_step_guided", "tdx_unet_eval_step_update", "tdx_cond_drop_labels", "tdx_cond_drop_rows")
 
 
 def test_new_symbols_declared_listed_and_exported():

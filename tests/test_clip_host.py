@@ -9,7 +9,7 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ("tdx_p_sample_step_x0", "tdx_p_sample_step_x0_guided", "tdx_unet_eval_step_x0")
+NEW_SYMBOLS = ("tdx_p_sample_step_x0", "tdx_p_sample_step_x0_guided", "tdx_unet_eval_step_update")
 INF = float("inf")
 
 

@@ -12,7 +12,7 @@ from tiny_diffusion_amd.schedule import ForwardProcess, ddim_schedule, ddpm_sche
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("tdx_step_begin_sched", "tdx_p_sample_step_sched", "tdx_p_sample_step_sched_philox",
-               "tdx_unet_prepare_sampling_sched", "tdx_unet_eval_step_sched")
+               "tdx_unet_prepare_sampling_sched", "tdx_unet_eval_step_update")
 
 
 @pytest.mark.parametrize("S", [1, 7, 10, 50, 1000])

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ("tdx_p_sample_step_ms", "tdx_p_sample_step_ms_guided", "tdx_unet_eval_step_ms")
+NEW_SYMBOLS = ("tdx_p_sample_step_ms", "tdx_p_sample_step_ms_guided", "tdx_unet_eval_step_update")
 LOGSNR_10 = [0, 5, 22, 73, 202, 410, 603, 757, 886, 999]   # the default ForwardProcess(), steps = 10
 
 

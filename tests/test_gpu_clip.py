@@ -17,6 +17,7 @@ from oracle import ref_latent as RLT  # noqa: E402
 from oracle import ref_transformer as RT  # noqa: E402
 from oracle.weights import (make_state_dict, make_state_dict_laion, make_state_dict_latent,  # noqa: E402
                             make_state_dict_transformer)
+from inpaint_helpers import cpu_x0_step as _cpu_x0_step, spy_entries  # noqa: E402
 from parity_helpers import rel_mse  # noqa: E402
 
 from tiny_diffusion_amd._lib import check, lib  # noqa: E402
@@ -186,19 +187,6 @@ def _draw(shape, row, guided, w, seed):
         d = torch.randn(shape, generator=g)
         out = torch.cat([out + (1 - w) * d, out - w * d])
     return x.contiguous(), out.contiguous(), z.contiguous()
-
-
-def _cpu_x0_step(x, out, z, row, lo, hi, k, w=None):
-    """The fp32 restatement: every product and sum a separate torch op, in p_step_x0's order."""
-    p, q, A, Bx, sg = row.unbind()
-    if w is not None:
-        n = x.shape[0]
-        oc, ou = out[:n], out[n:]
-        out = ou + torch.tensor(w, dtype=torch.float32) * (oc - ou)
-    x0 = p * x + q * out
-    x0c = torch.minimum(torch.maximum(x0, torch.tensor(lo)), torch.tensor(hi))
-    zz = z if (z is not None and k > 0) else torch.zeros_like(x)
-    return (A * x0c + Bx * x) + sg * zz, x0
 
 
 def _call_x0(xo, x, out, z, coef, tau, t_idx, lo, hi, philox=0, seed=0, w=None, n=None):
@@ -495,9 +483,8 @@ def test_defaults_are_the_path_as_it_was(monkeypatch):
     from tiny_diffusion_amd import diffusion as D
 
     calls = []
-    for name in ("tdx_p_sample_step_x0", "tdx_p_sample_step_x0_guided", "tdx_unet_eval_step_x0"):
-        real = getattr(lib, name)
-        monkeypatch.setattr(lib, name, lambda *a, _real=real, _name=name: (calls.append(_name), _real(*a))[1])
+    spy_entries(monkeypatch, lib, ("tdx_p_sample_step_x0", "tdx_p_sample_step_x0_guided", "tdx_p_sample_update",
+                                   "tdx_unet_eval_step_update"), calls)
     n = 3
     fp = ForwardProcess(num_timesteps=20)
     for kind, mod, w in (("uncond", D, None), ("cond", C, 2.0)):
@@ -513,13 +500,15 @@ def test_defaults_are_the_path_as_it_was(monkeypatch):
                              mod.ddim_sample(m, fp, "cuda", **cond, steps=6, eta=0.4, **kw, **extra)))
             for o in outs[1:]:
                 assert torch.equal(outs[0][0], o[0]) and torch.equal(outs[0][1], o[1]), (kind, w, list(kw))
-        assert not calls
+        assert calls and not [c for c in calls if "[x0" in c or "step_x0" in c]      # eps-form updates only
+        calls.clear()
+        g = ",guided" if w is not None else ""
         # and the spies do see a clipped call: the one-call step in graph + Philox mode, the separate kernel otherwise
         mod.ddim_sample(m, fp, "cuda", **cond, steps=3, x_T=x_T, use_graph=True, philox_seed=3, clip_denoised=True)
-        assert calls == ["tdx_unet_eval_step_x0"] * 4, calls     # one warm-up step, three captured
+        assert calls == ["tdx_unet_eval_step_update[x0,sched" + g + "]"] * 4, calls     # one warm-up step, three captured
         calls.clear()
         mod.ddim_sample(m, fp, "cuda", **cond, steps=3, x_T=x_T, noises=zs, clip_denoised=True)
-        assert calls == ["tdx_p_sample_step_x0" + ("_guided" if w is not None else "")] * 3, calls
+        assert calls == ["tdx_p_sample_update[x0,sched" + g + "]"] * 3, calls
         calls.clear()
 
 

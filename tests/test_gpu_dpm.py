@@ -19,6 +19,7 @@ from oracle import ref_latent as RLT  # noqa: E402
 from oracle import ref_transformer as RT  # noqa: E402
 from oracle.weights import (make_state_dict, make_state_dict_laion, make_state_dict_latent,  # noqa: E402
                             make_state_dict_transformer)
+from inpaint_helpers import cpu_ms_step as _cpu_ms_step, spy_entries  # noqa: E402
 from parity_helpers import rel_mse  # noqa: E402
 
 from tiny_diffusion_amd._lib import check, lib  # noqa: E402
@@ -181,18 +182,6 @@ def _draw(n, row, seed):
 
 def _cfg_cpu(oc, ou, w):
     return ou + torch.tensor(w, dtype=torch.float32) * (oc - ou)
-
-
-def _cpu_ms_step(x, out, hist, row, lo, hi):
-    """The fp32 restatement: every product and sum a separate torch op, in p_step_ms's order; the H term only when
-    H != 0.  Returns (x', the clamped x0, x0)."""
-    p, q, A, Bx, H = row.unbind()
-    x0 = p * x + q * out
-    x0c = torch.minimum(torch.maximum(x0, torch.tensor(lo)), torch.tensor(hi))
-    r = A * x0c + Bx * x
-    if H.item() != 0.0:
-        r = r + H * hist
-    return r, x0c, x0
 
 
 def _call_ms(xo, x, out, hist, coef, t_idx, lo, hi, w=None, n=None):
@@ -477,15 +466,14 @@ def test_half_batch_launches_index_one_history():
 
 
 def test_module_wrappers(monkeypatch):
-    """dpm_sample of the drop-in modules reaches the new entries - the one-call step in graph + Philox mode (one warm-up
-    step and S captured), the separate kernel otherwise - and sample / ddim_sample never do."""
+    """dpm_sample of the drop-in modules asks for the multistep update - the one-call step in graph + Philox mode (one
+    warm-up step and S captured), the separate kernel otherwise - and sample / ddim_sample never do."""
     from tiny_diffusion_amd import conditional_diffusion as C
     from tiny_diffusion_amd import diffusion as D
 
     calls = []
-    for name in ("tdx_p_sample_step_ms", "tdx_p_sample_step_ms_guided", "tdx_unet_eval_step_ms"):
-        real = getattr(lib, name)
-        monkeypatch.setattr(lib, name, lambda *a, _real=real, _name=name: (calls.append(_name), _real(*a))[1])
+    spy_entries(monkeypatch, lib, ("tdx_p_sample_step_ms", "tdx_p_sample_step_ms_guided", "tdx_p_sample_update",
+                                   "tdx_unet_eval_step_update"), calls)
     n = 3
     fp = ForwardProcess()
     for kind, mod, w in (("uncond", D, None), ("cond", C, 2.0)):
@@ -495,12 +483,14 @@ def test_module_wrappers(monkeypatch):
         mod.ddim_sample(m, fp, "cuda", **cond, steps=3, x_T=x_T, use_graph=True, philox_seed=3, clip_denoised=True)
         mod.ddim_sample(m, fp, "cuda", **cond, steps=3, x_T=x_T)
         mod.sample(m, ForwardProcess(num_timesteps=5), "cuda", **cond, x_T=x_T, use_graph=True, philox_seed=3)
-        assert not calls
+        assert calls and not [c for c in calls if "[ms" in c or "step_ms" in c]
+        calls.clear()
+        g = ",guided" if w is not None else ""
         a = mod.dpm_sample(m, fp, "cuda", **cond, steps=3, x_T=x_T, use_graph=True, philox_seed=3)
-        assert calls == ["tdx_unet_eval_step_ms"] * 4, calls
+        assert calls == ["tdx_unet_eval_step_update[ms,sched" + g + "]"] * 4, calls
         calls.clear()
         b = mod.dpm_sample(m, fp, "cuda", **cond, steps=3, x_T=x_T)
-        assert calls == ["tdx_p_sample_step_ms" + ("_guided" if w is not None else "")] * 3, calls
+        assert calls == ["tdx_p_sample_update[ms,sched" + g + "]"] * 3, calls
         calls.clear()
         assert a.shape == x_T.shape and rel_mse(a, b) < 1e-10
         c = mod.dpm_sample(m, fp, "cuda", **cond, timesteps=logsnr_timesteps(fp, 3), x_T=x_T)

@@ -12,7 +12,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from inpaint_helpers import (INF, SHAPES, amp, block_mask, cpu_ms_masked_step, cpu_x0_masked_step,  # noqa: E402
-                             fp64_forward, inpaint_chain64, inpaint_dpm_chain64, inputs, known_data, model, null_cond)
+                             fp64_forward, inpaint_chain64, inpaint_dpm_chain64, inputs, known_data, model, null_cond,
+                             spy_entries)
 from parity_helpers import rel_mse  # noqa: E402
 
 from tiny_diffusion_amd._lib import check, lib  # noqa: E402
@@ -24,7 +25,7 @@ TDX_E_BADARG = -1
 CHAIN_TOL = 1e-8    # the project's chain tolerance (test_gpu_clip.py / test_gpu_ddim.py: relative MSE against fp64)
 MODES = {"eager": dict(use_graph=False), "graph": dict(use_graph=True), "philox": dict(use_graph=True, philox_seed=7)}
 MASKED = ("tdx_p_sample_step_x0_masked", "tdx_p_sample_step_x0_guided_masked", "tdx_p_sample_step_ms_masked",
-          "tdx_p_sample_step_ms_guided_masked", "tdx_unet_eval_step_x0_masked", "tdx_unet_eval_step_ms_masked")
+          "tdx_p_sample_step_ms_guided_masked")
 
 
 def _stream():
@@ -489,24 +490,23 @@ def test_known_region_is_returned_exactly(sampler, clip):
 
 # ---------------------------------------------------------------- 8. known=None is the path as it was
 def test_defaults_are_the_path_as_it_was(monkeypatch):
-    """The sequence of sampling entries each sampler calls without ``known`` / ``mask`` - written out here from the code
-    as it was before the keywords existed - in every mode, guided or not; ``known=None, mask=None`` is the same call."""
+    """The sequence of sampling entries each sampler calls without ``known`` / ``mask``, and the update each call asks
+    for (``spy_entries``) - the unmasked one, in every mode, guided or not; ``known=None, mask=None`` is the same call."""
     from tiny_diffusion_amd import _lib
     from tiny_diffusion_amd import conditional_diffusion as C
     from tiny_diffusion_amd import diffusion as D
 
     calls = []
-    watched = [nm for nm in _lib.EXPORTS if "p_sample_step" in nm or "eval_step" in nm or "step_begin" in nm
-               or "prepare_sampling" in nm or "sampling_tables" in nm]
-    assert set(MASKED) <= set(watched)
-    for name in watched:
-        real = getattr(lib, name)
-        monkeypatch.setattr(lib, name, lambda *a, _real=real, _name=name: (calls.append(_name), _real(*a))[1])
+    watched = [nm for nm in _lib.EXPORTS if "p_sample_step" in nm or "p_sample_update" in nm or "eval_step" in nm
+               or "step_begin" in nm or "prepare_sampling" in nm or "sampling_tables" in nm]
+    assert set(MASKED) | {"tdx_p_sample_update", "tdx_unet_eval_step_update"} <= set(watched)
+    spy_entries(monkeypatch, lib, watched, calls)
     n, T, S = 3, 20, 6
     fp = ForwardProcess(num_timesteps=T)
     Sd = dpm_solver_schedule(fp, steps=S).steps
     for kind, mod, w in (("uncond", D, None), ("cond", C, 2.0)):
-        g = "_guided" if w is not None else ""
+        g = ",guided" if w is not None else ""
+        up, ev = "tdx_p_sample_update[", "tdx_unet_eval_step_update["
         m = model(kind, 2)
         x_T, zs, y = inputs(kind, n, T, seed=4)
         cond = dict(n_samples=n) if kind == "uncond" else dict(n_samples=n, y=y, guidance_scale=w)
@@ -514,23 +514,23 @@ def test_defaults_are_the_path_as_it_was(monkeypatch):
             dict(x_T=x_T, use_graph=True, philox_seed=3)
         det, dgph = dict(x_T=x_T), dict(x_T=x_T, use_graph=True)
         expect = [
-            # the reference's chain: the plain update, one per step; one warm-up + one captured step; tables + the
+            # the reference's chain: the eps-form update, one per step; one warm-up + one captured step; tables + the
             # one-call step (one warm-up + GRAPH_STEPS captured, replayed twice)
-            ("sample", {}, rec, ["tdx_p_sample_step" + g] * T),
-            ("sample", {}, gph, ["tdx_p_sample_step" + g] * 2),
+            ("sample", {}, rec, [up + "eps" + g + "]"] * T),
+            ("sample", {}, gph, [up + "eps" + g + "]"] * 2),
             ("sample", {}, phx, ["tdx_unet_prepare_sampling"]
-             + ["tdx_unet_eval_step" + g] * (1 + GRAPH_STEPS)),
-            ("ddim_sample", dict(steps=S, eta=0.4), rec, ["tdx_p_sample_step" + (g or "_sched")] * S),
-            ("ddim_sample", dict(steps=S, eta=0.4), gph, ["tdx_p_sample_step" + (g or "_sched")] * 2),
+             + [ev + "eps" + g + "]" if g else "tdx_unet_eval_step"] * (1 + GRAPH_STEPS)),
+            ("ddim_sample", dict(steps=S, eta=0.4), rec, [up + "eps,sched" + g + "]"] * S),
+            ("ddim_sample", dict(steps=S, eta=0.4), gph, [up + "eps,sched" + g + "]"] * 2),
             ("ddim_sample", dict(steps=S, eta=0.4), phx, ["tdx_unet_prepare_sampling_sched"]
-             + ["tdx_unet_eval_step" + (g or "_sched")] * (1 + S)),
-            ("ddim_sample", dict(steps=S, eta=0.4, clip_denoised=True), rec, ["tdx_p_sample_step_x0" + g] * S),
+             + [ev + "eps,sched" + g + "]"] * (1 + S)),
+            ("ddim_sample", dict(steps=S, eta=0.4, clip_denoised=True), rec, [up + "x0,sched" + g + "]"] * S),
             ("ddim_sample", dict(steps=S, eta=0.4, clip_denoised=True), phx, ["tdx_unet_prepare_sampling_sched"]
-             + ["tdx_unet_eval_step_x0"] * (1 + S)),
-            ("dpm_sample", dict(steps=S), det, ["tdx_p_sample_step_ms" + g] * Sd),
-            ("dpm_sample", dict(steps=S), dgph, ["tdx_p_sample_step_ms" + g] * 2),
+             + [ev + "x0,sched" + g + "]"] * (1 + S)),
+            ("dpm_sample", dict(steps=S), det, [up + "ms,sched" + g + "]"] * Sd),
+            ("dpm_sample", dict(steps=S), dgph, [up + "ms,sched" + g + "]"] * 2),
             ("dpm_sample", dict(steps=S), phx, ["tdx_unet_prepare_sampling_sched"]
-             + ["tdx_unet_eval_step_ms"] * (1 + Sd)),
+             + [ev + "ms,sched" + g + "]"] * (1 + Sd)),
         ]
         for sampler, extra, kw, want in expect:
             outs = []
@@ -545,13 +545,13 @@ def test_defaults_are_the_path_as_it_was(monkeypatch):
         mod.ddim_sample(m, fp, "cuda", **cond, steps=3, x_T=x_T, use_graph=True, philox_seed=3, known=known, mask=mask)
         # (under a condition the masked chain leaves the tables aside: the direct time path, the eager chain's bits)
         head = "tdx_unet_prepare_sampling_sched" if kind == "uncond" else "tdx_unet_drop_sampling_tables"
-        assert calls == [head] + ["tdx_unet_eval_step_x0_masked"] * 4, calls
+        assert calls == [head] + [ev + "x0,sched" + g + ",masked]"] * 4, calls
         calls.clear()
         mod.dpm_sample(m, fp, "cuda", **cond, steps=S, x_T=x_T, known=known, mask=mask)
-        assert calls == ["tdx_p_sample_step_ms" + g + "_masked"] * Sd, calls
+        assert calls == [up + "ms,sched" + g + ",masked]"] * Sd, calls
         calls.clear()
         mod.sample(m, fp, "cuda", **cond, x_T=x_T, noises=zs, known=known, mask=mask)
-        assert calls == ["tdx_p_sample_step_x0" + g + "_masked"] * T, calls
+        assert calls == [up + "x0,sched" + g + ",masked]"] * T, calls
         calls.clear()
 
 

@@ -13,7 +13,7 @@ from inpaint_helpers import blend32
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("tdx_p_sample_step_x0_masked", "tdx_p_sample_step_x0_guided_masked", "tdx_p_sample_step_ms_masked",
-               "tdx_p_sample_step_ms_guided_masked", "tdx_unet_eval_step_x0_masked", "tdx_unet_eval_step_ms_masked",
+               "tdx_p_sample_step_ms_guided_masked", "tdx_unet_eval_step_update",
                "tdx_unet_drop_sampling_tables")
 NAN, INF = float("nan"), float("inf")
 

@@ -194,23 +194,17 @@ _SIGS = {
     "tdx_initial_conv_input_grad": (C.c_int, [_ptr, _ptr, _ptr] + [C.c_int] * 5 + [_ptr]),
     "tdx_unet_eval_step": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int64,
                                      _ptr, C.c_size_t, C.c_int, C.c_uint64, _ptr]),
-    "tdx_unet_eval_step_sched": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, _ptr, _ptr, _ptr,
-                                           _ptr, C.c_int64, _ptr, C.c_size_t, C.c_int, C.c_uint64, _ptr]),
-    "tdx_unet_eval_step_guided": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, _ptr, _ptr, _ptr,
-                                            _ptr, C.c_int64, _ptr, C.c_size_t, C.c_int, C.c_uint64, C.c_float, _ptr]),
+    "tdx_unet_eval_step_update": (C.c_int, [_ptr] * 8 + [C.c_int, _ptr, _ptr, _ptr, _ptr, C.c_int64, _ptr, C.c_size_t,
+                                            C.c_int, C.c_uint64, C.c_int, C.c_int] + [C.c_float] * 3 + [_ptr] * 4),
+    "tdx_p_sample_update": (C.c_int, [_ptr, _ptr, _ptr, C.c_int64, C.c_int, _ptr, _ptr, _ptr, _ptr, C.c_int, C.c_uint64,
+                                      C.c_int, C.c_float, C.c_float, C.c_float, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "tdx_p_sample_step_guided": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int64, C.c_float, C.c_int,
                                            C.c_uint64, _ptr, _ptr]),
     "tdx_p_sample_step_x0": (C.c_int, [_ptr] * 7 + [C.c_int64, C.c_float, C.c_float, C.c_int, C.c_uint64, _ptr, _ptr]),
     "tdx_p_sample_step_x0_guided": (C.c_int, [_ptr] * 6 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int,
                                                            C.c_uint64, _ptr, _ptr]),
-    "tdx_unet_eval_step_x0": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, _ptr, _ptr, _ptr,
-                                        _ptr, C.c_int64, _ptr, C.c_size_t, C.c_int, C.c_uint64, C.c_int, C.c_float,
-                                        C.c_float, C.c_float, _ptr]),
     "tdx_p_sample_step_ms": (C.c_int, [_ptr] * 6 + [C.c_int64, C.c_float, C.c_float, _ptr, _ptr]),
     "tdx_p_sample_step_ms_guided": (C.c_int, [_ptr] * 5 + [C.c_int64, C.c_float, C.c_float, C.c_float, _ptr, _ptr]),
-    "tdx_unet_eval_step_ms": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, _ptr, _ptr, _ptr, _ptr,
-                                        C.c_int64, _ptr, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
-                                        _ptr, _ptr]),
     "tdx_p_sample_step_x0_masked": (C.c_int, [_ptr] * 9 + [C.c_int64, C.c_float, C.c_float, C.c_int, C.c_uint64, _ptr,
                                                            _ptr]),
     "tdx_p_sample_step_x0_guided_masked": (C.c_int, [_ptr] * 8 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int,
@@ -218,12 +212,6 @@ _SIGS = {
     "tdx_p_sample_step_ms_masked": (C.c_int, [_ptr] * 8 + [C.c_int64, C.c_float, C.c_float, _ptr, _ptr]),
     "tdx_p_sample_step_ms_guided_masked": (C.c_int, [_ptr] * 7 + [C.c_int64, C.c_float, C.c_float, C.c_float, _ptr,
                                                                   _ptr]),
-    "tdx_unet_eval_step_x0_masked": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, _ptr, _ptr,
-                                               _ptr, _ptr, C.c_int64, _ptr, C.c_size_t, C.c_int, C.c_uint64, C.c_int,
-                                               C.c_float, C.c_float, C.c_float, _ptr, _ptr, _ptr]),
-    "tdx_unet_eval_step_ms_masked": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, _ptr, _ptr, _ptr,
-                                               _ptr, C.c_int64, _ptr, C.c_size_t, C.c_int, C.c_int, C.c_float,
-                                               C.c_float, C.c_float, _ptr, _ptr, _ptr, _ptr]),
     "tdx_cond_drop_labels": (C.c_int, [_ptr, _ptr, C.c_int, C.c_float, C.c_uint64, C.c_uint64, _ptr]),
     "tdx_cond_drop_rows": (C.c_int, [_ptr, _ptr, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, _ptr]),
     "tdx_timestep_embedding": (C.c_int, [_ptr, _ptr, C.c_int, C.c_int, _ptr]),
@@ -242,6 +230,7 @@ _SIGS = {
 }
 
 EXPORTS = tuple(_SIGS)
+STEP_EPS, STEP_X0, STEP_MS = 0, 1, 2   # TDX_STEP_*: the forms of tdx_p_sample_update / tdx_unet_eval_step_update
 
 
 def _bind():

@@ -67,65 +67,59 @@ __device__ static inline float p_step(float x, float e, float z, float c1, float
   return __fadd_rn(__fmul_rn(c1, inner), __fmul_rn(sg, z));
 }
 
-// The update in x0 form with the implied x0 clamped to [lo, hi] (clipped-x0 sampling, "static thresholding"):
-//   x0 = p*x + q*out;  x0c = min(max(x0, lo), hi);  x' = (A*x0c + Bx*x) + sigma*z
-// from a (p, q, A, Bx, sigma) row (schedule.py x0_form).  Every product and sum is rounded separately, in this
-// order - a CPU fp32 tensor expression reproduces it bit for bit, as it does p_step.
-__device__ static inline float p_step_x0(float x, float o, float z, float p, float q, float A, float Bx, float sg,
-                                         float lo, float hi) {
-  const float x0 = __fadd_rn(__fmul_rn(p, x), __fmul_rn(q, o));
-  const float x0c = fminf(fmaxf(x0, lo), hi);
-  return __fadd_rn(__fadd_rn(__fmul_rn(A, x0c), __fmul_rn(Bx, x)), __fmul_rn(sg, z));
+// The x0-form updates (schedule.py x0_form / multistep_form) share three pieces, every product and sum rounded
+// separately and in this order - a CPU fp32 tensor expression reproduces each bit for bit, as it does p_step.
+// 1. The implied x0, clamped to [lo, hi] (clipped-x0 sampling, "static thresholding"; infinite bounds never bind):
+//      x0c = min(max(p*x + q*out, lo), hi)
+__device__ static inline float x0_clamped(float x, float o, float p, float q, float lo, float hi) {
+  return fminf(fmaxf(__fadd_rn(__fmul_rn(p, x), __fmul_rn(q, o)), lo), hi);
 }
 
-// The second-order multistep update (DPM-Solver++(2M), Lu et al. 2022) in the same x0 form, with the clamped x0 of the
-// step before as history:
-//   x0 = p*x + q*out;  x0c = min(max(x0, lo), hi);  x' = (A*x0c + Bx*x) + H*hprev
-// from a (p, q, A, Bx, H) row (schedule.py multistep_form); rounded operation by operation, in this order, like
-// p_step_x0.  H == 0 (the first and the last step, every step of order 1): the history term is not added and the
-// callers do not load hprev (H is uniform over a launch), so an uninitialised history buffer is harmless there.
-// *x0c_out is what the caller stores as the next step's history.
-__device__ static inline float p_step_ms(float x, float o, float hprev, float p, float q, float A, float Bx,
-                                         float H, float lo, float hi, float* x0c_out) {
-  const float x0 = __fadd_rn(__fmul_rn(p, x), __fmul_rn(q, o));
-  const float x0c = fminf(fmaxf(x0, lo), hi);
-  *x0c_out = x0c;
-  float r = __fadd_rn(__fmul_rn(A, x0c), __fmul_rn(Bx, x));
-  if (H != 0.0f) r = __fadd_rn(r, __fmul_rn(H, hprev));
-  return r;
-}
-
-// Inpainting (masked sampling with a known region): the blend of the clamped prediction with the caller's data between
-// the clamp and the step,  x0m = (1 - m)*x0c + m*known,  each operation rounded separately.  m == 1 gives `known` and
-// m == 0 gives x0c bit for bit ((1-1)*x0c = +-0, 1*known = known; 1*x0c = x0c, 0*known = +-0: for finite operands); a
-// fractional m is a soft edge.  `known` is the user's data: it is not clamped.
+// 2. Inpainting: the blend with the caller's data between the clamp and the step,  x0m = (1 - m)*x0c + m*known.
+// m == 1 gives `known` and m == 0 gives x0c bit for bit ((1-1)*x0c = +-0, 1*known = known; 1*x0c = x0c, 0*known = +-0:
+// for finite operands); a fractional m is a soft edge.  `known` is not clamped.  The known region steps from x0 = known
+// with the chain's own x and z - the posterior step of the forward process given x_0 = known.
 __device__ static inline float x0_blend(float x0c, float known, float m) {
   return __fadd_rn(__fmul_rn(__fsub_rn(1.0f, m), x0c), __fmul_rn(m, known));
 }
 
-// p_step_x0 with the blend:  x0 = p*x + q*out;  x0c = min(max(x0, lo), hi);  x0m = x0_blend(x0c, known, m);
-// x' = (A*x0m + Bx*x) + sigma*z.  The known region steps from x0 = known with the chain's own x and z - the posterior
-// step of the forward process given x_0 = known; on row 0 (A = 1, Bx = 0, sigma*z = 0) it returns x0m itself.
-__device__ static inline float p_step_x0_masked(float x, float o, float z, float known, float m, float p, float q,
-                                                float A, float Bx, float sg, float lo, float hi) {
-  const float x0 = __fadd_rn(__fmul_rn(p, x), __fmul_rn(q, o));
-  const float x0c = fminf(fmaxf(x0, lo), hi);
-  const float x0m = x0_blend(x0c, known, m);
-  return __fadd_rn(__fadd_rn(__fmul_rn(A, x0m), __fmul_rn(Bx, x)), __fmul_rn(sg, z));
+// 3a. The stochastic step from a (p, q, A, Bx, sigma) row:  x' = (A*x0 + Bx*x) + sigma*z.  On row 0 (A = 1, Bx = 0,
+// z = 0) it returns x0 itself.
+__device__ static inline float x0_step_noise(float x0, float x, float z, float A, float Bx, float sg) {
+  return __fadd_rn(__fadd_rn(__fmul_rn(A, x0), __fmul_rn(Bx, x)), __fmul_rn(sg, z));
 }
 
-// p_step_ms with the blend:  x' = (A*x0m + Bx*x) + H*hprev, and *x0c_out is x0m - the history holds the BLENDED
-// prediction, which keeps the known region on the forward marginal of the deterministic chain (with the clamped
-// prediction as history it leaves it).  The H == 0 rule is p_step_ms's.
-__device__ static inline float p_step_ms_masked(float x, float o, float hprev, float known, float m, float p, float q,
-                                                float A, float Bx, float H, float lo, float hi, float* x0c_out) {
-  const float x0 = __fadd_rn(__fmul_rn(p, x), __fmul_rn(q, o));
-  const float x0c = fminf(fmaxf(x0, lo), hi);
-  const float x0m = x0_blend(x0c, known, m);
-  *x0c_out = x0m;
-  float r = __fadd_rn(__fmul_rn(A, x0m), __fmul_rn(Bx, x));
+// 3b. The second-order multistep step (DPM-Solver++(2M), Lu et al. 2022) from a (p, q, A, Bx, H) row, with the x0 of
+// the step before as history:  x' = (A*x0 + Bx*x) + H*hprev.  H == 0 (the first and the last step, every step of
+// order 1): the history term is not added and the callers do not load hprev (H is uniform over a launch), so an
+// uninitialised history buffer is harmless there.
+__device__ static inline float x0_step_hist(float x0, float x, float hprev, float A, float Bx, float H) {
+  float r = __fadd_rn(__fmul_rn(A, x0), __fmul_rn(Bx, x));
   if (H != 0.0f) r = __fadd_rn(r, __fmul_rn(H, hprev));
   return r;
+}
+
+// One row of a table: (S,5) rows (p, q, A, Bx, e = sigma | H), or the (S,3) rows (c1, c2, sigma) of p_step in A, Bx, e
+struct PRow { float p, q, A, Bx, e; };
+template <int FORM>
+__device__ static inline PRow pstep_row(const float* coef, int t) {
+  if (FORM == TDX_STEP_EPS) return PRow{0.f, 0.f, coef[3 * t + 0], coef[3 * t + 1], coef[3 * t + 2]};
+  return PRow{coef[5 * t + 0], coef[5 * t + 1], coef[5 * t + 2], coef[5 * t + 3], coef[5 * t + 4]};
+}
+
+// The update of one element, for pstep_kernel (elementwise.hip) and the epilogue of final_conv (edge_conv.hip).  o: the
+// network's output (guided: the cfg_eps combination); zh: the noise (EPS, X0; 0 for none) or the history (MS; not
+// loaded when r.e == 0); known / m: read when MK only.  MS: *x0_out is what the caller stores as the next step's
+// history - the BLENDED prediction when MK, which keeps the known region on the forward marginal of the deterministic
+// chain (with the clamped prediction as history it leaves it).
+template <int FORM, bool MK>
+__device__ static inline float pstep_elem(float x, float o, float zh, float known, float m, const PRow& r, float lo,
+                                          float hi, float* x0_out) {
+  if (FORM == TDX_STEP_EPS) return p_step(x, o, zh, r.A, r.Bx, r.e);
+  float x0 = x0_clamped(x, o, r.p, r.q, lo, hi);
+  if (MK) x0 = x0_blend(x0, known, m);
+  if (FORM == TDX_STEP_MS) *x0_out = x0;
+  return FORM == TDX_STEP_MS ? x0_step_hist(x0, x, zh, r.A, r.Bx, r.e) : x0_step_noise(x0, x, zh, r.A, r.Bx, r.e);
 }
 
 // classifier-free guidance (Ho & Salimans 2021): eps_u + w (eps_c - eps_u), each operation rounded separately - the

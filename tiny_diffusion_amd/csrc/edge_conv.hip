@@ -120,44 +120,23 @@ thin_to_fat_conv_kernel(const float* __restrict__ thin, const float* __restrict_
 // sum_{o,tap} g(x0)[p - tap][o] W[o][c][tap] = sum_{tap'} sum_o g(x0)[p + tap'][o] W[o][c][8 - tap'], i.e. this
 // kernel on the gradient of x0 with the weight image ws[c][tap'][o] = initial_conv.weight[o][c][8 - tap'] (w is
 // [cor][CO][9]; stored channels o >= cor are padding: zero weights) and no bias.
-// PS = true (sampling): the reverse-process update of diffusion.py:272-274 in the epilogue - the lane that holds
-// eps_hat of an element also reads x, draws or loads z and writes x' in place (x is not an input of this kernel:
-// the network read it in initial_conv), exactly the arithmetic and the Philox indexing of p_sample_kernel; the
-// step's last launch disappears.  eps_hat is still written to `out`.
+// PS = true (sampling): the reverse-process update ps (PStep, internal.h) in the epilogue - the lane that holds the
+// network's output of an element also reads x, draws or loads z / the history / known and mask, and writes x' in place
+// (x is not an input of this kernel: the network read it in initial_conv) with pstep_elem, the arithmetic and the
+// Philox indexing of pstep_kernel bit for bit; the step's last launch disappears.  The output is still written to
+// `out`.  FORM / MK: the update's form and whether it blends (template parameters: an instantiation carries no trace
+// of the others).  hist, known, mask and the Philox element are indexed by the element's place in the whole batch
+// (idx + ps.elem0); x and z start at this launch's first element.
 // GD = true (with PS; classifier-free guidance): B = 2n samples whose first half ran under the caller's condition and
 // whose second half under the null condition, both from the same x.  The pixel loop runs over the first half's n H W
 // pixels; a lane group accumulates the convolution of its pixel AND of the twin pixel n H W further on against the same
-// LDS weight reads, writes both eps_hat values to `out`, combines them (cfg_eps) and writes the one update to both halves
-// of x.  Noise as in the unguided chain of n samples: z holds n samples, Philox is indexed by the first half's element.
-// X0 = true (with PS; clipped-x0 sampling): the update is p_step_x0 from a (S,5) row (p, q, A, Bx, sigma) and the bounds
-// lo / hi - the arithmetic of p_sample_x0_kernel / p_sample_x0_guided_kernel, bit for bit.  A template parameter: the
-// X0 = false instantiations carry no trace of it.
-// MS = true (with PS; the multistep sampler): the update is p_step_ms from a (S,5) row (p, q, A, Bx, H) against the
-// history ps.hist (the clamped x0 of the step before, one value per element of the unguided batch / the first half),
-// which the same lane overwrites with this step's clamped x0; no noise.  The arithmetic of p_sample_ms_kernel /
-// p_sample_ms_guided_kernel, bit for bit; again a template parameter that the other instantiations do not see.
-// MK = true (with X0 or MS; inpainting): the clamped prediction is blended with ps.known under ps.mask before the step
-// (p_step_x0_masked / p_step_ms_masked) - the arithmetic of p_sample_x0_masked_kernel / p_sample_ms_masked_kernel, bit
-// for bit.  The two loads belong to the lane that already loads x and are indexed like hist (idx + elem0).  A template
-// parameter that only X0 / MS instantiations take.
-struct PSampleOps {
-  float* x; const float* z; const float* coef; const int32_t* t_idx; uint64_t seed; int philox; int64_t* counter_dec;
-  int64_t elem0;   // index of this launch's first element in the whole batch (a half-batch launch keeps the batch's Philox stream)
-  const int64_t* tau;   // timestep schedule (DDIM): *t_idx is the step index k, the Philox stream tau[k]; null: identity
-  float w;              // GD: guidance scale
-  int64_t half;         // GD: elements of one half of x / out (the twin of element idx is idx + half)
-  int x0;               // table kind: 0 = (S,3) rows (c1, c2, sigma) of p_step, 1 = (S,5) rows of p_step_x0 (the X0 kernels),
-                        // 2 = (S,5) rows (p, q, A, Bx, H) of p_step_ms (the MS kernels)
-  float lo, hi;         // X0 / MS: the clamp of the implied x0
-  float* hist;          // MS: the history, indexed by the element's index in the whole batch (idx + elem0)
-  const float* known;   // MK: the known data and its mask, one value per element of the unguided batch / the first half,
-  const float* mask;    //     indexed like hist
-};
-template <int CO, bool DGRAD, bool PS, typename TF, bool GD = false, bool X0 = false, bool MS = false, bool MK = false>
+// LDS weight reads, writes both outputs to `out`, combines them (cfg_eps) and writes the one update to both halves of
+// x (one launch: elem0 == 0).  Noise as in the unguided chain of n samples.
+template <int CO, bool DGRAD, bool PS, typename TF, bool GD = false, int FORM = TDX_STEP_EPS, bool MK = false>
 __global__ void __launch_bounds__(256)
 fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
                         const float* __restrict__ bias, float* __restrict__ out, int B, int H, int W, int cor,
-                        PSampleOps ps) {
+                        PStep ps) {
   __shared__ __attribute__((aligned(16))) float ws[CO][9][IC_CO];
   if (DGRAD) {
     for (int i = threadIdx.x; i < CO * 9 * IC_CO; i += 256) {
@@ -180,18 +159,12 @@ fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
   for (int co = 0; co < CO; ++co) bv[co] = DGRAD ? 0.f : bias[co];
   int ps_t = 0;
   uint64_t ps_nt = 0;
-  float ps_c1 = 0.f, ps_c2 = 0.f, ps_sg = 0.f;
-  float ps_p = 0.f, ps_q = 0.f;   // X0: the row is (p, q, A = ps_c1, Bx = ps_c2, sigma); MS: (p, q, A, Bx, H = ps_sg)
+  PRow ps_r = {};
   if (PS) {
     ps_t = *ps.t_idx;
     ps_nt = ps.tau ? (uint64_t)ps.tau[ps_t] : (uint64_t)ps_t;
-    if (X0 || MS) {
-      ps_p = ps.coef[5 * ps_t + 0]; ps_q = ps.coef[5 * ps_t + 1];
-      ps_c1 = ps.coef[5 * ps_t + 2]; ps_c2 = ps.coef[5 * ps_t + 3]; ps_sg = ps.coef[5 * ps_t + 4];
-    } else {
-      ps_c1 = ps.coef[3 * ps_t + 0]; ps_c2 = ps.coef[3 * ps_t + 1]; ps_sg = ps.coef[3 * ps_t + 2];
-    }
-    // table-mode sampling: the step counter is advanced by the last kernel of the step (see p_sample_kernel)
+    ps_r = pstep_row<FORM>(ps.coef, ps_t);
+    // table-mode sampling: the step counter is advanced by the last kernel of the step (see pstep_kernel)
     if (ps.counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *ps.counter_dec = (int64_t)ps_t - 1;
   }
   for (int64_t p = (int64_t)blockIdx.x * 16 + pl; p < Mpad; p += (int64_t)gridDim.x * 16) {
@@ -254,50 +227,29 @@ fat_to_thin_conv_kernel(const TF* __restrict__ in, const float* __restrict__ w,
         const float e = s[co] + bv[co];
         out[idx] = e;
         if (PS) {
-          float zv = 0.f;   // diffusion.py:267-270: no noise on the last step
-          if (!MS && ps_t > 0) {
-            if (ps.philox) {   // element idx = component idx % 4 of block idx / 4 (p_sample_kernel<true>)
-              const int64_t gidx = idx + ps.elem0;
-              const float4 z4 = philox_normal4((uint64_t)(gidx >> 2), ps_nt, ps.seed);
-              const int k = (int)(gidx & 3);
-              zv = k == 0 ? z4.x : k == 1 ? z4.y : k == 2 ? z4.z : z4.w;
-            } else if (ps.z) {
-              zv = ps.z[idx];
-            }
-          }
-          if (MS) {   // deterministic: the history in the place of the noise
-            float eg = e, x0c;
-            if (GD) {
-              const float eu = s2[co] + bv[co];
-              out[idx + ps.half] = eu;
-              eg = cfg_eps(e, eu, ps.w);
-            }
-            float* hp = ps.hist + idx + ps.elem0;
-            const float hv = ps_sg != 0.0f ? *hp : 0.f;
-            const float xn = MK ? p_step_ms_masked(ps.x[idx], eg, hv, ps.known[idx + ps.elem0], ps.mask[idx + ps.elem0],
-                                                   ps_p, ps_q, ps_c1, ps_c2, ps_sg, ps.lo, ps.hi, &x0c)
-                                : p_step_ms(ps.x[idx], eg, hv, ps_p, ps_q, ps_c1, ps_c2, ps_sg, ps.lo, ps.hi, &x0c);
-            ps.x[idx] = xn;
-            if (GD) ps.x[idx + ps.half] = xn;
-            *hp = x0c;
-          } else if (GD) {
+          const int64_t gidx = idx + ps.elem0;
+          float eg = e, zh = 0.f, kn = 0.f, mv = 0.f, x0 = 0.f;
+          if (GD) {
             const float eu = s2[co] + bv[co];
             out[idx + ps.half] = eu;
-            const float eg = cfg_eps(e, eu, ps.w);
-            const float xn = MK ? p_step_x0_masked(ps.x[idx], eg, zv, ps.known[idx], ps.mask[idx], ps_p, ps_q, ps_c1,
-                                                   ps_c2, ps_sg, ps.lo, ps.hi)   // guided: one launch, elem0 == 0
-                           : X0 ? p_step_x0(ps.x[idx], eg, zv, ps_p, ps_q, ps_c1, ps_c2, ps_sg, ps.lo, ps.hi)
-                                : p_step(ps.x[idx], eg, zv, ps_c1, ps_c2, ps_sg);
-            ps.x[idx] = xn;
-            ps.x[idx + ps.half] = xn;
-          } else if (MK) {
-            ps.x[idx] = p_step_x0_masked(ps.x[idx], e, zv, ps.known[idx + ps.elem0], ps.mask[idx + ps.elem0], ps_p, ps_q,
-                                         ps_c1, ps_c2, ps_sg, ps.lo, ps.hi);
-          } else if (X0) {
-            ps.x[idx] = p_step_x0(ps.x[idx], e, zv, ps_p, ps_q, ps_c1, ps_c2, ps_sg, ps.lo, ps.hi);
-          } else {
-            ps.x[idx] = p_step(ps.x[idx], e, zv, ps_c1, ps_c2, ps_sg);
+            eg = cfg_eps(e, eu, ps.w);
           }
+          if (FORM == TDX_STEP_MS) {   // deterministic: the history in the place of the noise
+            if (ps_r.e != 0.0f) zh = ps.hist[gidx];
+          } else if (ps_t > 0) {   // diffusion.py:267-270: no noise on the last step
+            if (ps.philox) {   // element gidx = component gidx % 4 of block gidx / 4 (pstep_kernel)
+              const float4 z4 = philox_normal4((uint64_t)(gidx >> 2), ps_nt, ps.seed);
+              const int k = (int)(gidx & 3);
+              zh = k == 0 ? z4.x : k == 1 ? z4.y : k == 2 ? z4.z : z4.w;
+            } else if (ps.z) {
+              zh = ps.z[idx];
+            }
+          }
+          if (MK) { kn = ps.known[gidx]; mv = ps.mask[gidx]; }
+          const float xn = pstep_elem<FORM, MK>(ps.x[idx], eg, zh, kn, mv, ps_r, ps.lo, ps.hi, &x0);
+          ps.x[idx] = xn;
+          if (GD) ps.x[idx + ps.half] = xn;
+          if (FORM == TDX_STEP_MS) ps.hist[gidx] = x0;
         }
       }
     }
@@ -556,8 +508,8 @@ int tdx_final_conv_fwd(const void* in, const float* w, const float* bias, float*
   const int grid = (int)std::min<int64_t>((M + 15) / 16, 8192);
   if (cout != 1 && cout != 4) return TDX_E_SHAPE;
   TDX_IO_DISPATCH(io16, T,
-    if (cout == 1) fat_to_thin_conv_kernel<1, false, false, T><<<grid, 256, 0, st>>>((const T*)in, w, bias, out, B, H, W, IC_CO, PSampleOps{});
-    else fat_to_thin_conv_kernel<4, false, false, T><<<grid, 256, 0, st>>>((const T*)in, w, bias, out, B, H, W, IC_CO, PSampleOps{}));
+    if (cout == 1) fat_to_thin_conv_kernel<1, false, false, T><<<grid, 256, 0, st>>>((const T*)in, w, bias, out, B, H, W, IC_CO, PStep{});
+    else fat_to_thin_conv_kernel<4, false, false, T><<<grid, 256, 0, st>>>((const T*)in, w, bias, out, B, H, W, IC_CO, PStep{}));
   TDX_CHECK_LAUNCH();
   return 0;
 }
@@ -571,77 +523,44 @@ int tdx_initial_conv_dgrad(const void* g_x0, const float* w, float* g_x, int B, 
   const int grid = (int)std::min<int64_t>((M + 15) / 16, 8192);
   if (!((cin == 1 && cout_real == 64) || (cin == 4 && cout_real == 32))) return TDX_E_SHAPE;
   TDX_IO_DISPATCH(io16, T,
-    if (cin == 1) fat_to_thin_conv_kernel<1, true, false, T><<<grid, 256, 0, st>>>((const T*)g_x0, w, nullptr, g_x, B, H, W, cout_real, PSampleOps{});
-    else fat_to_thin_conv_kernel<4, true, false, T><<<grid, 256, 0, st>>>((const T*)g_x0, w, nullptr, g_x, B, H, W, cout_real, PSampleOps{}));
+    if (cin == 1) fat_to_thin_conv_kernel<1, true, false, T><<<grid, 256, 0, st>>>((const T*)g_x0, w, nullptr, g_x, B, H, W, cout_real, PStep{});
+    else fat_to_thin_conv_kernel<4, true, false, T><<<grid, 256, 0, st>>>((const T*)g_x0, w, nullptr, g_x, B, H, W, cout_real, PStep{}));
   TDX_CHECK_LAUNCH();
   return 0;
 }
 
-// final_conv forward with the reverse-process update fused in (sampling; PSampleOps above)
+// final_conv forward with the reverse-process update fused in (sampling; PStep): one dispatch over the element type of
+// the input, cout, guided, the form and masked
+namespace {
+template <typename T, bool GD, int FORM, bool MK>
+void launch_psample(const void* in, const float* w, const float* bias, float* eps_out, int B, int H, int W, int cout,
+                    const PStep& ps, int grid, hipStream_t st) {
+  if (cout == 1) fat_to_thin_conv_kernel<1, false, true, T, GD, FORM, MK><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps);
+  else fat_to_thin_conv_kernel<4, false, true, T, GD, FORM, MK><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps);
+}
+template <typename T, bool GD>
+void launch_psample_form(const void* in, const float* w, const float* bias, float* eps_out, int B, int H, int W,
+                         int cout, const PStep& ps, int grid, hipStream_t st) {
+#define TDX_PS_FORM(FORM_, MK_) launch_psample<T, GD, FORM_, MK_>(in, w, bias, eps_out, B, H, W, cout, ps, grid, st)
+  if (ps.form == TDX_STEP_EPS) TDX_PS_FORM(TDX_STEP_EPS, false);
+  else if (ps.form == TDX_STEP_X0) { if (ps.known) TDX_PS_FORM(TDX_STEP_X0, true); else TDX_PS_FORM(TDX_STEP_X0, false); }
+  else { if (ps.known) TDX_PS_FORM(TDX_STEP_MS, true); else TDX_PS_FORM(TDX_STEP_MS, false); }
+#undef TDX_PS_FORM
+}
+}  // namespace
+
 int tdx_final_conv_fwd_psample(const void* in, const float* w, const float* bias, float* eps_out, int B, int H, int W,
-                               int cout, float* x, const float* z, const float* coef, const int32_t* t_idx,
-                               uint64_t seed, int philox, int64_t* counter_dec, hipStream_t st, int io16, int64_t elem0,
-                               const int64_t* tau, int guided, float gw, int x0, float lo, float hi, float* hist,
-                               const float* known, const float* mask) {
-  if (!x || !coef || !t_idx || (elem0 & 3)) return TDX_E_BADARG;
-  if (x0 && !(lo < hi)) return TDX_E_BADARG;
-  if (x0 < 0 || x0 > 2 || (x0 == 2 && !hist)) return TDX_E_BADARG;
-  if ((known != nullptr) != (mask != nullptr) || (known && !x0)) return TDX_E_BADARG;   // the masked update is an x0-form one
-  if (guided && ((B & 1) || elem0)) return TDX_E_BADARG;   // two equal halves, the whole batch in one launch
-  const int64_t M = (int64_t)(guided ? B / 2 : B) * H * W;
-  const int grid = (int)std::min<int64_t>((M + 15) / 16, 8192);
-  const PSampleOps ps{x, z, coef, t_idx, seed, philox, counter_dec, elem0, tau, gw, guided ? M * cout : 0, x0, lo, hi, hist, known, mask};
+                               int cout, const PStep& s, hipStream_t st, int io16) {
+  if (!s.x || (s.guided && (B & 1))) return TDX_E_BADARG;   // guided: two equal halves
+  const int64_t M = (int64_t)(s.guided ? B / 2 : B) * H * W;
+  if (pstep_valid(s, M * cout)) return TDX_E_BADARG;
   if (cout != 1 && cout != 4) return TDX_E_SHAPE;
-  if (known) {   // the inpainting variants of the two x0-form families
-#define TDX_PS_MASKED(GD_, X0_, MS_)                                                                                   \
-    TDX_IO_DISPATCH(io16, T,                                                                                            \
-      if (cout == 1) fat_to_thin_conv_kernel<1, false, true, T, GD_, X0_, MS_, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps); \
-      else fat_to_thin_conv_kernel<4, false, true, T, GD_, X0_, MS_, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps))
-    if (x0 == 2) {
-      if (guided) { TDX_PS_MASKED(true, false, true); } else { TDX_PS_MASKED(false, false, true); }
-    } else {
-      if (guided) { TDX_PS_MASKED(true, true, false); } else { TDX_PS_MASKED(false, true, false); }
-    }
-#undef TDX_PS_MASKED
-    TDX_CHECK_LAUNCH();
-    return 0;
-  }
-  if (x0 == 2) {   // the multistep variants: the (S,5) table (p, q, A, Bx, H) and the history
-    if (guided) {
-      TDX_IO_DISPATCH(io16, T,
-        if (cout == 1) fat_to_thin_conv_kernel<1, false, true, T, true, false, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps);
-        else fat_to_thin_conv_kernel<4, false, true, T, true, false, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps));
-    } else {
-      TDX_IO_DISPATCH(io16, T,
-        if (cout == 1) fat_to_thin_conv_kernel<1, false, true, T, false, false, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps);
-        else fat_to_thin_conv_kernel<4, false, true, T, false, false, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps));
-    }
-    TDX_CHECK_LAUNCH();
-    return 0;
-  }
-  if (x0) {   // the clipped-x0 variants: the (S,5) table
-    if (guided) {
-      TDX_IO_DISPATCH(io16, T,
-        if (cout == 1) fat_to_thin_conv_kernel<1, false, true, T, true, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps);
-        else fat_to_thin_conv_kernel<4, false, true, T, true, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps));
-    } else {
-      TDX_IO_DISPATCH(io16, T,
-        if (cout == 1) fat_to_thin_conv_kernel<1, false, true, T, false, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps);
-        else fat_to_thin_conv_kernel<4, false, true, T, false, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps));
-    }
-    TDX_CHECK_LAUNCH();
-    return 0;
-  }
-  if (guided) {
-    TDX_IO_DISPATCH(io16, T,
-      if (cout == 1) fat_to_thin_conv_kernel<1, false, true, T, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps);
-      else fat_to_thin_conv_kernel<4, false, true, T, true><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps));
-    TDX_CHECK_LAUNCH();
-    return 0;
-  }
+  const int grid = (int)std::min<int64_t>((M + 15) / 16, 8192);
+  PStep ps = s;
+  ps.half = s.guided ? M * cout : 0;
   TDX_IO_DISPATCH(io16, T,
-    if (cout == 1) fat_to_thin_conv_kernel<1, false, true, T><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps);
-    else fat_to_thin_conv_kernel<4, false, true, T><<<grid, 256, 0, st>>>((const T*)in, w, bias, eps_out, B, H, W, IC_CO, ps));
+    if (s.guided) launch_psample_form<T, true>(in, w, bias, eps_out, B, H, W, cout, ps, grid, st);
+    else launch_psample_form<T, false>(in, w, bias, eps_out, B, H, W, cout, ps, grid, st));
   TDX_CHECK_LAUNCH();
   return 0;
 }

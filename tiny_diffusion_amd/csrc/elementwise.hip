@@ -1,7 +1,7 @@
 // HBM-bound elementwise kernels of the DDPM path: q_sample (diffusion.py:177-190),
 // the reverse-process update (diffusion.py:272-274), MSE loss (diffusion.py:231),
 // Adam (diffusion.py:211/236), plus the roofline probes used by bench.py.
-#include "common.h"
+#include "internal.h"
 
 // ------------------------------------------------------------------ q_sample
 // x_t = sqrt_ac[t[n]] * x0 + sqrt_1mac[t[n]] * noise ; 16 B per lane per tensor.
@@ -158,423 +158,190 @@ extern "C" int tdx_q_sample_target_philox(const float* x0, const int64_t* t, con
 }
 
 // ------------------------------------------------------------- p_sample step
-// x' = c1*(x - c2*eps) + sigma*z, evaluated in the reference's operation order
-// (diffusion.py:272-274): mul, sub, mul, mul, add - each rounded separately.
-// (p_step: common.h - the boundary convolution fuses the same update into its epilogue when sampling)
-
-template <bool PHILOX>
-__global__ void p_sample_kernel(float4* xo, const float4* x,  // may alias: in-place update
-                                const float4* __restrict__ eps, const float4* __restrict__ z,
-                                const float* __restrict__ coef, const int32_t* __restrict__ t_idx,
-                                int64_t n4, uint64_t seed, int64_t* counter_dec = nullptr,
-                                const int64_t* __restrict__ tau = nullptr) {
-  // t = the coefficient row.  With a timestep schedule (tau != null, DDIM) it is the step index k and the Philox
-  // stream is the network's timestep tau[k], so the identity schedule draws today's noise; the noise term is
-  // skipped at k == 0 either way.
-  const int t = *t_idx;
-  const uint64_t nt = tau ? (uint64_t)tau[t] : (uint64_t)t;
+// One reverse-process update (PStep, internal.h) over n4 float4, grid-strided; xo may alias x (in-place update).
+// t = the coefficient row.  With a timestep schedule (tau != null, DDIM) it is the step index k and the Philox stream
+// is the network's timestep tau[k], so the identity schedule draws the identity chain's noise; block i, component of
+// the float4.  The noise term is skipped at t == 0 (diffusion.py:267-270) and MS has none: H is uniform over the
+// launch and at H == 0 the history is not loaded at all (the first step's buffer may hold anything).  An element's
+// history is read and written by the same thread, as x is when xo aliases it.
+// GD: x and out hold 2 n4 float4 whose halves ran under the caller's and under the null condition; the two outputs are
+// combined first (cfg_eps is linear in the network's output, whatever it predicts) and the one update is written to
+// both halves.  z, hist, known, mask and the Philox index are the first half's - the guided chain of n samples
+// consumes the stream of the unguided chain of n samples.
+template <int FORM, bool GD, bool MK, bool PHILOX>
+__global__ void pstep_kernel(float4* xo, const float4* x, const float4* __restrict__ out, int64_t n4, const PStep s) {
+  const float4* __restrict__ z = (const float4*)s.z;
+  const float4* __restrict__ known = (const float4*)s.known;
+  const float4* __restrict__ mask = (const float4*)s.mask;
+  float4* hist = (float4*)s.hist;
+  const int t = *s.t_idx;
+  const uint64_t nt = s.tau ? (uint64_t)s.tau[t] : (uint64_t)t;
   // table-mode sampling (tdx_unet_eval_step): the step counter is advanced HERE, by the last kernel of the
   // step, because the head kernel of the step reads it from every workgroup (nobody else touches it in between)
-  if (counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *counter_dec = (int64_t)t - 1;
-  const float c1 = coef[3 * t + 0], c2 = coef[3 * t + 1], sg = coef[3 * t + 2];
+  if (s.counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *s.counter_dec = (int64_t)t - 1;
+  const PRow r = pstep_row<FORM>(s.coef, t);
+  const float w = s.w, lo = s.lo, hi = s.hi;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
        i += (int64_t)gridDim.x * blockDim.x) {
-    float4 xv = x[i], ev = eps[i], zv = make_float4(0.f, 0.f, 0.f, 0.f), o;
-    if (PHILOX) {
-      if (t > 0) zv = philox_normal4((uint64_t)i, nt, seed);
-    } else if (z && t > 0) {  // diffusion.py:267-270: no noise on the last step
-      zv = z[i];
+    const float4 xv = x[i];
+    float4 e = out[i], zh = make_float4(0.f, 0.f, 0.f, 0.f), kn = zh, mv = zh, o, h;
+    if (FORM == TDX_STEP_MS) {
+      if (r.e != 0.0f) zh = hist[i];
+    } else if (PHILOX) {
+      if (t > 0) zh = philox_normal4((uint64_t)i, nt, s.seed);
+    } else if (z && t > 0) {
+      zh = z[i];
     }
-    o.x = p_step(xv.x, ev.x, zv.x, c1, c2, sg);
-    o.y = p_step(xv.y, ev.y, zv.y, c1, c2, sg);
-    o.z = p_step(xv.z, ev.z, zv.z, c1, c2, sg);
-    o.w = p_step(xv.w, ev.w, zv.w, c1, c2, sg);
+    if (MK) { kn = known[i]; mv = mask[i]; }
+    if (GD) {
+      const float4 eu = out[i + n4];
+      e.x = cfg_eps(e.x, eu.x, w);
+      e.y = cfg_eps(e.y, eu.y, w);
+      e.z = cfg_eps(e.z, eu.z, w);
+      e.w = cfg_eps(e.w, eu.w, w);
+    }
+    o.x = pstep_elem<FORM, MK>(xv.x, e.x, zh.x, kn.x, mv.x, r, lo, hi, &h.x);
+    o.y = pstep_elem<FORM, MK>(xv.y, e.y, zh.y, kn.y, mv.y, r, lo, hi, &h.y);
+    o.z = pstep_elem<FORM, MK>(xv.z, e.z, zh.z, kn.z, mv.z, r, lo, hi, &h.z);
+    o.w = pstep_elem<FORM, MK>(xv.w, e.w, zh.w, kn.w, mv.w, r, lo, hi, &h.w);
     xo[i] = o;
+    if (GD) xo[i + n4] = o;
+    if (FORM == TDX_STEP_MS) hist[i] = h;
   }
 }
 
-extern "C" int tdx_p_sample_step(float* x_out, const float* x, const float* eps, const float* z,
-                                 const float* coef, const int32_t* t_idx, int64_t n,
-                                 tdx_stream_t stream) {
-  if (!x_out || !x || !eps || !coef || !t_idx || n <= 0) return TDX_E_BADARG;
-  if (n % 4) return TDX_E_SHAPE;
-  p_sample_kernel<false><<<ew_grid(n / 4, 256), 256, 0, to_stream(stream)>>>(
-      (float4*)x_out, (const float4*)x, (const float4*)eps, (const float4*)z, coef, t_idx, n / 4,
-      0);
+// the 16 live instantiations: EPS has no masked update, MS no noise (one value of PHILOX)
+template <int FORM, bool GD, bool MK>
+static void pstep_launch_noise(const PStep& s, float4* xo, const float4* x, const float4* out, int64_t n4, hipStream_t st) {
+  const int grid = ew_grid(n4, 256);
+  if constexpr (FORM != TDX_STEP_MS) {
+    if (s.philox) {
+      pstep_kernel<FORM, GD, MK, true><<<grid, 256, 0, st>>>(xo, x, out, n4, s);
+      return;
+    }
+  }
+  pstep_kernel<FORM, GD, MK, false><<<grid, 256, 0, st>>>(xo, x, out, n4, s);
+}
+template <int FORM>
+static void pstep_launch_form(const PStep& s, float4* xo, const float4* x, const float4* out, int64_t n4, hipStream_t st) {
+  if (FORM != TDX_STEP_EPS && s.known) {
+    if (s.guided) pstep_launch_noise<FORM, true, FORM != TDX_STEP_EPS>(s, xo, x, out, n4, st);
+    else pstep_launch_noise<FORM, false, FORM != TDX_STEP_EPS>(s, xo, x, out, n4, st);
+  } else {
+    if (s.guided) pstep_launch_noise<FORM, true, false>(s, xo, x, out, n4, st);
+    else pstep_launch_noise<FORM, false, false>(s, xo, x, out, n4, st);
+  }
+}
+
+int tdx_pstep_launch(const PStep& s, float* x_out, const float* x, const float* out, int64_t n, hipStream_t st) {
+  if (!x_out || !x || !out || (s.guided && x_out != x)) return TDX_E_BADARG;
+  const int rc = pstep_valid(s, n);
+  if (rc) return rc;
+  if (s.form == TDX_STEP_EPS) pstep_launch_form<TDX_STEP_EPS>(s, (float4*)x_out, (const float4*)x, (const float4*)out, n / 4, st);
+  else if (s.form == TDX_STEP_X0) pstep_launch_form<TDX_STEP_X0>(s, (float4*)x_out, (const float4*)x, (const float4*)out, n / 4, st);
+  else pstep_launch_form<TDX_STEP_MS>(s, (float4*)x_out, (const float4*)x, (const float4*)out, n / 4, st);
   TDX_CHECK_LAUNCH();
   return 0;
 }
 
-// the update with the counter decrement of table-mode sampling folded in (z == null: in-kernel Philox noise)
-// (counter_dec == null: no decrement; tau != null: coefficient row k, timestep tau[k] - the scheduled update)
-int tdx_p_sample_step_dec(float* x_out, const float* x, const float* eps, const float* z, const float* coef,
-                          const int32_t* t_idx, int64_t n, uint64_t seed, int64_t* counter_dec, hipStream_t st,
-                          const int64_t* tau) {
-  if (!x_out || !x || !eps || !coef || !t_idx || n <= 0) return TDX_E_BADARG;
-  if (n % 4) return TDX_E_SHAPE;
-  if (z)
-    p_sample_kernel<false><<<ew_grid(n / 4, 256), 256, 0, st>>>((float4*)x_out, (const float4*)x, (const float4*)eps,
-                                                               (const float4*)z, coef, t_idx, n / 4, 0, counter_dec,
-                                                               tau);
-  else
-    p_sample_kernel<true><<<ew_grid(n / 4, 256), 256, 0, st>>>((float4*)x_out, (const float4*)x, (const float4*)eps,
-                                                              nullptr, coef, t_idx, n / 4, seed, counter_dec, tau);
-  TDX_CHECK_LAUNCH();
-  return 0;
+static PStep pstep_of(int form, const float* coef, const int32_t* t_idx, const int64_t* tau, const float* z, int philox,
+                      uint64_t seed, int guided, float w, float lo, float hi, float* hist, const float* known,
+                      const float* mask, int64_t* counter_dec) {
+  PStep s{};
+  s.form = form; s.coef = coef; s.t_idx = t_idx; s.tau = tau;
+  s.z = z; s.philox = philox != 0; s.seed = seed;
+  s.guided = guided != 0; s.w = w;
+  s.lo = lo; s.hi = hi;
+  s.hist = hist; s.known = known; s.mask = mask; s.counter_dec = counter_dec;
+  return s;
+}
+
+extern "C" int tdx_p_sample_update(float* x_out, const float* x, const float* out, int64_t n, int form,
+                                   const float* coef, const int32_t* t_idx, const int64_t* tau, const float* z,
+                                   int use_philox, uint64_t philox_seed, int guided, float w, float lo, float hi,
+                                   float* hist, const float* known, const float* mask, int64_t* counter_dec,
+                                   tdx_stream_t stream) {
+  const PStep s = pstep_of(form, coef, t_idx, tau, z, use_philox, philox_seed, guided, w, lo, hi, hist, known, mask,
+                           counter_dec);
+  return tdx_pstep_launch(s, x_out, x, out, n, to_stream(stream)) ? TDX_E_BADARG : 0;
+}
+
+// The entries of each form (include/tdx.h): the null checks that are the entry's own, then the one launcher.
+extern "C" int tdx_p_sample_step(float* x_out, const float* x, const float* eps, const float* z,
+                                 const float* coef, const int32_t* t_idx, int64_t n,
+                                 tdx_stream_t stream) {
+  const PStep s = pstep_of(TDX_STEP_EPS, coef, t_idx, nullptr, z, 0, 0, 0, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr);
+  return tdx_pstep_launch(s, x_out, x, eps, n, to_stream(stream));
 }
 
 extern "C" int tdx_p_sample_step_philox(float* x_out, const float* x, const float* eps,
                                         const float* coef, const int32_t* t_idx, int64_t n,
                                         uint64_t seed, tdx_stream_t stream) {
-  if (!x_out || !x || !eps || !coef || !t_idx || n <= 0) return TDX_E_BADARG;
-  if (n % 4) return TDX_E_SHAPE;
-  p_sample_kernel<true><<<ew_grid(n / 4, 256), 256, 0, to_stream(stream)>>>(
-      (float4*)x_out, (const float4*)x, (const float4*)eps, nullptr, coef, t_idx, n / 4, seed);
-  TDX_CHECK_LAUNCH();
-  return 0;
+  const PStep s = pstep_of(TDX_STEP_EPS, coef, t_idx, nullptr, nullptr, 1, seed, 0, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr);
+  return tdx_pstep_launch(s, x_out, x, eps, n, to_stream(stream));
 }
 
-// The update of a timestep schedule (DDIM): coefficient row k = *k_idx of the (S,3) table, noise at k > 0 only,
-// Philox stream tau[k].  z == null in the first form: no noise term (as tdx_p_sample_step).
 extern "C" int tdx_p_sample_step_sched(float* x_out, const float* x, const float* eps, const float* z,
                                        const float* coef, const int64_t* tau, const int32_t* k_idx, int64_t n,
                                        tdx_stream_t stream) {
-  if (!x_out || !x || !eps || !coef || !tau || !k_idx || n <= 0) return TDX_E_BADARG;
-  if (n % 4) return TDX_E_SHAPE;
-  p_sample_kernel<false><<<ew_grid(n / 4, 256), 256, 0, to_stream(stream)>>>(
-      (float4*)x_out, (const float4*)x, (const float4*)eps, (const float4*)z, coef, k_idx, n / 4, 0, nullptr, tau);
-  TDX_CHECK_LAUNCH();
-  return 0;
+  if (!tau) return TDX_E_BADARG;
+  const PStep s = pstep_of(TDX_STEP_EPS, coef, k_idx, tau, z, 0, 0, 0, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr);
+  return tdx_pstep_launch(s, x_out, x, eps, n, to_stream(stream));
 }
 
 extern "C" int tdx_p_sample_step_sched_philox(float* x_out, const float* x, const float* eps, const float* coef,
                                               const int64_t* tau, const int32_t* k_idx, int64_t n, uint64_t seed,
                                               tdx_stream_t stream) {
-  if (!x_out || !x || !eps || !coef || !tau || !k_idx || n <= 0) return TDX_E_BADARG;
-  if (n % 4) return TDX_E_SHAPE;
-  p_sample_kernel<true><<<ew_grid(n / 4, 256), 256, 0, to_stream(stream)>>>(
-      (float4*)x_out, (const float4*)x, (const float4*)eps, nullptr, coef, k_idx, n / 4, seed, nullptr, tau);
-  TDX_CHECK_LAUNCH();
-  return 0;
+  if (!tau) return TDX_E_BADARG;
+  const PStep s = pstep_of(TDX_STEP_EPS, coef, k_idx, tau, nullptr, 1, seed, 0, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr);
+  return tdx_pstep_launch(s, x_out, x, eps, n, to_stream(stream));
 }
 
-// Guided update (classifier-free guidance).  x and eps hold 2 n4 float4: the first half ran the network under the
-// caller's condition, the second under the null condition, and the two halves of x are equal.  For i < n4:
-// e = cfg_eps(eps[i], eps[i + n4], w), x' = p_step(x[i], e, z, ...) written to x[i] and x[i + n4].  The noise is one draw
-// per element of the FIRST half - z has n4 float4, Philox is indexed by i - so the guided chain of n samples consumes
-// the stream of the unguided chain of n samples.  t, tau and counter_dec as in p_sample_kernel.
-__global__ void p_sample_guided_kernel(float4* x, const float4* __restrict__ eps, const float4* __restrict__ z,
-                                       const float* __restrict__ coef, const int32_t* __restrict__ t_idx, int64_t n4,
-                                       float w, int philox, uint64_t seed, int64_t* counter_dec,
-                                       const int64_t* __restrict__ tau) {
-  const int t = *t_idx;
-  const uint64_t nt = tau ? (uint64_t)tau[t] : (uint64_t)t;
-  if (counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *counter_dec = (int64_t)t - 1;
-  const float c1 = coef[3 * t + 0], c2 = coef[3 * t + 1], sg = coef[3 * t + 2];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 xv = x[i], ec = eps[i], eu = eps[i + n4];
-    float4 zv = make_float4(0.f, 0.f, 0.f, 0.f), o;
-    if (t > 0) {
-      if (philox) zv = philox_normal4((uint64_t)i, nt, seed);
-      else if (z) zv = z[i];
-    }
-    o.x = p_step(xv.x, cfg_eps(ec.x, eu.x, w), zv.x, c1, c2, sg);
-    o.y = p_step(xv.y, cfg_eps(ec.y, eu.y, w), zv.y, c1, c2, sg);
-    o.z = p_step(xv.z, cfg_eps(ec.z, eu.z, w), zv.z, c1, c2, sg);
-    o.w = p_step(xv.w, cfg_eps(ec.w, eu.w, w), zv.w, c1, c2, sg);
-    x[i] = o;
-    x[i + n4] = o;
-  }
-}
-
-// tau == null: the identity chain (t_idx holds the timestep); counter_dec != null: the table-mode decrement
 extern "C" int tdx_p_sample_step_guided(float* x, const float* eps, const float* z, const float* coef,
                                         const int64_t* tau, const int32_t* t_idx, int64_t n_half_elems, float w,
                                         int use_philox, uint64_t philox_seed, int64_t* counter_dec,
                                         tdx_stream_t stream) {
-  if (!x || !eps || !coef || !t_idx || n_half_elems <= 0) return TDX_E_BADARG;
-  if (n_half_elems % 4) return TDX_E_SHAPE;
-  p_sample_guided_kernel<<<ew_grid(n_half_elems / 4, 256), 256, 0, to_stream(stream)>>>(
-      (float4*)x, (const float4*)eps, (const float4*)z, coef, t_idx, n_half_elems / 4, w, use_philox != 0, philox_seed,
-      counter_dec, tau);
-  TDX_CHECK_LAUNCH();
-  return 0;
+  const PStep s = pstep_of(TDX_STEP_EPS, coef, t_idx, tau, z, use_philox, philox_seed, 1, w, 0.f, 0.f, nullptr, nullptr, nullptr, counter_dec);
+  return tdx_pstep_launch(s, x, x, eps, n_half_elems, to_stream(stream));
 }
 
-// ------------------------------------------------------------- p_sample step, x0 form (clipped-x0 sampling)
-// x' = p_step_x0(x, out, z, row t of the (S,5) table (p, q, A, Bx, sigma), lo, hi) (common.h; the boundary convolution
-// fuses the same update into its epilogue).  t, tau, counter_dec, the noise term (none at t == 0) and the Philox
-// indexing (block i, component of the float4, stream tau[t]) are p_sample_kernel's, so a clipped chain consumes the
-// noise of the unclipped chain of the same seed.
-__device__ __forceinline__ float4 p_step_x0_4(const float4 x, const float4 o, const float4 z, float p, float q, float A,
-                                              float Bx, float sg, float lo, float hi) {
-  float4 r;
-  r.x = p_step_x0(x.x, o.x, z.x, p, q, A, Bx, sg, lo, hi);
-  r.y = p_step_x0(x.y, o.y, z.y, p, q, A, Bx, sg, lo, hi);
-  r.z = p_step_x0(x.z, o.z, z.z, p, q, A, Bx, sg, lo, hi);
-  r.w = p_step_x0(x.w, o.w, z.w, p, q, A, Bx, sg, lo, hi);
-  return r;
-}
-
-__global__ void p_sample_x0_kernel(float4* xo, const float4* x,  // may alias: in-place update
-                                   const float4* __restrict__ out, const float4* __restrict__ z,
-                                   const float* __restrict__ coef, const int32_t* __restrict__ t_idx, int64_t n4,
-                                   float lo, float hi, int philox, uint64_t seed, int64_t* counter_dec,
-                                   const int64_t* __restrict__ tau) {
-  const int t = *t_idx;
-  const uint64_t nt = tau ? (uint64_t)tau[t] : (uint64_t)t;
-  if (counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *counter_dec = (int64_t)t - 1;
-  const float p = coef[5 * t + 0], q = coef[5 * t + 1], A = coef[5 * t + 2], Bx = coef[5 * t + 3], sg = coef[5 * t + 4];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 xv = x[i], ov = out[i];
-    float4 zv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (t > 0) {
-      if (philox) zv = philox_normal4((uint64_t)i, nt, seed);
-      else if (z) zv = z[i];
-    }
-    xo[i] = p_step_x0_4(xv, ov, zv, p, q, A, Bx, sg, lo, hi);
-  }
-}
-
-// Guided: the layout and the noise of p_sample_guided_kernel; the two outputs are combined first (cfg_eps is linear in
-// the network's output, whatever it predicts), the x0 form is applied to the combination.
-__global__ void p_sample_x0_guided_kernel(float4* x, const float4* __restrict__ out, const float4* __restrict__ z,
-                                          const float* __restrict__ coef, const int32_t* __restrict__ t_idx,
-                                          int64_t n4, float w, float lo, float hi, int philox, uint64_t seed,
-                                          int64_t* counter_dec, const int64_t* __restrict__ tau) {
-  const int t = *t_idx;
-  const uint64_t nt = tau ? (uint64_t)tau[t] : (uint64_t)t;
-  if (counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *counter_dec = (int64_t)t - 1;
-  const float p = coef[5 * t + 0], q = coef[5 * t + 1], A = coef[5 * t + 2], Bx = coef[5 * t + 3], sg = coef[5 * t + 4];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 xv = x[i], oc = out[i], ou = out[i + n4];
-    float4 zv = make_float4(0.f, 0.f, 0.f, 0.f), e;
-    if (t > 0) {
-      if (philox) zv = philox_normal4((uint64_t)i, nt, seed);
-      else if (z) zv = z[i];
-    }
-    e.x = cfg_eps(oc.x, ou.x, w);
-    e.y = cfg_eps(oc.y, ou.y, w);
-    e.z = cfg_eps(oc.z, ou.z, w);
-    e.w = cfg_eps(oc.w, ou.w, w);
-    const float4 o = p_step_x0_4(xv, e, zv, p, q, A, Bx, sg, lo, hi);
-    x[i] = o;
-    x[i + n4] = o;
-  }
-}
-
-// One entry for every mode: z a noise tensor or null, use_philox in-kernel noise (z ignored), tau null (t_idx holds the
-// timestep) or the schedule's timesteps, counter_dec null or the table-mode step counter.  !(lo < hi) - a NaN
-// included - is a bad argument; infinite bounds never bind.
 extern "C" int tdx_p_sample_step_x0(float* x_out, const float* x, const float* out, const float* z, const float* coef5,
                                     const int64_t* tau, const int32_t* t_idx, int64_t n, float lo, float hi,
                                     int use_philox, uint64_t philox_seed, int64_t* counter_dec, tdx_stream_t stream) {
-  if (!x_out || !x || !out || !coef5 || !t_idx || n <= 0 || (n % 4) || !(lo < hi)) return TDX_E_BADARG;
-  p_sample_x0_kernel<<<ew_grid(n / 4, 256), 256, 0, to_stream(stream)>>>(
-      (float4*)x_out, (const float4*)x, (const float4*)out, (const float4*)z, coef5, t_idx, n / 4, lo, hi,
-      use_philox != 0, philox_seed, counter_dec, tau);
-  TDX_CHECK_LAUNCH();
-  return 0;
+  const PStep s = pstep_of(TDX_STEP_X0, coef5, t_idx, tau, z, use_philox, philox_seed, 0, 0.f, lo, hi, nullptr, nullptr, nullptr, counter_dec);
+  return tdx_pstep_launch(s, x_out, x, out, n, to_stream(stream));
 }
 
 extern "C" int tdx_p_sample_step_x0_guided(float* x, const float* out, const float* z, const float* coef5,
                                            const int64_t* tau, const int32_t* t_idx, int64_t n_half_elems, float w,
                                            float lo, float hi, int use_philox, uint64_t philox_seed,
                                            int64_t* counter_dec, tdx_stream_t stream) {
-  if (!x || !out || !coef5 || !t_idx || n_half_elems <= 0 || (n_half_elems % 4) || !(lo < hi)) return TDX_E_BADARG;
-  p_sample_x0_guided_kernel<<<ew_grid(n_half_elems / 4, 256), 256, 0, to_stream(stream)>>>(
-      (float4*)x, (const float4*)out, (const float4*)z, coef5, t_idx, n_half_elems / 4, w, lo, hi, use_philox != 0,
-      philox_seed, counter_dec, tau);
-  TDX_CHECK_LAUNCH();
-  return 0;
+  const PStep s = pstep_of(TDX_STEP_X0, coef5, t_idx, tau, z, use_philox, philox_seed, 1, w, lo, hi, nullptr, nullptr, nullptr, counter_dec);
+  return tdx_pstep_launch(s, x, x, out, n_half_elems, to_stream(stream));
 }
 
-// ------------------------------------------------------------- p_sample step, multistep (DPM-Solver++(2M))
-// x' = p_step_ms(x, out, hist, row t of the (S,5) table (p, q, A, Bx, H), lo, hi) and hist <- the clamped x0, in one
-// pass (common.h; the boundary convolution fuses the same update into its epilogue).  Deterministic: no noise, so no
-// tau.  H is uniform over the launch: at H == 0 the history is not loaded at all (the first step's buffer may hold
-// anything).  An element's history is read and written by the same thread, as x is when xo aliases it.
-__device__ __forceinline__ float4 p_step_ms_4(const float4 x, const float4 o, const float4 h, float p, float q, float A,
-                                              float Bx, float H, float lo, float hi, float4* x0c) {
-  float4 r;
-  r.x = p_step_ms(x.x, o.x, h.x, p, q, A, Bx, H, lo, hi, &x0c->x);
-  r.y = p_step_ms(x.y, o.y, h.y, p, q, A, Bx, H, lo, hi, &x0c->y);
-  r.z = p_step_ms(x.z, o.z, h.z, p, q, A, Bx, H, lo, hi, &x0c->z);
-  r.w = p_step_ms(x.w, o.w, h.w, p, q, A, Bx, H, lo, hi, &x0c->w);
-  return r;
-}
-
-__global__ void p_sample_ms_kernel(float4* xo, const float4* x,  // may alias: in-place update
-                                   const float4* __restrict__ out, float4* hist, const float* __restrict__ coef,
-                                   const int32_t* __restrict__ t_idx, int64_t n4, float lo, float hi,
-                                   int64_t* counter_dec) {
-  const int t = *t_idx;
-  if (counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *counter_dec = (int64_t)t - 1;
-  const float p = coef[5 * t + 0], q = coef[5 * t + 1], A = coef[5 * t + 2], Bx = coef[5 * t + 3], H = coef[5 * t + 4];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 xv = x[i], ov = out[i];
-    float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), x0c;
-    if (H != 0.0f) hv = hist[i];
-    xo[i] = p_step_ms_4(xv, ov, hv, p, q, A, Bx, H, lo, hi, &x0c);
-    hist[i] = x0c;
-  }
-}
-
-// Guided: the layout of p_sample_guided_kernel; the two outputs are combined first (cfg_eps), the multistep update is
-// applied to the combination against ONE history of n4 float4 (the two halves of x are equal), written to both halves.
-__global__ void p_sample_ms_guided_kernel(float4* x, const float4* __restrict__ out, float4* hist,
-                                          const float* __restrict__ coef, const int32_t* __restrict__ t_idx,
-                                          int64_t n4, float w, float lo, float hi, int64_t* counter_dec) {
-  const int t = *t_idx;
-  if (counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *counter_dec = (int64_t)t - 1;
-  const float p = coef[5 * t + 0], q = coef[5 * t + 1], A = coef[5 * t + 2], Bx = coef[5 * t + 3], H = coef[5 * t + 4];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 xv = x[i], oc = out[i], ou = out[i + n4];
-    float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), x0c, e;
-    if (H != 0.0f) hv = hist[i];
-    e.x = cfg_eps(oc.x, ou.x, w);
-    e.y = cfg_eps(oc.y, ou.y, w);
-    e.z = cfg_eps(oc.z, ou.z, w);
-    e.w = cfg_eps(oc.w, ou.w, w);
-    const float4 o = p_step_ms_4(xv, e, hv, p, q, A, Bx, H, lo, hi, &x0c);
-    x[i] = o;
-    x[i + n4] = o;
-    hist[i] = x0c;
-  }
-}
-
-// counter_dec null or the table-mode step counter.  !(lo < hi) - a NaN included - is a bad argument; infinite bounds
-// never bind (no clipping).  hist: n floats, read only when the row's H != 0, always written.
 extern "C" int tdx_p_sample_step_ms(float* x_out, const float* x, const float* out, float* hist, const float* coef5,
                                     const int32_t* t_idx, int64_t n, float lo, float hi, int64_t* counter_dec,
                                     tdx_stream_t stream) {
-  if (!x_out || !x || !out || !hist || !coef5 || !t_idx || n <= 0 || (n % 4) || !(lo < hi)) return TDX_E_BADARG;
-  p_sample_ms_kernel<<<ew_grid(n / 4, 256), 256, 0, to_stream(stream)>>>(
-      (float4*)x_out, (const float4*)x, (const float4*)out, (float4*)hist, coef5, t_idx, n / 4, lo, hi, counter_dec);
-  TDX_CHECK_LAUNCH();
-  return 0;
+  const PStep s = pstep_of(TDX_STEP_MS, coef5, t_idx, nullptr, nullptr, 0, 0, 0, 0.f, lo, hi, hist, nullptr, nullptr, counter_dec);
+  return tdx_pstep_launch(s, x_out, x, out, n, to_stream(stream));
 }
 
 extern "C" int tdx_p_sample_step_ms_guided(float* x, const float* out, float* hist, const float* coef5,
                                            const int32_t* t_idx, int64_t n_half_elems, float w, float lo, float hi,
                                            int64_t* counter_dec, tdx_stream_t stream) {
-  if (!x || !out || !hist || !coef5 || !t_idx || n_half_elems <= 0 || (n_half_elems % 4) || !(lo < hi))
-    return TDX_E_BADARG;
-  p_sample_ms_guided_kernel<<<ew_grid(n_half_elems / 4, 256), 256, 0, to_stream(stream)>>>(
-      (float4*)x, (const float4*)out, (float4*)hist, coef5, t_idx, n_half_elems / 4, w, lo, hi, counter_dec);
-  TDX_CHECK_LAUNCH();
-  return 0;
+  const PStep s = pstep_of(TDX_STEP_MS, coef5, t_idx, nullptr, nullptr, 0, 0, 1, w, lo, hi, hist, nullptr, nullptr, counter_dec);
+  return tdx_pstep_launch(s, x, x, out, n_half_elems, to_stream(stream));
 }
 
-// ------------------------------------------------------------- p_sample step, masked (inpainting)
-// The x0-form and the multistep update with a known region (common.h: x0_blend, p_step_x0_masked, p_step_ms_masked):
-// the clamped prediction is blended with `known` under `mask` before the step.  known / mask hold one value per element
-// of the n samples (guided: of the first half, indexed like hist).  Everything else - t, tau, counter_dec, the noise,
-// the Philox indexing, in-place use, the H == 0 rule - is the unmasked kernel's, which these stand beside.
-__device__ __forceinline__ float4 p_step_x0_masked_4(const float4 x, const float4 o, const float4 z, const float4 kn,
-                                                     const float4 m, float p, float q, float A, float Bx, float sg,
-                                                     float lo, float hi) {
-  float4 r;
-  r.x = p_step_x0_masked(x.x, o.x, z.x, kn.x, m.x, p, q, A, Bx, sg, lo, hi);
-  r.y = p_step_x0_masked(x.y, o.y, z.y, kn.y, m.y, p, q, A, Bx, sg, lo, hi);
-  r.z = p_step_x0_masked(x.z, o.z, z.z, kn.z, m.z, p, q, A, Bx, sg, lo, hi);
-  r.w = p_step_x0_masked(x.w, o.w, z.w, kn.w, m.w, p, q, A, Bx, sg, lo, hi);
-  return r;
-}
-
-__device__ __forceinline__ float4 p_step_ms_masked_4(const float4 x, const float4 o, const float4 h, const float4 kn,
-                                                     const float4 m, float p, float q, float A, float Bx, float H,
-                                                     float lo, float hi, float4* x0m) {
-  float4 r;
-  r.x = p_step_ms_masked(x.x, o.x, h.x, kn.x, m.x, p, q, A, Bx, H, lo, hi, &x0m->x);
-  r.y = p_step_ms_masked(x.y, o.y, h.y, kn.y, m.y, p, q, A, Bx, H, lo, hi, &x0m->y);
-  r.z = p_step_ms_masked(x.z, o.z, h.z, kn.z, m.z, p, q, A, Bx, H, lo, hi, &x0m->z);
-  r.w = p_step_ms_masked(x.w, o.w, h.w, kn.w, m.w, p, q, A, Bx, H, lo, hi, &x0m->w);
-  return r;
-}
-
-// GD = false: p_sample_x0_kernel's layout (xo may alias x).  GD = true: p_sample_x0_guided_kernel's (xo == x holds
-// 2 n4 float4, out likewise; the two outputs are combined first and the one update is written to both halves).
-template <bool GD>
-__global__ void p_sample_x0_masked_kernel(float4* xo, const float4* x, const float4* __restrict__ out,
-                                          const float4* __restrict__ z, const float4* __restrict__ known,
-                                          const float4* __restrict__ mask, const float* __restrict__ coef,
-                                          const int32_t* __restrict__ t_idx, int64_t n4, float w, float lo, float hi,
-                                          int philox, uint64_t seed, int64_t* counter_dec,
-                                          const int64_t* __restrict__ tau) {
-  const int t = *t_idx;
-  const uint64_t nt = tau ? (uint64_t)tau[t] : (uint64_t)t;
-  if (counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *counter_dec = (int64_t)t - 1;
-  const float p = coef[5 * t + 0], q = coef[5 * t + 1], A = coef[5 * t + 2], Bx = coef[5 * t + 3], sg = coef[5 * t + 4];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 xv = x[i], kn = known[i], mv = mask[i];
-    float4 e = out[i];
-    float4 zv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (t > 0) {
-      if (philox) zv = philox_normal4((uint64_t)i, nt, seed);
-      else if (z) zv = z[i];
-    }
-    if (GD) {
-      const float4 ou = out[i + n4];
-      e.x = cfg_eps(e.x, ou.x, w);
-      e.y = cfg_eps(e.y, ou.y, w);
-      e.z = cfg_eps(e.z, ou.z, w);
-      e.w = cfg_eps(e.w, ou.w, w);
-    }
-    const float4 o = p_step_x0_masked_4(xv, e, zv, kn, mv, p, q, A, Bx, sg, lo, hi);
-    xo[i] = o;
-    if (GD) xo[i + n4] = o;
-  }
-}
-
-template <bool GD>
-__global__ void p_sample_ms_masked_kernel(float4* xo, const float4* x, const float4* __restrict__ out, float4* hist,
-                                          const float4* __restrict__ known, const float4* __restrict__ mask,
-                                          const float* __restrict__ coef, const int32_t* __restrict__ t_idx,
-                                          int64_t n4, float w, float lo, float hi, int64_t* counter_dec) {
-  const int t = *t_idx;
-  if (counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *counter_dec = (int64_t)t - 1;
-  const float p = coef[5 * t + 0], q = coef[5 * t + 1], A = coef[5 * t + 2], Bx = coef[5 * t + 3], H = coef[5 * t + 4];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 xv = x[i], kn = known[i], mv = mask[i];
-    float4 e = out[i];
-    float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), x0m;
-    if (H != 0.0f) hv = hist[i];
-    if (GD) {
-      const float4 ou = out[i + n4];
-      e.x = cfg_eps(e.x, ou.x, w);
-      e.y = cfg_eps(e.y, ou.y, w);
-      e.z = cfg_eps(e.z, ou.z, w);
-      e.w = cfg_eps(e.w, ou.w, w);
-    }
-    const float4 o = p_step_ms_masked_4(xv, e, hv, kn, mv, p, q, A, Bx, H, lo, hi, &x0m);
-    xo[i] = o;
-    if (GD) xo[i + n4] = o;
-    hist[i] = x0m;
-  }
-}
-
-// The arguments of tdx_p_sample_step_x0 plus known / mask (n floats each); TDX_E_BADARG in its cases and for a null
-// known or mask.
 extern "C" int tdx_p_sample_step_x0_masked(float* x_out, const float* x, const float* out, const float* z,
                                            const float* known, const float* mask, const float* coef5,
                                            const int64_t* tau, const int32_t* t_idx, int64_t n, float lo, float hi,
                                            int use_philox, uint64_t philox_seed, int64_t* counter_dec,
                                            tdx_stream_t stream) {
-  if (!x_out || !x || !out || !known || !mask || !coef5 || !t_idx || n <= 0 || (n % 4) || !(lo < hi))
-    return TDX_E_BADARG;
-  p_sample_x0_masked_kernel<false><<<ew_grid(n / 4, 256), 256, 0, to_stream(stream)>>>(
-      (float4*)x_out, (const float4*)x, (const float4*)out, (const float4*)z, (const float4*)known, (const float4*)mask,
-      coef5, t_idx, n / 4, 0.f, lo, hi, use_philox != 0, philox_seed, counter_dec, tau);
-  TDX_CHECK_LAUNCH();
-  return 0;
+  if (!known || !mask) return TDX_E_BADARG;
+  const PStep s = pstep_of(TDX_STEP_X0, coef5, t_idx, tau, z, use_philox, philox_seed, 0, 0.f, lo, hi, nullptr, known, mask, counter_dec);
+  return tdx_pstep_launch(s, x_out, x, out, n, to_stream(stream));
 }
 
 extern "C" int tdx_p_sample_step_x0_guided_masked(float* x, const float* out, const float* z, const float* known,
@@ -582,41 +349,27 @@ extern "C" int tdx_p_sample_step_x0_guided_masked(float* x, const float* out, co
                                                   const int32_t* t_idx, int64_t n_half_elems, float w, float lo,
                                                   float hi, int use_philox, uint64_t philox_seed, int64_t* counter_dec,
                                                   tdx_stream_t stream) {
-  if (!x || !out || !known || !mask || !coef5 || !t_idx || n_half_elems <= 0 || (n_half_elems % 4) || !(lo < hi))
-    return TDX_E_BADARG;
-  p_sample_x0_masked_kernel<true><<<ew_grid(n_half_elems / 4, 256), 256, 0, to_stream(stream)>>>(
-      (float4*)x, (const float4*)x, (const float4*)out, (const float4*)z, (const float4*)known, (const float4*)mask,
-      coef5, t_idx, n_half_elems / 4, w, lo, hi, use_philox != 0, philox_seed, counter_dec, tau);
-  TDX_CHECK_LAUNCH();
-  return 0;
+  if (!known || !mask) return TDX_E_BADARG;
+  const PStep s = pstep_of(TDX_STEP_X0, coef5, t_idx, tau, z, use_philox, philox_seed, 1, w, lo, hi, nullptr, known, mask, counter_dec);
+  return tdx_pstep_launch(s, x, x, out, n_half_elems, to_stream(stream));
 }
 
-// The arguments of tdx_p_sample_step_ms plus known / mask; hist receives the blended prediction.
 extern "C" int tdx_p_sample_step_ms_masked(float* x_out, const float* x, const float* out, float* hist,
                                            const float* known, const float* mask, const float* coef5,
                                            const int32_t* t_idx, int64_t n, float lo, float hi, int64_t* counter_dec,
                                            tdx_stream_t stream) {
-  if (!x_out || !x || !out || !hist || !known || !mask || !coef5 || !t_idx || n <= 0 || (n % 4) || !(lo < hi))
-    return TDX_E_BADARG;
-  p_sample_ms_masked_kernel<false><<<ew_grid(n / 4, 256), 256, 0, to_stream(stream)>>>(
-      (float4*)x_out, (const float4*)x, (const float4*)out, (float4*)hist, (const float4*)known, (const float4*)mask,
-      coef5, t_idx, n / 4, 0.f, lo, hi, counter_dec);
-  TDX_CHECK_LAUNCH();
-  return 0;
+  if (!known || !mask) return TDX_E_BADARG;
+  const PStep s = pstep_of(TDX_STEP_MS, coef5, t_idx, nullptr, nullptr, 0, 0, 0, 0.f, lo, hi, hist, known, mask, counter_dec);
+  return tdx_pstep_launch(s, x_out, x, out, n, to_stream(stream));
 }
 
 extern "C" int tdx_p_sample_step_ms_guided_masked(float* x, const float* out, float* hist, const float* known,
                                                   const float* mask, const float* coef5, const int32_t* t_idx,
                                                   int64_t n_half_elems, float w, float lo, float hi,
                                                   int64_t* counter_dec, tdx_stream_t stream) {
-  if (!x || !out || !hist || !known || !mask || !coef5 || !t_idx || n_half_elems <= 0 || (n_half_elems % 4) ||
-      !(lo < hi))
-    return TDX_E_BADARG;
-  p_sample_ms_masked_kernel<true><<<ew_grid(n_half_elems / 4, 256), 256, 0, to_stream(stream)>>>(
-      (float4*)x, (const float4*)x, (const float4*)out, (float4*)hist, (const float4*)known, (const float4*)mask, coef5,
-      t_idx, n_half_elems / 4, w, lo, hi, counter_dec);
-  TDX_CHECK_LAUNCH();
-  return 0;
+  if (!known || !mask) return TDX_E_BADARG;
+  const PStep s = pstep_of(TDX_STEP_MS, coef5, t_idx, nullptr, nullptr, 0, 0, 1, w, lo, hi, hist, known, mask, counter_dec);
+  return tdx_pstep_launch(s, x, x, out, n_half_elems, to_stream(stream));
 }
 
 // Device-side step counter for graph-captured sampling: t = *counter; t_idx = t; t_vec[:] = t;

@@ -18,13 +18,45 @@ int tdx_initial_conv_dgrad(const void* g_x0, const float* w, float* g_x, int B, 
                            int cout_real, hipStream_t st, int io16 = 0);
 int tdx_final_conv_fwd(const void* in, const float* w, const float* bias, float* out, int B, int H,
                        int W, int cout, hipStream_t st, int io16 = 0);
+// One reverse-process update x <- step(x, out, noise | history), as the elementwise kernel (tdx_pstep_launch,
+// elementwise.hip) and the epilogue of final_conv (tdx_final_conv_fwd_psample, edge_conv.hip) run it.  form says what
+// the rows of coef are and which update of common.h (pstep_elem) they drive:
+//   TDX_STEP_EPS  (S,3) rows (c1, c2, sigma)         x' = c1*(x - c2*out) + sigma*z
+//   TDX_STEP_X0   (S,5) rows (p, q, A, Bx, sigma)    x' = (A*x0 + Bx*x) + sigma*z,  x0 = clamp(p*x + q*out, lo, hi)
+//   TDX_STEP_MS   (S,5) rows (p, q, A, Bx, H)        x' = (A*x0 + Bx*x) + H*hist;  hist <- x0   (deterministic)
+// Row t = *t_idx.  Noise at t > 0 only: Philox block (element / 4), stream tau[t] (t when tau == null), or z, or none.
+// guided: x and out hold two halves - the caller's condition, the null condition - that cfg_eps combines under w; the
+// one update is written to both halves of x, and z / hist / known / mask / Philox are those of the first half.
+// known / mask (X0, MS): x0 <- x0_blend(x0, known, mask) before the step (inpainting).
+struct PStep {
+  int form; const float* coef; const int32_t* t_idx; const int64_t* tau;
+  const float* z; int philox; uint64_t seed;   // philox: in-kernel noise, z ignored
+  int guided; float w;
+  float lo, hi;
+  float* hist;
+  const float* known; const float* mask;
+  int64_t* counter_dec;   // non-null: *counter_dec = *t_idx - 1 (the table-mode step counter, advanced by a step's last kernel)
+  // the fused epilogue only: the state it updates in place (x and z start at this launch's first element), that
+  // element's index in the whole batch (a half-batch launch keeps the batch's Philox stream; hist, known and mask are
+  // indexed by it) and the elements of one guided half
+  float* x; int64_t elem0, half;
+};
+// 0, or the error of an update over n elements (guided: per half): TDX_E_SHAPE for an eps-form n % 4 != 0 with
+// nothing else wrong, as the eps-form entries have always answered; TDX_E_BADARG for every other broken rule
+static inline int pstep_valid(const PStep& s, int64_t n) {
+  if (!s.coef || !s.t_idx || n <= 0 || (s.elem0 & 3) || (s.guided && s.elem0)) return TDX_E_BADARG;
+  if (s.form != TDX_STEP_EPS && s.form != TDX_STEP_X0 && s.form != TDX_STEP_MS) return TDX_E_BADARG;
+  if (s.form != TDX_STEP_EPS && !(s.lo < s.hi)) return TDX_E_BADARG;   // rejects a NaN bound
+  if (s.form == TDX_STEP_MS && (!s.hist || s.z)) return TDX_E_BADARG;
+  if ((s.known != nullptr) != (s.mask != nullptr) || (s.known && s.form == TDX_STEP_EPS)) return TDX_E_BADARG;
+  if (n % 4) return s.form == TDX_STEP_EPS ? TDX_E_SHAPE : TDX_E_BADARG;
+  return 0;
+}
+// x_out may alias x (guided: it must); the fused-only fields of s are ignored
+int tdx_pstep_launch(const PStep& s, float* x_out, const float* x, const float* out, int64_t n, hipStream_t st);
+// final_conv forward with the update in its epilogue (sampling): s.x in place, the network's output still goes to eps_out
 int tdx_final_conv_fwd_psample(const void* in, const float* w, const float* bias, float* eps_out, int B, int H, int W,
-                               int cout, float* x, const float* z, const float* coef, const int32_t* t_idx,
-                               uint64_t seed, int philox, int64_t* counter_dec, hipStream_t st, int io16 = 0,
-                               int64_t elem0 = 0, const int64_t* tau = nullptr, int guided = 0, float gw = 0.f,
-                               int x0 = 0, float lo = 0.f, float hi = 0.f,   // x0 = 1: the (S,5) table and the clamp of p_step_x0
-                               float* hist = nullptr,   // x0 = 2: the (S,5) table of p_step_ms, its clamp and its history
-                               const float* known = nullptr, const float* mask = nullptr);   // x0 != 0, both or neither: the masked update (inpainting)
+                               int cout, const PStep& s, hipStream_t st, int io16 = 0);
 int tdx_final_conv_dgrad(const float* g_out, const float* w, void* g_in, int B, int H, int W,
                          int cout, hipStream_t st, int io16 = 0);
 int tdx_final_conv_wgrad(const void* in, const float* g_out, float* partial, float* dw, float* db,
@@ -129,9 +161,6 @@ int tdx_sample_head(const int64_t* counter, int32_t* t_idx, int64_t* t_vec, int 
                     const float* tab2, const float* tab3, const float* tc1, const float* tc2, const float* tc3,
                     float* o1, float* o2, float* o3, hipStream_t st, int B0 = 0, float* o1b = nullptr, float* o2b = nullptr,
                     float* o3b = nullptr, const int64_t* tau = nullptr);
-int tdx_p_sample_step_dec(float* x_out, const float* x, const float* eps, const float* z, const float* coef,
-                          const int32_t* t_idx, int64_t n, uint64_t seed, int64_t* counter_dec, hipStream_t st,
-                          const int64_t* tau = nullptr);
 // latent MLP noise model (latent_diffusion.py:16-128), kind TDX_UNET_LATENT_MLP of tdx_unet_*
 size_t tdx_latent_workspace_floats(int B);
 size_t tdx_latent_infer_ss_floats(void);

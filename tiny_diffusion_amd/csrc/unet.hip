@@ -229,7 +229,7 @@ struct tdx_unet {
   const int64_t* tab_tau;   // timestep schedule the T rows were built at (tdx_unet_prepare_sampling_sched); null: t = 0..T-1
   bool skip_time_path;   // set by tdx_unet_eval_step around its forward: the projections are already in the workspace
   // set by tdx_unet_eval_step around its forward: final_conv applies the reverse-process update in its epilogue
-  struct PS { float* x; const float* z; const float* coef; const int32_t* t_idx; uint64_t seed; int philox; int64_t* counter_dec; int64_t elem0; const int64_t* tau; int guided; float w; int x0; float lo, hi; float* hist; const float* known; const float* mask; } ps;   // x0: 1 = coef is the (S,5) table of the clipped-x0 update, lo / hi its clamp; 2 = the multistep table, hist its history; known / mask (x0 != 0): the masked update, indexed like hist
+  PStep ps;   // ps.x != null: armed
   bool whole_batch;      // set by a guided eval step around its forward: the two halves of a guided batch are not the halves of "sample_halves"
   // half-batch inference (tdx_unet_forward, INFER mode): the second half runs on this stream, forked from / joined to the caller's
   hipStream_t half_own;
@@ -662,7 +662,7 @@ static int pack_tail(tdx_unet* u, const void* const* params, tdx_stream_t stream
 // joined at the end (legal inside a stream capture: tools/micro/capture_fork_probe.hip, cases 0-11) - each in a
 // workspace layout of its own: one half's bubbles, tails and small kernels are covered by the other half's
 // convolutions.  Results equal the whole-batch forward up to the summation order of the split-K plans (which
-// depend on M); in-kernel noise keeps the whole batch's Philox indexing (PS::elem0).
+// depend on M); in-kernel noise keeps the whole batch's Philox indexing (PStep::elem0).
 static bool infer_halves(const tdx_unet* u, int batch, size_t workspace_bytes, int* b0) {
   if (!u->spec || !u->half_own || u->whole_batch || !g_tdx_sample_halves || batch < 2 || batch < g_tdx_sample_halves_min) return false;
   const int h0 = (batch + 1) / 2;
@@ -673,7 +673,7 @@ static bool infer_halves(const tdx_unet* u, int batch, size_t workspace_bytes, i
 
 static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const* buffers, const float* x,
                              const int64_t* t, const void* cond, float* out, void* workspace, size_t workspace_bytes,
-                             int batch, int mode, tdx_stream_t stream, const tdx_unet::PS& ps);
+                             int batch, int mode, tdx_stream_t stream, const PStep& ps);
 
 extern "C" int tdx_unet_forward(tdx_unet* u, const void* const* params, void* const* buffers,
                                 const float* x, const int64_t* t, const void* cond, float* out,
@@ -694,7 +694,7 @@ extern "C" int tdx_unet_forward(tdx_unet* u, const void* const* params, void* co
     const void* cond1 = !cond ? nullptr
                         : u->kind == 1 ? static_cast<const void*>(static_cast<const float*>(cond) + (size_t)b0 * S.time_dim)
                                        : static_cast<const void*>(static_cast<const int64_t*>(cond) + b0);
-    tdx_unet::PS ps0 = u->ps, ps1 = u->ps;
+    PStep ps0 = u->ps, ps1 = u->ps;
     if (ps1.x) {
       ps1.x += b0 * per;
       if (ps1.z) ps1.z += b0 * per;
@@ -717,7 +717,7 @@ extern "C" int tdx_unet_forward(tdx_unet* u, const void* const* params, void* co
 
 static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const* buffers, const float* x,
                              const int64_t* t, const void* cond, float* out, void* workspace, size_t workspace_bytes,
-                             int batch, int mode, tdx_stream_t stream, const tdx_unet::PS& ps) {
+                             int batch, int mode, tdx_stream_t stream, const PStep& ps) {
   if (!u->spec) {  // latent MLP
     if (workspace_bytes < tdx_latent_workspace_floats(batch) * sizeof(float)) return TDX_E_WORKSPACE;
     if (mode == TDX_MODE_INFER && !u->packed) {
@@ -930,8 +930,7 @@ static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const
                              S.out_hw, S.out_hw, 64, 64, 0, io16, stream));
   if (infer && ps.x)
     RC(tdx_final_conv_fwd_psample(ws + L.d1a, P[TDX_P_FINAL_W], P[TDX_P_FINAL_B], out, B, S.out_hw, S.out_hw, S.in_ch,
-                                  ps.x, ps.z, ps.coef, ps.t_idx, ps.seed, ps.philox, ps.counter_dec, st, io16, ps.elem0,
-                                  ps.tau, ps.guided, ps.w, ps.x0, ps.lo, ps.hi, ps.hist, ps.known, ps.mask));
+                                  ps, st, io16));
   else
     RC(tdx_final_conv_fwd(ws + L.d1a, P[TDX_P_FINAL_W], P[TDX_P_FINAL_B], out, B, S.out_hw, S.out_hw, S.in_ch, st, io16));
 
@@ -1284,26 +1283,20 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
   return 0;
 }
 
-// tau == null: the step counter is the timestep t (tdx_unet_eval_step).  tau != null: a schedule of n_steps steps
-// (tdx_unet_eval_step_sched) - the counter is the step index k, the coefficient row, and the network runs at tau[k].
-// guided (tdx_unet_eval_step_guided): batch = 2n rows of x, the second half under the null condition, n_elems the first
-// half's; the update combines the two predictions with scale w and writes both halves (z: n rows).
-// x0 (tdx_unet_eval_step_x0): coef is the (S,5) table of the clipped-x0 update and lo / hi its clamp; the head, the
-// counter and the half-batch logic do not know the difference.  x0 == 2 (tdx_unet_eval_step_ms): the (S,5) table of
-// the multistep update and its history hist (z is null: the chain is deterministic); a half-batch launch indexes the
-// one history by the element's place in the whole batch (PS::elem0).  known / mask (tdx_unet_eval_step_{x0,ms}_masked;
-// x0 != 0, both or neither): the masked update, n_elems floats each, indexed like the history.
+// One reverse step: the head (step counter, timestep vector), the forward and the update ps (PStep, internal.h; its
+// counter_dec and fused-only fields are set here).  ps.tau == null: the step counter is the timestep t; otherwise a
+// schedule of n_steps steps - the counter is the step index k, the coefficient row, and the network runs at tau[k].
+// ps.guided: batch = 2n rows of x, the second half under the null condition, n_elems the first half's.  The head, the
+// counter and the half-batch logic do not know the update's form; a half-batch launch indexes the one history, known
+// and mask by the element's place in the whole batch (PStep::elem0).
 static int eval_step_impl(tdx_unet* u, const void* const* params, void* const* buffers, float* x, const void* cond,
-                          const float* z, const float* coef, const int64_t* tau, int n_steps, int64_t* counter, int32_t* t_idx,
-                          int64_t* t_vec, float* eps, int64_t n_elems, void* workspace, size_t workspace_bytes,
-                          int batch, uint64_t philox_seed, tdx_stream_t stream, bool guided = false, float w = 0.f,
-                          int x0 = 0, float lo = 0.f, float hi = 0.f, float* hist = nullptr,
-                          const float* known = nullptr, const float* mask = nullptr) {
-  if (!u || !x || !coef || !counter || !t_idx || !t_vec || !eps || batch <= 0 || n_elems <= 0)
-    return TDX_E_BADARG;
-  if (x0 && !(lo < hi)) return TDX_E_BADARG;
-  if (x0 == 2 && (!hist || z)) return TDX_E_BADARG;
-  if ((known != nullptr) != (mask != nullptr) || (known && !x0)) return TDX_E_BADARG;
+                          PStep ps, int n_steps, int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps,
+                          int64_t n_elems, void* workspace, size_t workspace_bytes, int batch, tdx_stream_t stream) {
+  const int64_t* tau = ps.tau;
+  const bool guided = ps.guided;
+  if (!u || !params || !buffers || !x || !counter || !t_vec || !eps || !workspace || batch <= 0 || ps.t_idx != t_idx)
+    return TDX_E_BADARG;   // (params, buffers, workspace: before the head kernel writes anything, not after)
+  if (const int rc = pstep_valid(ps, n_elems)) return rc;
   if (guided) {
     if (!u->spec) return TDX_E_SHAPE;   // the UNets only
     if ((batch & 1) || 2 * n_elems != (int64_t)batch * u->spec->in_ch * u->spec->out_hw * u->spec->out_hw) return TDX_E_BADARG;
@@ -1347,51 +1340,28 @@ static int eval_step_impl(tdx_unet* u, const void* const* params, void* const* b
   // the UNets apply the update in final_conv's epilogue (one launch less); the latent MLP keeps the separate kernel
   const bool fuse_ps = u->spec && (g_tdx_sample_fuse & 4) &&
                        (guided ? 2 : 1) * n_elems == (int64_t)batch * u->spec->in_ch * u->spec->out_hw * u->spec->out_hw;
-  if (fuse_ps) u->ps = {x, z, coef, t_idx, philox_seed, z ? 0 : 1, tab ? counter : nullptr, 0, tau, guided, w, x0, lo, hi, hist, known, mask};
+  ps.counter_dec = tab ? counter : nullptr;
+  if (fuse_ps) { u->ps = ps; u->ps.x = x; }
   const int rc = tdx_unet_forward(u, params, buffers, x, t_vec, cond, eps, workspace, workspace_bytes, batch,
                                   TDX_MODE_INFER, stream);
   u->skip_time_path = false;
   u->whole_batch = false;
   u->ps = {};
-  if (rc) return rc;
-  if (fuse_ps) return 0;
-  if (known) {   // the separate masked kernels, exactly where the unmasked step falls back to the separate ones
-    if (x0 == 2) {
-      if (guided)
-        return tdx_p_sample_step_ms_guided_masked(x, eps, hist, known, mask, coef, t_idx, n_elems, w, lo, hi,
-                                                  tab ? counter : nullptr, stream);
-      return tdx_p_sample_step_ms_masked(x, x, eps, hist, known, mask, coef, t_idx, n_elems, lo, hi,
-                                         tab ? counter : nullptr, stream);
-    }
-    if (guided)
-      return tdx_p_sample_step_x0_guided_masked(x, eps, z, known, mask, coef, tau, t_idx, n_elems, w, lo, hi, z ? 0 : 1,
-                                                philox_seed, tab ? counter : nullptr, stream);
-    return tdx_p_sample_step_x0_masked(x, x, eps, z, known, mask, coef, tau, t_idx, n_elems, lo, hi, z ? 0 : 1,
-                                       philox_seed, tab ? counter : nullptr, stream);
-  }
-  if (x0 == 2) {
-    if (guided)
-      return tdx_p_sample_step_ms_guided(x, eps, hist, coef, t_idx, n_elems, w, lo, hi, tab ? counter : nullptr, stream);
-    return tdx_p_sample_step_ms(x, x, eps, hist, coef, t_idx, n_elems, lo, hi, tab ? counter : nullptr, stream);
-  }
-  if (x0) {
-    if (guided)
-      return tdx_p_sample_step_x0_guided(x, eps, z, coef, tau, t_idx, n_elems, w, lo, hi, z ? 0 : 1, philox_seed,
-                                         tab ? counter : nullptr, stream);
-    return tdx_p_sample_step_x0(x, x, eps, z, coef, tau, t_idx, n_elems, lo, hi, z ? 0 : 1, philox_seed,
-                                tab ? counter : nullptr, stream);
-  }
-  if (guided)
-    return tdx_p_sample_step_guided(x, eps, z, coef, tau, t_idx, n_elems, w, z ? 0 : 1, philox_seed, tab ? counter : nullptr,
-                                    stream);
-  // elementwise, so x is updated in place; both kernels skip the noise term at t == 0
-  if (tab) return tdx_p_sample_step_dec(x, x, eps, z, coef, t_idx, n_elems, philox_seed, counter, to_stream(stream), tau);
-  if (tau) {
-    if (z) return tdx_p_sample_step_sched(x, x, eps, z, coef, tau, t_idx, n_elems, stream);
-    return tdx_p_sample_step_sched_philox(x, x, eps, coef, tau, t_idx, n_elems, philox_seed, stream);
-  }
-  if (z) return tdx_p_sample_step(x, x, eps, z, coef, t_idx, n_elems, stream);
-  return tdx_p_sample_step_philox(x, x, eps, coef, t_idx, n_elems, philox_seed, stream);
+  if (rc || fuse_ps) return rc;
+  // elementwise, so x is updated in place
+  return tdx_pstep_launch(ps, x, x, eps, n_elems, to_stream(stream));
+}
+
+static PStep eval_pstep(int form, const float* coef, const int32_t* t_idx, const int64_t* tau, const float* z,
+                        uint64_t philox_seed, int guided, float w, float lo, float hi, float* hist, const float* known,
+                        const float* mask) {
+  PStep s{};
+  s.form = form; s.coef = coef; s.t_idx = t_idx; s.tau = tau;
+  s.z = z; s.philox = !z && form != TDX_STEP_MS; s.seed = philox_seed;   // z == null: in-kernel Philox noise
+  s.guided = guided != 0; s.w = w;
+  s.lo = lo; s.hi = hi;
+  s.hist = hist; s.known = known; s.mask = mask;
+  return s;
 }
 
 extern "C" int tdx_unet_eval_step(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
@@ -1399,86 +1369,24 @@ extern "C" int tdx_unet_eval_step(tdx_unet* u, const void* const* params, void* 
                                   int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
                                   void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed,
                                   tdx_stream_t stream) {
-  return eval_step_impl(u, params, buffers, x, cond, z, coef, nullptr, 0, counter, t_idx, t_vec, eps, n_elems,
-                        workspace, workspace_bytes, batch, philox_seed, stream);
+  return eval_step_impl(u, params, buffers, x, cond,
+                        eval_pstep(TDX_STEP_EPS, coef, t_idx, nullptr, z, philox_seed, 0, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr),
+                        0, counter, t_idx, t_vec, eps, n_elems, workspace, workspace_bytes, batch, stream);
 }
 
-extern "C" int tdx_unet_eval_step_sched(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
-                                        const void* cond, const float* z, const float* coef, const int64_t* tau, int S,
-                                        int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
-                                        void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed,
-                                        tdx_stream_t stream) {
-  if (!tau || S <= 0) return TDX_E_BADARG;
-  return eval_step_impl(u, params, buffers, x, cond, z, coef, tau, S, counter, t_idx, t_vec, eps, n_elems, workspace,
-                        workspace_bytes, batch, philox_seed, stream);
-}
-
-// The guided step (classifier-free guidance): tdx_unet_eval_step_sched's arguments plus the scale w; tau == null is the
-// identity chain (S ignored).  batch = 2n, n_elems = the first half's elements.
-extern "C" int tdx_unet_eval_step_guided(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
+// Every other step (include/tdx.h): a schedule, guidance, the x0 and the multistep form, a known region.  The update
+// runs in final_conv's epilogue, or in pstep_kernel when the epilogue is switched off (knob "sample_fuse") and for the
+// latent MLP (u->spec == nullptr; the transformer has no plan: its host loop calls tdx_p_sample_update itself).
+extern "C" int tdx_unet_eval_step_update(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
                                          const void* cond, const float* z, const float* coef, const int64_t* tau, int S,
                                          int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
-                                         void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed, float w,
-                                         tdx_stream_t stream) {
-  if (tau && S <= 0) return TDX_E_BADARG;
-  return eval_step_impl(u, params, buffers, x, cond, z, coef, tau, tau ? S : 0, counter, t_idx, t_vec, eps, n_elems,
-                        workspace, workspace_bytes, batch, philox_seed, stream, true, w);
-}
-
-// The clipped-x0 step: tdx_unet_eval_step_guided's arguments with coef5 the (S,5) table (p, q, A, Bx, sigma) and the
-// clamp [lo, hi] of the implied x0.  guided == 0: an unguided step (w ignored, n_elems all of x's elements, every model);
-// tau == null: the identity chain.  The update runs in final_conv's epilogue, or in tdx_p_sample_step_x0{,_guided} when
-// the epilogue is switched off (knob "sample_fuse") and for the latent MLP (u->spec == nullptr; the transformer has no
-// plan: its host loop calls that kernel itself).
-extern "C" int tdx_unet_eval_step_x0(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
-                                     const void* cond, const float* z, const float* coef5, const int64_t* tau, int S,
-                                     int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
-                                     void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed,
-                                     int guided, float w, float lo, float hi, tdx_stream_t stream) {
-  if (tau && S <= 0) return TDX_E_BADARG;
-  return eval_step_impl(u, params, buffers, x, cond, z, coef5, tau, tau ? S : 0, counter, t_idx, t_vec, eps, n_elems,
-                        workspace, workspace_bytes, batch, philox_seed, stream, guided != 0, w, 1, lo, hi);
-}
-
-// The multistep step (DPM-Solver++(2M), see tdx_p_sample_step_ms): tdx_unet_eval_step_x0's arguments without the noise
-// (no z, no seed: the chain is deterministic) plus the history hist - n_elems floats that the caller keeps from step to
-// step, read only when the row's H != 0.  coef5 is the (S,5) table (p, q, A, Bx, H).  The update runs in final_conv's
-// epilogue, or in tdx_p_sample_step_ms{,_guided} when the epilogue is switched off and for the latent MLP.
-extern "C" int tdx_unet_eval_step_ms(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
-                                     const void* cond, const float* coef5, const int64_t* tau, int S, int64_t* counter,
-                                     int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems, void* workspace,
-                                     size_t workspace_bytes, int batch, int guided, float w, float lo, float hi,
-                                     float* hist, tdx_stream_t stream) {
-  if ((tau && S <= 0) || !hist) return TDX_E_BADARG;
-  return eval_step_impl(u, params, buffers, x, cond, nullptr, coef5, tau, tau ? S : 0, counter, t_idx, t_vec, eps,
-                        n_elems, workspace, workspace_bytes, batch, 0, stream, guided != 0, w, 2, lo, hi, hist);
-}
-
-// The masked steps (inpainting; see tdx_p_sample_step_x0_masked / tdx_p_sample_step_ms_masked): the arguments of
-// tdx_unet_eval_step_x0 / tdx_unet_eval_step_ms plus known / mask, n_elems floats each.  The update runs in final_conv's
-// epilogue, or in the separate masked kernels wherever the unmasked step uses the separate ones.
-extern "C" int tdx_unet_eval_step_x0_masked(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
-                                            const void* cond, const float* z, const float* coef5, const int64_t* tau,
-                                            int S, int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps,
-                                            int64_t n_elems, void* workspace, size_t workspace_bytes, int batch,
-                                            uint64_t philox_seed, int guided, float w, float lo, float hi,
-                                            const float* known, const float* mask, tdx_stream_t stream) {
-  if ((tau && S <= 0) || !known || !mask) return TDX_E_BADARG;
-  return eval_step_impl(u, params, buffers, x, cond, z, coef5, tau, tau ? S : 0, counter, t_idx, t_vec, eps, n_elems,
-                        workspace, workspace_bytes, batch, philox_seed, stream, guided != 0, w, 1, lo, hi, nullptr,
-                        known, mask);
-}
-
-extern "C" int tdx_unet_eval_step_ms_masked(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
-                                            const void* cond, const float* coef5, const int64_t* tau, int S,
-                                            int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps,
-                                            int64_t n_elems, void* workspace, size_t workspace_bytes, int batch,
-                                            int guided, float w, float lo, float hi, float* hist, const float* known,
-                                            const float* mask, tdx_stream_t stream) {
-  if ((tau && S <= 0) || !hist || !known || !mask) return TDX_E_BADARG;
-  return eval_step_impl(u, params, buffers, x, cond, nullptr, coef5, tau, tau ? S : 0, counter, t_idx, t_vec, eps,
-                        n_elems, workspace, workspace_bytes, batch, 0, stream, guided != 0, w, 2, lo, hi, hist, known,
-                        mask);
+                                         void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed,
+                                         int form, int guided, float w, float lo, float hi, float* hist,
+                                         const float* known, const float* mask, tdx_stream_t stream) {
+  const PStep ps = eval_pstep(form, coef, t_idx, tau, z, philox_seed, guided, w, lo, hi, hist, known, mask);
+  if ((tau && S <= 0) || pstep_valid(ps, n_elems)) return TDX_E_BADARG;
+  return eval_step_impl(u, params, buffers, x, cond, ps, tau ? S : 0, counter, t_idx, t_vec, eps, n_elems, workspace,
+                        workspace_bytes, batch, stream);
 }
 
 // Build the sampling tables for the CURRENT INFER pack (call after tdx_unet_pack / the first INFER forward, once

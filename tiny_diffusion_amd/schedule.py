@@ -735,55 +735,16 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
     kn, mk = (None, None) if km is None else tuple(
         v.to(device).expand(n_samples, *shape).contiguous() for v in km)
 
+    form = _lib.STEP_MS if ms else _lib.STEP_EPS if clip is None else _lib.STEP_X0
+
     def update(eps, z):
-        """x <- c1 (x - c2 eps) + sigma z, elementwise and in place; Philox noise in the kernel under a seed."""
-        xp, ep, cp, kp, n = x.data_ptr(), eps.data_ptr(), coef.data_ptr(), t_idx.data_ptr(), x.numel()
-        if kn is not None and ms:   # the multistep update from the blend x0m = (1 - mask) x0c + mask known; hist <- x0m
-            if guided:
-                check(lib.tdx_p_sample_step_ms_guided_masked(xp, ep, hist.data_ptr(), kn.data_ptr(), mk.data_ptr(), cp,
-                                                             kp, half, w, lo, hi, None, st()),
-                      "tdx_p_sample_step_ms_guided_masked")
-            else:
-                check(lib.tdx_p_sample_step_ms_masked(xp, xp, ep, hist.data_ptr(), kn.data_ptr(), mk.data_ptr(), cp, kp,
-                                                      n, lo, hi, None, st()), "tdx_p_sample_step_ms_masked")
-        elif kn is not None:   # the x0-form update from the blend
-            ph = (int(philox_seed is not None), philox_seed or 0, None, st())
-            if guided:
-                check(lib.tdx_p_sample_step_x0_guided_masked(xp, ep, z, kn.data_ptr(), mk.data_ptr(), cp,
-                                                             tau.data_ptr(), kp, half, w, lo, hi, *ph),
-                      "tdx_p_sample_step_x0_guided_masked")
-            else:
-                check(lib.tdx_p_sample_step_x0_masked(xp, xp, ep, z, kn.data_ptr(), mk.data_ptr(), cp, tau.data_ptr(),
-                                                      kp, n, lo, hi, *ph), "tdx_p_sample_step_x0_masked")
-        elif ms:   # x <- A clamp(p x + q out) + Bx x + H hist, hist <- the clamped x0
-            if guided:
-                check(lib.tdx_p_sample_step_ms_guided(xp, ep, hist.data_ptr(), cp, kp, half, w, lo, hi, None, st()),
-                      "tdx_p_sample_step_ms_guided")
-            else:
-                check(lib.tdx_p_sample_step_ms(xp, xp, ep, hist.data_ptr(), cp, kp, n, lo, hi, None, st()),
-                      "tdx_p_sample_step_ms")
-        elif clip is not None:   # x <- A clamp(p x + q out) + Bx x + sigma z: one entry for every mode
-            ph = (int(philox_seed is not None), philox_seed or 0, None, st())
-            if guided:
-                check(lib.tdx_p_sample_step_x0_guided(xp, ep, z, cp, tau.data_ptr(), kp, half, w, lo, hi, *ph),
-                      "tdx_p_sample_step_x0_guided")
-            else:
-                check(lib.tdx_p_sample_step_x0(xp, xp, ep, z, cp, tau.data_ptr(), kp, n, lo, hi, *ph),
-                      "tdx_p_sample_step_x0")
-        elif guided:   # both halves of x from the combined prediction
-            check(lib.tdx_p_sample_step_guided(xp, ep, z, cp, None if tau is None else tau.data_ptr(), kp, half, w,
-                                               int(philox_seed is not None), philox_seed or 0, None, st()),
-                  "tdx_p_sample_step_guided")
-        elif tau is None and philox_seed is not None:
-            check(lib.tdx_p_sample_step_philox(xp, xp, ep, cp, kp, n, philox_seed, st()), "tdx_p_sample_step")
-        elif tau is None:
-            check(lib.tdx_p_sample_step(xp, xp, ep, z, cp, kp, n, st()), "tdx_p_sample_step")
-        elif philox_seed is not None:
-            check(lib.tdx_p_sample_step_sched_philox(xp, xp, ep, cp, tau.data_ptr(), kp, n, philox_seed, st()),
-                  "tdx_p_sample_step_sched_philox")
-        else:
-            check(lib.tdx_p_sample_step_sched(xp, xp, ep, z, cp, tau.data_ptr(), kp, n, st()),
-                  "tdx_p_sample_step_sched")
+        """x <- step(x, eps, z | hist), elementwise and in place (tdx_p_sample_update: the table's form, guided or
+        not, masked or not); Philox noise in the kernel under a seed, none on a multistep chain."""
+        check(lib.tdx_p_sample_update(x.data_ptr(), x.data_ptr(), eps.data_ptr(), half if guided else x.numel(), form,
+                                      coef.data_ptr(), t_idx.data_ptr(), _lib.ptr(tau), None if ms else z,
+                                      int(philox_seed is not None), philox_seed or 0, int(guided), w if guided else 0.0,
+                                      lo, hi, _lib.ptr(hist), _lib.ptr(kn), _lib.ptr(mk), None, st()),
+              "tdx_p_sample_update")
 
     def step_begin(counter):
         """t_idx <- counter, t_vec <- its timestep, counter <- counter - 1, on the device."""

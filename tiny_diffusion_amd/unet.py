@@ -553,54 +553,38 @@ class NoiseModelBase(nn.Module):
     def _run_eval_step(self, x, y, coef, counter, t_idx, t_vec, eps, z=None, philox_seed: int = 0, tau=None,
                        S: int = 0, guidance_scale: Optional[float] = None, clip=None, hist=None, known=None,
                        mask=None):
-        """One reverse step of sample() in place on ``x`` (tdx_unet_eval_step): the step index is
-        read from and decremented in device memory, so the call can sit in a HIP graph.  ``tau``: the
-        device timesteps of a schedule of ``S`` steps (tdx_unet_eval_step_sched; ``coef`` is then (S,3)).
-        ``guidance_scale``: the guided step (tdx_unet_eval_step_guided) - ``x``, ``y`` and ``eps`` hold 2n rows, the
-        second half under the null condition, ``z`` n rows.  ``clip=(lo, hi)``: the clipped-x0 step
-        (tdx_unet_eval_step_x0), guided or not - ``coef`` is then the (S,5) table of ``TimestepSchedule.x0_form``.
-        ``hist`` (with ``clip``, infinite bounds for none): the multistep step (tdx_unet_eval_step_ms) against that
-        history buffer - ``coef`` is the (S,5) table of ``MultistepSchedule.multistep_form``; no ``z``, no seed.
-        ``known`` / ``mask`` (with ``clip``; both or neither): the masked step of inpainting
-        (tdx_unet_eval_step_x0_masked / tdx_unet_eval_step_ms_masked) - contiguous fp32 device tensors of n rows."""
+        """One reverse step of sample() in place on ``x``: the step index is read from and decremented in device
+        memory, so the call can sit in a HIP graph.  Nothing but ``z`` / ``philox_seed``: tdx_unet_eval_step, the
+        reference's chain with ``coef`` its (T,3) table.  Anything else: tdx_unet_eval_step_update.  ``tau``: the device
+        timesteps of a schedule of ``S`` steps.  ``guidance_scale``: the guided step - ``x``, ``y`` and ``eps`` hold 2n
+        rows, the second half under the null condition, ``z`` n rows.  ``clip=(lo, hi)`` (infinite bounds for none): the
+        x0 form, ``coef`` the (S,5) table of ``TimestepSchedule.x0_form``; with ``hist`` the multistep form against that
+        history buffer, ``coef`` the (S,5) table of ``MultistepSchedule.multistep_form`` (no ``z``, no seed).
+        ``known`` / ``mask`` (with ``clip``; both or neither): the masked step of inpainting - contiguous fp32 device
+        tensors of n rows."""
         if (known is None) != (mask is None):
             raise ValueError("known and mask go together")
+        if known is not None and clip is None:
+            raise ValueError("the masked step runs in x0 form: give clip (infinite bounds for none)")
         plan, pptr, bptr, st = self._plan_ptrs(x)
-        head = (plan.handle, pptr, bptr, x.data_ptr(), _dptr(y), _dptr(z), coef.data_ptr())
-        rest = (counter.data_ptr(), t_idx.data_ptr(), t_vec.data_ptr(), eps.data_ptr(), x.numel(),
-                plan.workspace.data_ptr(), plan.ws_bytes, x.shape[0], philox_seed, st)
-        if known is not None:
-            if clip is None:
-                raise ValueError("the masked step runs in x0 form: give clip (infinite bounds for none)")
-            g = guidance_scale is not None
-            gargs = (int(g), float(guidance_scale) if g else 0.0, float(clip[0]), float(clip[1]))
-            nel = x.numel() // 2 if g else x.numel()
-            if hist is not None:
-                check(lib.tdx_unet_eval_step_ms_masked(*head[:5], coef.data_ptr(), _dptr(tau), int(S), *rest[:4], nel,
-                                                       *rest[5:8], *gargs, hist.data_ptr(), known.data_ptr(),
-                                                       mask.data_ptr(), st), "tdx_unet_eval_step_ms_masked")
-            else:
-                check(lib.tdx_unet_eval_step_x0_masked(*head, _dptr(tau), int(S), *rest[:4], nel, *rest[5:-1], *gargs,
-                                                       known.data_ptr(), mask.data_ptr(), st),
-                      "tdx_unet_eval_step_x0_masked")
-        elif hist is not None:
-            g = guidance_scale is not None
-            check(lib.tdx_unet_eval_step_ms(*head[:5], coef.data_ptr(), _dptr(tau), int(S), *rest[:4],
-                                            x.numel() // 2 if g else x.numel(), *rest[5:8], int(g),
-                                            float(guidance_scale) if g else 0.0, float(clip[0]), float(clip[1]),
-                                            hist.data_ptr(), st), "tdx_unet_eval_step_ms")
-        elif clip is not None:
-            g = guidance_scale is not None
-            rest = rest[:4] + (x.numel() // 2 if g else x.numel(),) + rest[5:-1] \
-                + (int(g), float(guidance_scale) if g else 0.0, float(clip[0]), float(clip[1]), st)
-            check(lib.tdx_unet_eval_step_x0(*head, _dptr(tau), int(S), *rest), "tdx_unet_eval_step_x0")
-        elif guidance_scale is not None:
-            rest = rest[:4] + (x.numel() // 2,) + rest[5:-1] + (float(guidance_scale), st)
-            check(lib.tdx_unet_eval_step_guided(*head, _dptr(tau), int(S), *rest), "tdx_unet_eval_step_guided")
-        elif tau is None:
-            check(lib.tdx_unet_eval_step(*head, *rest), "tdx_unet_eval_step")
+        g = guidance_scale is not None
+        form = _lib.STEP_MS if hist is not None else _lib.STEP_EPS if clip is None else _lib.STEP_X0
+        lo, hi = (0.0, 0.0) if clip is None else (float(clip[0]), float(clip[1]))
+        if form == _lib.STEP_MS:
+            z, philox_seed = None, 0
+        if form == _lib.STEP_EPS and not g and tau is None:
+            check(lib.tdx_unet_eval_step(plan.handle, pptr, bptr, x.data_ptr(), _dptr(y), _dptr(z), coef.data_ptr(),
+                                         counter.data_ptr(), t_idx.data_ptr(), t_vec.data_ptr(), eps.data_ptr(),
+                                         x.numel(), plan.workspace.data_ptr(), plan.ws_bytes, x.shape[0], philox_seed,
+                                         st), "tdx_unet_eval_step")
         else:
-            check(lib.tdx_unet_eval_step_sched(*head, tau.data_ptr(), int(S), *rest), "tdx_unet_eval_step_sched")
+            check(lib.tdx_unet_eval_step_update(plan.handle, pptr, bptr, x.data_ptr(), _dptr(y), _dptr(z),
+                                                coef.data_ptr(), _dptr(tau), int(S), counter.data_ptr(),
+                                                t_idx.data_ptr(), t_vec.data_ptr(), eps.data_ptr(),
+                                                x.numel() // 2 if g else x.numel(), plan.workspace.data_ptr(),
+                                                plan.ws_bytes, x.shape[0], philox_seed, form, int(g),
+                                                float(guidance_scale) if g else 0.0, lo, hi, _dptr(hist), _dptr(known),
+                                                _dptr(mask), st), "tdx_unet_eval_step_update")
 
     def _drop_sampling_tables(self, x):
         """The eval steps on ``x`` that follow take the direct time path (tdx_unet_drop_sampling_tables): bit for bit
