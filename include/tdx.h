@@ -296,7 +296,10 @@ int tdx_pack_conv3x3(const float* w_oihw, float* w_fwd, float* w_dgrad, int cout
  *   final_conv    in (B,H,W,64) channels-last, w (cout,64,3,3), bias (cout) -> out (B,cout,H,W) NCHW; cout = 1 | 4.
  * backward: g_out in the forward output's layout; dw / db in the parameter's layout; the input gradient of
  * final_conv (g_in, channels-last) - initial_conv's input is the data, it has none.  scratch:
- * tdx_edge_conv_wgrad_scratch_floats(B,H,W) floats (consumed).  W >= 4.  Other shapes: TDX_E_SHAPE. */
+ * tdx_edge_conv_wgrad_scratch_floats(B,H,W) floats (consumed).  H and W are independent (any H >= 1).  The two backward
+ * entries need W >= 4 (their kernel walks the pixels in pairs) and return TDX_E_SHAPE for a narrower map before anything
+ * is written, g_in included; the forwards and tdx_initial_conv_input_grad take any W >= 1.  Other channel counts:
+ * TDX_E_SHAPE. */
 size_t tdx_edge_conv_wgrad_scratch_floats(int B, int H, int W);
 int tdx_initial_conv_forward(const float* x, const float* w, const float* bias, float* out, int B, int H, int W,
                              int cin, int cout, tdx_stream_t stream);
@@ -316,7 +319,8 @@ int tdx_final_conv_backward(const float* in, const float* g_out, const float* w,
  * (nn.Conv2d(cin,cout,3,padding=1), diffusion.py:28-98), NHWC.
  *   in  (B,H,W,cin)  wpk [cout][9][cin]  bias (cout) or NULL  out (B,H,W,cout)
  * With the dgrad pack and the roles of cin/cout swapped the same entry point
- * computes the input gradient.  cin % 32 == 0, cout % 64 == 0.
+ * computes the input gradient.  cin % 32 == 0, cout % 64 == 0; any H, W >= 1, independent of each other (so for
+ * every direct forward below: _splitk, _train, _infer, tdx_conv3x3_dgrad).
  * stats_partial (when TDX_CONV_OUT_STATS): [tdx_conv3x3_stat_tiles(...)][2][cout] holding,
  * per tile of tdx_conv3x3_stat_tile_rows(...) output pixels and per channel, the sum
  * and the sum of squared deviations from the TILE mean (merged by tdx_bn_finalize). */
@@ -415,7 +419,8 @@ int tdx_conv3x3_dgrad(const float* dy, const float* w_dgrad, float* dx, int B, i
 /* Weight gradient of the same convolution:
  *   dw_slabs[s][cout][9][cin] partial sums over pixel chunk s (split-K, deterministic)
  * followed by tdx_conv3x3_wgrad_reduce -> OIHW gradient.  `in` may be a pre-BN
- * tensor (TDX_CONV_IN_BNRELU with in_scale/in_shift). */
+ * tensor (TDX_CONV_IN_BNRELU with in_scale/in_shift).  cin % 64 == 0, cout % 64 == 0; any H, W >= 1, independent of
+ * each other (narrow and one-row maps included). */
 int tdx_conv3x3_wgrad_splits(int B, int H, int W, int cin, int cout);
 int tdx_conv3x3_wgrad(const float* in, const float* dy, float* dw_slabs,
                       int B, int H, int W, int cin, int cout, int flags,

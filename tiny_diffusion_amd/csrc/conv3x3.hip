@@ -1655,13 +1655,16 @@ conv3x3_wgrad_kernel(WgradArgs a) {
   // the ragged end of the pixel range is zero-filled by the hardware range check with no
   // instruction at all; the input descriptor starts (W+1) pixels before the tensor so that the
   // tap shift is a non-negative scalar, and a row whose tap falls outside the image gets an
-  // out-of-range offset.  (A dy row of zeros also cancels whatever the matching input row holds.)
+  // out-of-range offset.
   constexpr unsigned OOB = 0x80000000u;
   const int neg = (a.W + 1) * a.Cin;
   const auto rsrc_dy = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dy), 0,
                                                          (int)((int64_t)p_hi * a.Cout * 4), 0x00020000);
+  // (... and ENDS with the tensor: a valid tap of a pixel < M reads a pixel < M, so nothing legitimate lies behind it, and
+  // the rows past M of a ragged last tile - whose taps are judged on (oh, ow) alone - are refused by the range check
+  // instead of being read from whatever follows the tensor)
   const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.in) - neg, 0, (int)(((int64_t)a.M * a.Cin + 2 * neg) * 4), 0x00020000);
+      const_cast<float*>(a.in) - neg, 0, (int)(((int64_t)a.M * a.Cin + neg) * 4), 0x00020000);
   unsigned a_off[AI], b_off[BI];
 #pragma unroll
   for (int i = 0; i < AI; ++i) a_off[i] = (unsigned)((a_r0 + AROWS * i) * a.Cout + co0 + a_c4) * 4u;
@@ -1839,8 +1842,11 @@ conv3x3_wgrad_dma_kernel(WgradArgs a) {
   const int neg = (a.W + 1) * a.Cin;
   const auto rsrc_dy = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dy), 0,
                                                          (int)((int64_t)p_hi * a.Cout * 4), 0x00020000);
+  // (... and ENDS with the tensor: a valid tap of a pixel < M reads a pixel < M, so nothing legitimate lies behind it, and
+  // the rows past M of a ragged last tile - whose taps are judged on (oh, ow) alone - are refused by the range check
+  // instead of being read from whatever follows the tensor)
   const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.in) - neg, 0, (int)(((int64_t)a.M * a.Cin + 2 * neg) * 4), 0x00020000);
+      const_cast<float*>(a.in) - neg, 0, (int)(((int64_t)a.M * a.Cin + neg) * 4), 0x00020000);
   unsigned a_off[AI], b_off[BI];
 #pragma unroll
   for (int i = 0; i < AI; ++i) a_off[i] = (unsigned)((a_r0 + AROWS * i) * a.Cout + co0 + a_c4) * 4u;
@@ -2036,8 +2042,11 @@ extern "C" int tdx_conv3x3_wgrad(const float* in, const float* dy, float* dw_sla
   a.B = B; a.H = H; a.W = W; a.Cin = cin; a.Cout = cout; a.M = (int)M64;
   a.tilesCi = cin / c.bn; a.tilesCo = cout / c.bm; a.chunk = c.chunk;
   a.groups = a.tilesCi * a.tilesCo * c.splits;
-  a.adv_q = 32 / W; a.adv_s = 32 % W; a.dbg = 0;
-  if (H < 4 && 32 / W + 1 >= 2 * H) return TDX_E_SHAPE;  // two conditional subtracts must suffice
+  // 32 pixels further = 32 / W rows and 32 % W columns; only the row modulo H matters (the kernels test the tap's
+  // row against the image, nothing else), so the rows are reduced here: oh + adv_q + carry <= 2 H - 1 and the kernels'
+  // conditional subtracts suffice for every H x W.  (Unreduced, 32 / W >= 3 H - narrow, short maps such as 4 x 2 or
+  // 8 x 1 - left oh >= H and dropped valid taps; maps with H < 4 and W < 32 / (2 H - 1) were refused.)
+  a.adv_q = (32 / W) % H; a.adv_s = 32 % W; a.dbg = 0;
   hipStream_t st = to_stream(stream);
   if (c.bm == 128 && c.bn == 128) return launch_wgrad<128, 128>(a, c.splits, in_bn, st);
   if (c.bm == 128 && c.bn == 64) return launch_wgrad<128, 64>(a, c.splits, in_bn, st);

@@ -625,6 +625,7 @@ extern "C" int tdx_final_conv_backward(const float* in, const float* g_out, cons
                                        float* db, float* scratch, int B, int H, int W, int cout,
                                        tdx_stream_t stream) {
   if (!in || !g_out || !w || !g_in || !dw || !db || !scratch || B <= 0 || H <= 0 || W <= 0) return TDX_E_BADARG;
+  if (W < 4 || (cout != 1 && cout != 4)) return TDX_E_SHAPE;   // (before the input gradient: a refused call writes nothing)
   const int rc = tdx_final_conv_dgrad(g_out, w, g_in, B, H, W, cout, to_stream(stream));
   if (rc) return rc;
   return tdx_final_conv_wgrad(in, g_out, scratch, dw, db, B, H, W, cout, to_stream(stream));
