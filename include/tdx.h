@@ -627,6 +627,44 @@ int tdx_embedding_fwd(const float* weight, const int64_t* idx, float* out, int M
 int tdx_embedding_bwd(const float* g, const int64_t* idx, float* dweight, int M, int N, int num,
                       tdx_stream_t stream);
 
+/* ---- training of the "transformer" noise model: forward, loss and backward of
+ * diffusion_transformer.py:82-107 + F.mse_loss in one call (transformer.hip).
+ * Limits (those of the row kernels above): dim % 64 == 0, dim <= 1024, dim % num_heads == 0; anything else, or a
+ * size <= 0, a dropout_p outside [0, 1) or an ln_eps <= 0: TDX_E_SHAPE, and the workspace size is 0. */
+typedef struct tdx_transformer_shape {
+  int batch, latent_dim, dim, num_heads, num_layers, num_classes;
+  float dropout_p, ln_eps;
+} tdx_transformer_shape;
+size_t tdx_transformer_train_workspace_floats(const tdx_transformer_shape* shape);
+/* params / grads: 12 + 12 * num_layers device pointers in the module's state_dict() order:
+ *    0 pos_encoding (dim)                 1 time_embedding.0.weight (dim,1)    2 time_embedding.0.bias
+ *    3 time_embedding.2.weight (dim,dim)  4 time_embedding.2.bias              5 class_embedding.weight (classes,dim)
+ *    6 input_proj.weight (dim,latent)     7 input_proj.bias
+ *    8 + 12 l + {0 attention.in_proj_weight (3 dim,dim), 1 attention.in_proj_bias (3 dim), 2 attention.out_proj.weight,
+ *                3 attention.out_proj.bias, 4 norm1.weight, 5 norm1.bias, 6 ff.0.weight (4 dim,dim), 7 ff.0.bias,
+ *                8 ff.2.weight (dim,4 dim), 9 ff.2.bias, 10 norm2.weight, 11 norm2.bias}     for block l
+ *    8 + 12 L + {0 final_layer.0.weight, 1 final_layer.0.bias, 2 final_layer.1.weight (latent,dim), 3 final_layer.1.bias}
+ * Every gradient is WRITTEN, not accumulated: the Q and K thirds of in_proj_weight / in_proj_bias (the softmax over
+ * the single key of a length-1 sequence is constant) and the class_embedding rows of labels absent from y are exact
+ * zeros.  grads == NULL: forward and loss only.
+ * z_t (B,latent), t, y (B,) int64 (neither is range-checked: 0 <= y < num_classes is the caller's contract, as for
+ * tdx_embedding_fwd), target (B,latent).  loss_out[0] = mean((eps_hat - target)^2), or with w_table (T,) the weighted
+ * loss of tdx_mse_loss_grad_weighted (same passes, same fixed summation order); the gradients are those of
+ * gscale * loss_out[0].  eps_hat_out (B,latent) may be NULL.
+ * Dropout: train != 0 and dropout_p > 0 turn on the four sites of every block - the head weight (one draw per
+ * (row, head)), the attention output, ff's own dropout, the block's dropout.  Site k = 1 .. 4 L in forward order draws
+ * from Philox stream offset + k under key seed with tdx_dropout's element -> draw map (group = dim / num_heads at the
+ * head site, 1 elsewhere), so offset = 0 gives the masks of the module's own train-mode forward under that seed.  The
+ * backward regenerates the masks; none is stored.  rng_dev: NULL, or two device uint64 {seed, offset} that the kernels
+ * read INSTEAD of the two by-value arguments (a captured step then draws fresh masks at every replay).
+ * workspace: tdx_transformer_train_workspace_floats() floats, 16-byte aligned (TDX_E_BADARG otherwise).  One stream,
+ * no allocation, no host synchronisation: capturable. */
+int tdx_transformer_loss_grads(const tdx_transformer_shape* shape, const void* const* params, void* const* grads,
+                               const float* z_t, const int64_t* t, const int64_t* y, const float* target,
+                               const float* w_table, int train, uint64_t seed, uint64_t offset,
+                               const uint64_t* rng_dev, float gscale, float* loss_out, float* eps_hat_out,
+                               float* workspace, tdx_stream_t stream);
+
 typedef struct tdx_unet tdx_unet;
 
 /* num_classes == 0: unconditional (diffusion.py); > 0: class-conditional. */

@@ -163,6 +163,8 @@ _SIGS = {
     "tdx_add": (C.c_int, [_ptr, _ptr, _ptr, C.c_int64, C.c_int64, _ptr]),
     "tdx_embedding_fwd": (C.c_int, [_ptr, _ptr, _ptr, C.c_int, C.c_int, _ptr]),
     "tdx_embedding_bwd": (C.c_int, [_ptr, _ptr, _ptr, C.c_int, C.c_int, C.c_int, _ptr]),
+    "tdx_transformer_train_workspace_floats": (C.c_size_t, [_ptr]),
+    "tdx_transformer_loss_grads": (C.c_int, [_ptr] * 8 + [C.c_int, C.c_uint64, C.c_uint64, _ptr, C.c_float] + [_ptr] * 4),
     "tdx_unet_create": (C.c_int, [C.POINTER(_ptr), C.c_int, C.c_int]),
     "tdx_unet_create_ex": (C.c_int, [C.POINTER(_ptr), C.c_int, C.c_int, C.c_int]),
     "tdx_unet_create_hw": (C.c_int, [C.POINTER(_ptr), C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -12,14 +12,23 @@ the reference's names (``nn.MultiheadAttention.in_proj_weight`` etc.) and give t
 default initialisation; their torch ``forward`` is never called."""
 from __future__ import annotations
 
+import contextlib
+import ctypes as C
+import math
+from typing import Optional, Tuple
+
 import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .schedule import ForwardProcess, ddim_sample_loop, dpm_sample_loop, sample_loop
-from .vae import VAE, VAEConfig
+from ._lib import check, lib
+from .schedule import (ForwardProcess, _prediction, _snr_gamma, ddim_sample_loop, dpm_sample_loop, loss_weights,
+                       sample_loop)
+from .train import cosine_annealing_lr, ema_decay_at
+from .vae import VAE, VAEConfig, _f32, _number
 
-__all__ = ["TransformerBlock", "NoiseModel", "ForwardProcess", "sample", "ddim_sample", "dpm_sample", "VAE", "VAEConfig"]
+__all__ = ["TransformerBlock", "NoiseModel", "ForwardProcess", "sample", "ddim_sample", "dpm_sample", "VAE", "VAEConfig",
+           "TransformerTrainStep", "cosine_annealing_lr", "ema_decay_at"]
 
 
 class TransformerBlock(nn.Module):
@@ -159,3 +168,430 @@ def _check_labels(y, n_samples):
         raise ValueError("Class labels 'y' must be provided for conditional generation.")
     if y.shape[0] != n_samples:
         raise ValueError("y must have shape (n_samples,)")
+
+
+class _TShape(C.Structure):
+    """``tdx_transformer_shape`` (include/tdx.h)."""
+    _fields_ = [("batch", C.c_int), ("latent_dim", C.c_int), ("dim", C.c_int), ("num_heads", C.c_int),
+                ("num_layers", C.c_int), ("num_classes", C.c_int), ("dropout_p", C.c_float), ("ln_eps", C.c_float)]
+
+
+def _seed_arg(v, what):
+    if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 64):
+        raise ValueError(f"{what} must be None or an integer in [0, 2**64)")
+    return v
+
+
+def _i64(v: int) -> int:
+    """A uint64 as the int64 with the same bits (torch has no uint64 arithmetic; the kernels read the words as uint64)."""
+    return v - 2 ** 64 if v >= 2 ** 63 else v
+
+
+class TransformerTrainStep:
+    """The optimisation step of the transformer's training loop (diffusion_transformer.py:193-202: ``randint``,
+    ``q_sample``, forward, ``F.mse_loss``, ``zero_grad``, ``backward``, ``optimizer.step``) as one short chain of libtdx
+    launches with no autograd graph:
+
+        step = TransformerTrainStep(model, diffusion, lr=3e-4)
+        for epoch in range(num_epochs):
+            step.lr = cosine_annealing_lr(epoch, 3e-4, num_epochs)     # CosineAnnealingLR(T_max=num_epochs), per epoch
+            for z_0, labels in loader:
+                loss = step.step(z_0, labels)                          # device tensor, not synchronised
+            model.eval(); val = step.evaluate(z_0, labels); model.train()
+
+    ``tdx_transformer_loss_grads`` runs forward, loss and backward (csrc/transformer.hip); the parameters become views
+    of one flat fp32 buffer in ``state_dict()`` order with the gradient, Adam's two moments and the optional average
+    beside it, so the optimizer is one ``tdx_adam_step*`` / ``tdx_adam_ema_step*`` launch (``max_grad_norm``:
+    ``clip_grad_norm_`` fused into it).  ``state_dict()`` / ``load_state_dict()`` of the module keep working (in-place
+    copies land in the flat buffer); moving the module afterwards (``.to``, ``.cpu``) detaches it and the next call raises.
+
+    ``prediction`` / ``loss_weighting`` / ``snr_gamma`` / ``set_objective`` and ``ema_decay`` / ``ema_warmup`` /
+    ``ema_weights()`` / ``ema_state_dict()`` / ``load_ema_state_dict()`` / ``reset_ema()`` behave as in
+    ``train.TrainStep``.  ``lr`` is a plain attribute read at every step (a captured step reads it through its device
+    scalars).
+
+    Noise: ``noise`` given - used; else with ``philox_seed`` drawn in the q_sample kernel, keyed by ``(philox_seed,
+    step_count)``; else ``torch.randn_like``.  ``t=None`` draws ``torch.randint`` on the device as the reference does.
+
+    Dropout follows ``model.training``, with the blocks' ``p``; the masks are Philox draws, regenerated in the backward.
+    ``dropout_seed=None``: one key per step from torch's CPU generator, drawn exactly as the module's own forward
+    draws it, with offset 0 - ``torch.manual_seed`` reproduces a step, and with ``t`` and ``noise`` passed the step uses
+    the very masks of ``model(z_t, t, y)`` under the same seed.  ``dropout_seed=int``: that key with offset
+    ``step_count * 4 * num_layers``.  ``last_dropout_seed`` / ``last_dropout_offset`` hold what the last step used.
+
+    ``use_graph=True``: the first step with a batch size runs eagerly, the second is captured into a HIP graph, later
+    ones replay it; inputs, Adam's step-dependent scalars and the dropout ``{seed, offset}`` live in static device
+    buffers refreshed before each replay.  With ``philox_seed`` the step stays eager.
+
+    This model has no null class, so there is no ``cond_drop_prob`` (classifier-free guidance needs a model with one).
+    Not covered: data parallelism, the bf16 mode (fp32 only)."""
+
+    def __init__(self, model: "NoiseModel", diffusion: ForwardProcess, lr: float = 3e-4,
+                 betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, max_grad_norm: Optional[float] = None,
+                 prediction: str = "eps", loss_weighting=None, snr_gamma: float = 5.0,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False, philox_seed: Optional[int] = None,
+                 dropout_seed: Optional[int] = None, use_graph: bool = False):
+        if not isinstance(model, NoiseModel):
+            raise ValueError("TransformerTrainStep needs a diffusion_transformer.NoiseModel")
+        if not isinstance(diffusion, ForwardProcess):
+            raise ValueError("diffusion must be a ForwardProcess")
+        self.lr = _number(lr, "lr")
+        if not isinstance(betas, (tuple, list)) or len(betas) != 2:
+            raise ValueError("betas must be a pair of numbers")
+        self.betas = (_number(betas[0], "betas[0]"), _number(betas[1], "betas[1]"))
+        if not (0.0 <= self.betas[0] < 1.0 and 0.0 <= self.betas[1] < 1.0):
+            raise ValueError("betas must lie in [0, 1)")
+        self.eps = _number(eps, "eps")
+        if max_grad_norm is not None and not _number(max_grad_norm, "max_grad_norm") > 0:
+            raise ValueError("max_grad_norm must be None or > 0")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.model, self.diffusion = model, diffusion
+        self._w_table = None
+        self._check_objective(prediction, loss_weighting, snr_gamma)
+        if ema_decay is None:
+            if ema_warmup:
+                raise ValueError("ema_warmup=True needs an ema_decay")
+        elif isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 <= ema_decay <= 1.0:
+            raise ValueError("ema_decay must be None or a number in [0, 1]")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.philox_seed = _seed_arg(philox_seed, "philox_seed")
+        self.dropout_seed = _seed_arg(dropout_seed, "dropout_seed")
+        blocks = list(model.transformer_blocks)
+        if not blocks:
+            raise ValueError("the model has no transformer block")
+        ps = {b.p for b in blocks}
+        epss = {float(b.norm1.eps) for b in blocks} | {float(b.norm2.eps) for b in blocks} | {float(model.final_layer[0].eps)}
+        heads = {b.num_heads for b in blocks}
+        if len(ps) != 1 or len(epss) != 1 or len(heads) != 1:
+            raise ValueError("the fused step needs one dropout p, one LayerNorm eps and one head count for every block")
+        self.p = float(ps.pop())
+        if not 0.0 <= self.p < 1.0:
+            raise ValueError("dropout must lie in [0, 1)")
+        self.num_layers, self.num_heads = len(blocks), int(heads.pop())
+        self.num_classes = int(model.class_embedding.num_embeddings)
+        self._ln_eps = epss.pop()
+        self.use_graph = bool(use_graph)
+        self.step_count = 0
+        self.ema = None
+        self._ema_swapped = False
+        self.last_dropout_seed = self.last_dropout_offset = None
+        # ---- device work from here on
+        self._flatten()
+        dev = self.device
+        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._ws = {}            # batch size -> workspace of tdx_transformer_loss_grads
+        self._clip_scratch = None
+        self._graph = self._graph_key = self._hyper = self._grng = None
+        self._gz = self._gy = self._gt = self._gnoise = None
+        self._gws = None         # the workspace whose address the captured graph holds: owned by the graph's owner
+
+    # ------------------------------------------------------------------ setup
+    def _params(self):
+        named = dict(self.model.named_parameters())
+        return [(k, named[k]) for k in self.model.state_dict().keys()]
+
+    def _flatten(self):
+        named = self._params()
+        if len(named) != 12 + 12 * self.num_layers:
+            raise ValueError("unexpected parameter list: the fused step knows NoiseModel's 12 + 12 L tensors")
+        dev = named[0][1].device
+        for k, p in named:
+            if p.device.type != "cuda" or p.device != dev or p.dtype != torch.float32:
+                raise _lib.TdxError("TransformerTrainStep needs the model's fp32 parameters on one CUDA (ROCm) device "
+                                    f"(call .to('cuda') first): {k} is {p.dtype} on {p.device}")
+        self.device = dev
+        total = sum(p.numel() for _, p in named)
+        flat = torch.empty(total, dtype=torch.float32, device=dev)
+        self.flat_grad = torch.zeros_like(flat)
+        self.offsets, self.grad_views = {}, {}
+        o = 0
+        for k, p in named:
+            n = p.numel()
+            flat[o:o + n].copy_(p.detach().reshape(-1))
+            p.data = flat[o:o + n].view(p.shape)      # parameters become views of the flat buffer
+            self.grad_views[k] = self.flat_grad[o:o + n].view(p.shape)
+            self.offsets[k] = (o, o + n)
+            o += n
+        self.flat_param = flat
+        self.exp_avg = torch.zeros_like(flat)
+        self.exp_avg_sq = torch.zeros_like(flat)
+        if self.ema_decay is not None:
+            self.ema = flat.clone()
+        base, gbase = flat.data_ptr(), self.flat_grad.data_ptr()
+        n = len(named)
+        self._p_ptrs = (C.c_void_p * n)(*[base + 4 * self.offsets[k][0] for k, _ in named])
+        self._g_ptrs = (C.c_void_p * n)(*[gbase + 4 * self.offsets[k][0] for k, _ in named])
+        self._upload_weights()
+
+    def _check_attached(self):
+        for (k, p), want in zip(self._params(), self._p_ptrs):
+            if p.data_ptr() != want:
+                raise _lib.TdxError(f"{k} no longer lives in TransformerTrainStep's flat parameter buffer: the module was "
+                                    "moved or its parameters were replaced after the step was built (build a new one)")
+
+    # -------------------------------------------------------------- objective
+    def _check_objective(self, prediction, loss_weighting, snr_gamma):
+        prediction, gamma = _prediction(prediction), _snr_gamma(snr_gamma)
+        w_cpu = None if loss_weighting is None else loss_weights(self.diffusion, prediction, loss_weighting, gamma)
+        named = loss_weighting is None or isinstance(loss_weighting, str)
+        self.prediction, self.snr_gamma = prediction, gamma
+        self.loss_weighting = loss_weighting if named else "table"
+        self._w_cpu = None if named else w_cpu
+
+    def _upload_weights(self):
+        if self.loss_weighting is None:
+            self._w_table = None
+        elif self._w_cpu is not None:
+            self._w_table = self._w_cpu.to(self.device)
+        else:
+            self._w_table = self.diffusion.loss_weight_table(self.device, self.prediction, self.loss_weighting,
+                                                             self.snr_gamma)
+
+    def set_objective(self, prediction: str = "eps", loss_weighting=None, snr_gamma: float = 5.0):
+        """Change the training objective of an existing step (the constructor's three keywords, same errors): parameters
+        and optimizer state stay; a captured step is dropped and captured again on the next calls."""
+        self._check_objective(prediction, loss_weighting, snr_gamma)
+        self._upload_weights()
+        self._graph = self._graph_key = self._gws = None
+
+    # ------------------------------------------------------------- validation
+    def _check_batch(self, z_0, y, t, noise):
+        """Shapes first (``ValueError``), then the device (``TdxError``); returns tensors ready for the kernels."""
+        Ld = self.model.latent_dim
+        if not isinstance(z_0, torch.Tensor) or z_0.dim() != 2 or z_0.shape[0] < 1 or z_0.shape[1] != Ld:
+            raise ValueError(f"z_0 must be (B,{Ld})")
+        B = z_0.shape[0]
+        if not isinstance(y, torch.Tensor) or tuple(y.shape) != (B,) or y.dtype.is_floating_point:
+            raise ValueError("y must be an integer tensor of shape (B,)")
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (B,) or t.dtype.is_floating_point):
+            raise ValueError("t must be an integer tensor of shape (B,)")
+        if noise is not None and (not isinstance(noise, torch.Tensor) or tuple(noise.shape) != (B, Ld)):
+            raise ValueError(f"noise must be ({B},{Ld})")
+        for name, v in (("z_0", z_0), ("y", y), ("t", t), ("noise", noise)):
+            if v is not None and (not v.is_cuda or v.device != self.device):
+                raise _lib.TdxError(f"tiny_diffusion_amd runs on MI355X only: {name} is on {v.device}, the step on "
+                                    f"{self.device} (there is no CPU fallback)")
+        z_0 = z_0.contiguous().float()
+        y = y.contiguous().to(torch.int64)
+        t = None if t is None else t.contiguous().to(torch.int64)
+        noise = None if noise is None else noise.contiguous().float()
+        return B, z_0, y, t, noise
+
+    # ------------------------------------------------------------------- step
+    def _shape(self, B):
+        m = self.model
+        return _TShape(B, m.latent_dim, m.time_dim, self.num_heads, self.num_layers, self.num_classes, self.p, self._ln_eps)
+
+    def _workspace(self, B):
+        ws = self._ws.get(B)
+        if ws is None:
+            n = lib.tdx_transformer_train_workspace_floats(C.byref(self._shape(B)))
+            if n == 0:
+                raise _lib.TdxError("tdx_transformer_train_workspace_floats: shape not covered (dim % 64, dim <= 1024, "
+                                    "dim % num_heads)")
+            if len(self._ws) >= 4:   # small cache; the workspace a captured graph replays into is never evicted
+                self._ws = {k: v for k, v in self._ws.items() if v is self._gws}
+            ws = self._ws[B] = torch.empty(n, dtype=torch.float32, device=self.device)
+        return ws
+
+    def _next_rng(self):
+        """(seed, offset) of the dropout masks of the step about to run (see the class docstring)."""
+        if self.dropout_seed is not None:
+            return self.dropout_seed, self.step_count * 4 * self.num_layers
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.model.training else 0   # NoiseModel._rng_factory
+        return seed, 0
+
+    def _q_sample(self, z_0, t, noise):
+        """(z_t, target) from the existing forward-process entries."""
+        fp, dev = self.diffusion, self.device
+        if self.prediction != "eps":
+            if noise is None and self.philox_seed is not None:
+                return fp.q_sample_target_philox(z_0, t, self.philox_seed, self.step_count, self.prediction)
+            return fp.q_sample_target(dev, z_0, t, noise=noise, prediction=self.prediction)
+        if noise is None and self.philox_seed is not None:
+            return fp.q_sample_philox(z_0, t, self.philox_seed, self.step_count)
+        return fp.q_sample(dev, z_0, t, noise=noise)
+
+    def _loss_grads(self, z_t, t, y, target, B, loss, grads: bool, train: bool, rng, rng_dev=None, eps_hat=None):
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        check(lib.tdx_transformer_loss_grads(C.byref(self._shape(B)), self._p_ptrs, self._g_ptrs if grads else None,
+                                             z_t.data_ptr(), t.data_ptr(), y.data_ptr(), target.data_ptr(),
+                                             None if self._w_table is None else self._w_table.data_ptr(),
+                                             1 if train else 0, rng[0], rng[1],
+                                             None if rng_dev is None else rng_dev.data_ptr(), 1.0, loss.data_ptr(),
+                                             None if eps_hat is None else eps_hat.data_ptr(),
+                                             self._workspace(B).data_ptr(), st), "tdx_transformer_loss_grads")
+
+    def _ema_a(self) -> float:
+        return 1.0 - ema_decay_at(self.step_count - 1, self.ema_decay, self.ema_warmup)
+
+    def _adam_hyper(self):
+        """{lr / bc1, 1 / sqrt(bc2), grad_scale[, 1 - decay]} of the step ``step_count`` counts, with tdx_adam_step's
+        own arithmetic (fp32 arguments widened to double), so a captured step and an eager one update bit-identically."""
+        b1, b2 = _f32(self.betas[0]), _f32(self.betas[1])
+        bc1, bc2 = 1.0 - math.pow(b1, self.step_count), 1.0 - math.pow(b2, self.step_count)
+        hyper = [_f32(self.lr) / bc1, 1.0 / math.sqrt(bc2), 1.0]
+        return hyper if self.ema is None else hyper + [self._ema_a()]
+
+    def _adam(self, hyper=None):
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        bufs = [self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr()]
+        n = self.flat_param.numel()
+        b1, b2 = self.betas
+        hyp = None if hyper is None else hyper.data_ptr()
+        if self.ema is not None:
+            bufs.append(self.ema.data_ptr())
+        if self.max_grad_norm is not None:
+            if self._clip_scratch is None:
+                self._clip_scratch = torch.empty(lib.tdx_adam_clip_scratch_bytes(), dtype=torch.uint8, device=self.device)
+            if self.ema is not None:
+                check(lib.tdx_adam_ema_step_clip(*bufs, n, self.lr, b1, b2, self.eps, self.step_count, 1.0,
+                                                 self.max_grad_norm, self._ema_a(), hyp, self._clip_scratch.data_ptr(), st),
+                      "tdx_adam_ema_step_clip")
+            else:
+                check(lib.tdx_adam_step_clip(*bufs, n, self.lr, b1, b2, self.eps, self.step_count, 1.0,
+                                             self.max_grad_norm, hyp, self._clip_scratch.data_ptr(), st),
+                      "tdx_adam_step_clip")
+        elif hyper is not None:
+            if self.ema is not None:
+                check(lib.tdx_adam_ema_step_dev(*bufs, n, hyp, b1, b2, self.eps, st), "tdx_adam_ema_step_dev")
+            else:
+                check(lib.tdx_adam_step_dev(*bufs, n, hyp, b1, b2, self.eps, st), "tdx_adam_step_dev")
+        elif self.ema is not None:
+            check(lib.tdx_adam_ema_step(*bufs, n, self.lr, b1, b2, self.eps, self.step_count, 1.0, self._ema_a(), st),
+                  "tdx_adam_ema_step")
+        else:
+            check(lib.tdx_adam_step(*bufs, n, self.lr, b1, b2, self.eps, self.step_count, 1.0, st), "tdx_adam_step")
+
+    def _eager_step(self, z_0, y, t, noise, B, rng, hyper=None, rng_dev=None):
+        if t is None:
+            t = torch.randint(0, self.diffusion.num_timesteps, (B,), device=self.device)   # line 193
+        z_t, target = self._q_sample(z_0, t, noise)                                          # line 196
+        self._loss_grads(z_t, t, y, target, B, self.loss, True, self.model.training, rng, rng_dev)   # lines 197-201
+        self.last_dropout_seed, self.last_dropout_offset = rng
+        self.step_count += 1
+        self._adam(hyper)                                                                    # line 202
+        return self.loss
+
+    def step(self, z_0: torch.Tensor, y: torch.Tensor, t: Optional[torch.Tensor] = None,
+             noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One optimisation step on latents ``z_0`` (B, latent_dim) with labels ``y`` (B,); returns the (device, not
+        synchronised) loss - the weighted loss under ``loss_weighting`` - in a buffer that the next step overwrites."""
+        B, z_0, y, t, noise = self._check_batch(z_0, y, t, noise)
+        if self._ema_swapped:
+            raise RuntimeError("step() inside ema_weights(): the model holds the averaged weights")
+        self._check_attached()
+        if self.use_graph and self.philox_seed is None:
+            return self._graph_step(z_0, y, t, noise, B)
+        return self._eager_step(z_0, y, t, noise, B, self._next_rng())
+
+    def _graph_step(self, z_0, y, t, noise, B):
+        dev, Ld = self.device, self.model.latent_dim
+        key = (B, self.model.training)
+        if key != self._graph_key:
+            if self._graph_key != ("warm",) + key:
+                # the first step with this batch size runs eagerly (workspace, first-launch set-up); the next captures
+                self._graph, self._gws, self._graph_key = None, None, ("warm",) + key
+                return self._eager_step(z_0, y, t, noise, B, self._next_rng())
+            self._gz = torch.empty(B, Ld, dtype=torch.float32, device=dev)
+            self._gnoise = torch.empty(B, Ld, dtype=torch.float32, device=dev)
+            self._gy = torch.empty(B, dtype=torch.int64, device=dev)
+            self._gt = torch.zeros(B, dtype=torch.int64, device=dev)
+            self._grng = torch.zeros(2, dtype=torch.int64, device=dev)
+            self._hyper = torch.zeros(3 if self.ema is None else 4, dtype=torch.float32, device=dev)
+            # the graph holds the workspace's raw address and replays never pass through _workspace(): keep it alive
+            # (and cached under B) for as long as the graph, whatever other batch sizes evaluate() / step() see
+            self._graph = None
+            self._gws = self._workspace(B)
+            if self.max_grad_norm is not None and self._clip_scratch is None:
+                self._clip_scratch = torch.empty(lib.tdx_adam_clip_scratch_bytes(), dtype=torch.uint8, device=dev)
+            self.diffusion.tables(dev)
+            keep = (self.last_dropout_seed, self.last_dropout_offset)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._eager_step(self._gz, self._gy, self._gt, self._gnoise, B, (0, 0), hyper=self._hyper,
+                                 rng_dev=self._grng)
+            self.step_count -= 1   # the capture ran the host bookkeeping once without executing anything
+            self.last_dropout_seed, self.last_dropout_offset = keep
+            self._graph, self._graph_key = g, key
+        rng = self._next_rng()
+        self._gz.copy_(z_0)
+        self._gy.copy_(y)
+        if t is None:
+            self._gt.random_(0, self.diffusion.num_timesteps)   # outside the graph: torch's generator advances as in
+        else:                                                    # the eager step (randint, then randn_like)
+            self._gt.copy_(t)
+        if noise is None:
+            self._gnoise.normal_()
+        else:
+            self._gnoise.copy_(noise)
+        self._grng.copy_(torch.tensor([_i64(rng[0]), _i64(rng[1])], dtype=torch.int64))
+        self.last_dropout_seed, self.last_dropout_offset = rng
+        self.step_count += 1
+        self._hyper.copy_(torch.tensor(self._adam_hyper(), dtype=torch.float32))
+        self._graph.replay()
+        return self.loss
+
+    @torch.no_grad()
+    def evaluate(self, z_0: torch.Tensor, y: torch.Tensor, t: Optional[torch.Tensor] = None,
+                 noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The validation loop's loss (diffusion_transformer.py:219-228) as a fresh device scalar: the same forward and
+        loss launches with dropout off whatever ``model.training`` says; no gradient, moment, parameter, average or
+        ``step_count`` changes."""
+        B, z_0, y, t, noise = self._check_batch(z_0, y, t, noise)
+        self._check_attached()
+        if t is None:
+            t = torch.randint(0, self.diffusion.num_timesteps, (B,), device=self.device)
+        z_t, target = self._q_sample(z_0, t, noise)
+        out = torch.empty(1, dtype=torch.float32, device=self.device)
+        self._loss_grads(z_t, t, y, target, B, out, False, False, (0, 0))
+        return out[0]
+
+    # -------------------------------------------------------------------- EMA
+    def _need_ema(self, what: str):
+        if self.ema is None:
+            raise RuntimeError(f"{what} needs TransformerTrainStep(ema_decay=...)")
+        if self._ema_swapped:
+            raise RuntimeError(f"{what} inside ema_weights(): the average and the parameters have traded places")
+
+    def reset_ema(self):
+        """The average starts again from the current parameters."""
+        self._need_ema("reset_ema()")
+        self.ema.copy_(self.flat_param)
+
+    def ema_state_dict(self):
+        """The model's ``state_dict()`` with the averaged parameters (clones of the slices of ``self.ema``)."""
+        self._need_ema("ema_state_dict()")
+        out = type(self.model.state_dict())()
+        for k, v in self.model.state_dict().items():
+            lo, hi = self.offsets[k]
+            out[k] = self.ema[lo:hi].view(v.shape).clone()
+        return out
+
+    def load_ema_state_dict(self, sd):
+        """Inverse of ``ema_state_dict()``."""
+        self._need_ema("load_ema_state_dict()")
+        for k, (lo, hi) in self.offsets.items():
+            if sd[k].numel() != hi - lo:
+                raise ValueError(f"{k}: {tuple(sd[k].shape)} does not fit the parameter's {hi - lo} elements")
+        for k, (lo, hi) in self.offsets.items():
+            self.ema[lo:hi].copy_(sd[k].detach().reshape(-1))
+
+    def _swap_ema(self):
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        check(lib.tdx_swap_f32(self.flat_param.data_ptr(), self.ema.data_ptr(), self.flat_param.numel(), st),
+              "tdx_swap_f32")
+        self._ema_swapped = not self._ema_swapped
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the module IS the averaged model: one ``tdx_swap_f32`` launch exchanges ``flat_param`` and
+        ``ema`` on entry and again on exit (also when the body raises).  ``step()`` and a nested ``ema_weights()`` raise
+        inside."""
+        self._need_ema("ema_weights()")
+        self._swap_ema()
+        try:
+            yield self.model
+        finally:
+            self._swap_ema()
