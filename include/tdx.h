@@ -195,6 +195,40 @@ int tdx_p_sample_update(float* x_out, const float* x, const float* out, int64_t 
                         int guided, float w, float lo, float hi, float* hist, const float* known, const float* mask,
                         int64_t* counter_dec, tdx_stream_t stream);
 
+/* Dynamic thresholding (Saharia et al. 2022, Imagen, 2.3): the clamp of the x0 / multistep form with a bound per sample,
+ * a quantile of |x0 - c| over the sample, in place of the fixed one.  The data range is [lo, hi], finite, lo < hi;
+ * c = (lo + hi) / 2, h = (hi - lo) / 2.  Row t = *t_idx of coef5 gives p and q.  For sample b of n_samples, per elements
+ * each, every operation fp32, rounded separately, in the order written:
+ *   u_j   = p*x_j + q*o_j - c            o_j: the network's output; guided: out_u + w (out_c - out_u)
+ *   a     = sort(|u_j|), ascending
+ *   s_q   = a[rank] + frac * (a[min(rank+1, per-1)] - a[rank])
+ *   s_b   = max(s_q, h);   r_b = h / s_b
+ *   x0c_j = min(max(c + min(max(u_j, -s_b), s_b) * r_b, lo), hi)
+ * From x0c on the step is the x0-form / multistep step above: the blend with known / mask, (A*x0 + Bx*x) + sigma*z or
+ * + H*hist, and the history stores the thresholded (and blended) value.  Where s_q <= h this is the static clamp
+ * (s_b = h, r_b = 1), and the outer clamp keeps x0c in [lo, hi] exactly.  rank, frac: linear interpolation as in
+ * torch.quantile(|u|, q, dim=1), computed by the host in fp64: pos = q*(per-1), rank = floor(pos),
+ * frac = float32(pos - rank).  |u| is ordered by its bit pattern as an unsigned integer (exact for non-negative floats;
+ * a NaN sorts last, and a NaN s_q is written as it is).
+ *
+ * tdx_x0_dyn_threshold writes (s_b, r_b) of every sample to thr, (n_samples, 2) floats: one workgroup per sample, exact
+ * selection by radix over the 32-bit keys with integer LDS histograms (no global atomics; bit-reproducible).  x:
+ * n_samples*per floats (guided != 0: the first half of the 2n-row state); out: as many (guided: twice as many, the
+ * caller's condition then the null condition).  TDX_E_BADARG, nothing written: a null pointer, n_samples <= 0,
+ * per <= 0, per % 4, bounds that are not finite with lo < hi, rank outside [0, per), frac outside [0, 1]. */
+int tdx_x0_dyn_threshold(const float* x, const float* out, int n_samples, int per, const float* coef5,
+                         const int32_t* t_idx, int guided, float w, float lo, float hi, int rank, float frac, float* thr,
+                         tdx_stream_t stream);
+/* tdx_p_sample_update with the thresholded x0c: its arguments, then thr (what tdx_x0_dyn_threshold wrote for this x,
+ * out and row) and per (element j belongs to sample j / per).  TDX_STEP_X0 and TDX_STEP_MS only.  TDX_E_BADARG, nothing
+ * written: the cases of tdx_p_sample_update, TDX_STEP_EPS, a null thr, per <= 0, per % 4, n % per, a bound that is not
+ * finite. */
+int tdx_p_sample_update_dyn(float* x_out, const float* x, const float* out, int64_t n, int form, const float* coef,
+                            const int32_t* t_idx, const int64_t* tau, const float* z, int use_philox,
+                            uint64_t philox_seed, int guided, float w, float lo, float hi, float* hist,
+                            const float* known, const float* mask, int64_t* counter_dec, float* thr, int per,
+                            tdx_stream_t stream);
+
 /* Condition dropout for training the unconditional branch: sample b is dropped iff a Philox uniform in [0,1) keyed by
  * (seed, offset, b) is < p (p == 0: exact copy, p == 1: every sample).  A dropped sample gets label -1 / a zeroed row.
  * The two entries draw the same mask for the same key.  In place (y_out == y, c_out == c) is allowed. */
@@ -833,6 +867,18 @@ int tdx_unet_eval_step_update(tdx_unet* u, const void* const* params, void* cons
                               void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed, int form,
                               int guided, float w, float lo, float hi, float* hist, const float* known,
                               const float* mask, tdx_stream_t stream);
+/* The reverse step with dynamic thresholding (tdx_x0_dyn_threshold): tdx_unet_eval_step_update's arguments plus rank,
+ * frac and thr, (n, 2) floats kept by the caller (n = batch, guided: batch / 2; per = n_elems / n).  TDX_STEP_X0 and
+ * TDX_STEP_MS only.  The bound of a sample is known only after the whole forward, so the update never runs in
+ * final_conv's epilogue: the step is the head, the forward with the plain final_conv, the threshold launch and the
+ * update as tdx_p_sample_update_dyn.  Sampling tables (the update advances the counter), the half-batch forward and
+ * the latent MLP as in tdx_unet_eval_step_update.  TDX_E_BADARG: the cases of the three entries it is made of. */
+int tdx_unet_eval_step_update_dyn(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
+                                  const void* cond, const float* z, const float* coef, const int64_t* tau, int S,
+                                  int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps, int64_t n_elems,
+                                  void* workspace, size_t workspace_bytes, int batch, uint64_t philox_seed, int form,
+                                  int guided, float w, float lo, float hi, float* hist, const float* known,
+                                  const float* mask, int rank, float frac, float* thr, tdx_stream_t stream);
 
 /* Testing aid: offset (in floats) and element count of a named intermediate inside the
  * workspace after a forward: "x0", "Y0".."Y12", "ss0".."ss12", "e1p", "cat1", "d1a", ... */

@@ -32,11 +32,15 @@ def sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples
     """conditional_diffusion.py:354-386, including its argument errors.  ``guidance_scale=w``: classifier-free
     guidance ``eps_u + w (eps_c - eps_u)`` against the null label (schedule.sample_loop); ``None``: none.
     ``clip_denoised=True | (lo, hi)`` (through ``**kw``, like ``prediction``): clipped-x0 sampling, which keeps guided
-    samples inside the data range at w > 1.  ``known=x, mask=m`` (through ``**kw``; both or neither, broadcast to
+    samples inside the data range at w > 1 by pinning what leaves it to the ends of the range (``dynamic_threshold``
+    below rescales instead).  ``known=x, mask=m`` (through ``**kw``; both or neither, broadcast to
     ``(n_samples, *input shape)``): inpainting - every step blends the implied x_0 with ``known`` where ``mask`` is 1 (a
     fraction: a soft edge) and the returned sample equals ``known`` there exactly; ``x_T`` stays pure noise - an
     image-to-image start composes from the existing ``x_T=`` and ``timesteps=`` arguments and is not part of this
-    (schedule.sample_loop).  ``ddim_sample`` and ``dpm_sample`` take the two keywords too."""
+    (schedule.sample_loop).  ``ddim_sample`` and ``dpm_sample`` take the two keywords too.  ``dynamic_threshold=q`` (through ``**kw``; q in (0, 1]): Imagen's dynamic thresholding on the range of
+    ``clip_denoised`` ((-1, 1) when that is off) - per sample and step the q-quantile s of ``|x0 - centre|`` bounds the
+    implied x_0 and, where it exceeds the half range h, scales it back by h / s (schedule.sample_loop); ``ddim_sample``
+    and ``dpm_sample`` take it too."""
     _check_labels(y, n_samples)
     return sample_loop(noise_model, diffusion, device, n_samples, y, guidance_scale=guidance_scale, **kw)
 

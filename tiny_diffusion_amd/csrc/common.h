@@ -75,6 +75,19 @@ __device__ static inline float x0_clamped(float x, float o, float p, float q, fl
   return fminf(fmaxf(__fadd_rn(__fmul_rn(p, x), __fmul_rn(q, o)), lo), hi);
 }
 
+// 1b. The same with a bound per sample (dynamic thresholding, include/tdx.h): u = x0 - c is clamped to the sample's
+//      [-s, s], scaled back by r = h / s around the centre c of the data range, and clamped to [lo, hi]:
+//      x0c = min(max(c + min(max(p*x + q*out - c, -s), s) * r, lo), hi)
+// With s = h, r = 1 (the quantile does not exceed h) this is x0_clamped up to the sign of a zero.
+__device__ static inline float x0_dyn_u(float x, float o, float p, float q, float c) {
+  return __fsub_rn(__fadd_rn(__fmul_rn(p, x), __fmul_rn(q, o)), c);
+}
+__device__ static inline float x0_thresholded(float x, float o, float p, float q, float lo, float hi, float c, float s,
+                                              float r) {
+  const float v = fminf(fmaxf(x0_dyn_u(x, o, p, q, c), -s), s);
+  return fminf(fmaxf(__fadd_rn(c, __fmul_rn(v, r)), lo), hi);
+}
+
 // 2. Inpainting: the blend with the caller's data between the clamp and the step,  x0m = (1 - m)*x0c + m*known.
 // m == 1 gives `known` and m == 0 gives x0c bit for bit ((1-1)*x0c = +-0, 1*known = known; 1*x0c = x0c, 0*known = +-0:
 // for finite operands); a fractional m is a soft edge.  `known` is not clamped.  The known region steps from x0 = known
@@ -111,12 +124,13 @@ __device__ static inline PRow pstep_row(const float* coef, int t) {
 // network's output (guided: the cfg_eps combination); zh: the noise (EPS, X0; 0 for none) or the history (MS; not
 // loaded when r.e == 0); known / m: read when MK only.  MS: *x0_out is what the caller stores as the next step's
 // history - the BLENDED prediction when MK, which keeps the known region on the forward marginal of the deterministic
-// chain (with the clamped prediction as history it leaves it).
-template <int FORM, bool MK>
+// chain (with the clamped prediction as history it leaves it).  DT (X0, MS): the clamp is x0_thresholded with the
+// sample's (s, r) and the centre c.
+template <int FORM, bool MK, bool DT = false>
 __device__ static inline float pstep_elem(float x, float o, float zh, float known, float m, const PRow& r, float lo,
-                                          float hi, float* x0_out) {
+                                          float hi, float* x0_out, float c = 0.f, float ts = 0.f, float tr = 0.f) {
   if (FORM == TDX_STEP_EPS) return p_step(x, o, zh, r.A, r.Bx, r.e);
-  float x0 = x0_clamped(x, o, r.p, r.q, lo, hi);
+  float x0 = DT ? x0_thresholded(x, o, r.p, r.q, lo, hi, c, ts, tr) : x0_clamped(x, o, r.p, r.q, lo, hi);
   if (MK) x0 = x0_blend(x0, known, m);
   if (FORM == TDX_STEP_MS) *x0_out = x0;
   return FORM == TDX_STEP_MS ? x0_step_hist(x0, x, zh, r.A, r.Bx, r.e) : x0_step_noise(x0, x, zh, r.A, r.Bx, r.e);

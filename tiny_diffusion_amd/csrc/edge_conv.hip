@@ -552,6 +552,7 @@ void launch_psample_form(const void* in, const float* w, const float* bias, floa
 int tdx_final_conv_fwd_psample(const void* in, const float* w, const float* bias, float* eps_out, int B, int H, int W,
                                int cout, const PStep& s, hipStream_t st, int io16) {
   if (!s.x || (s.guided && (B & 1))) return TDX_E_BADARG;   // guided: two equal halves
+  if (s.thr) return TDX_E_BADARG;   // a sample's bound needs the whole output first: never in the epilogue
   const int64_t M = (int64_t)(s.guided ? B / 2 : B) * H * W;
   if (pstep_valid(s, M * cout)) return TDX_E_BADARG;
   if (cout != 1 && cout != 4) return TDX_E_SHAPE;

@@ -168,7 +168,9 @@ extern "C" int tdx_q_sample_target_philox(const float* x0, const int64_t* t, con
 // combined first (cfg_eps is linear in the network's output, whatever it predicts) and the one update is written to
 // both halves.  z, hist, known, mask and the Philox index are the first half's - the guided chain of n samples
 // consumes the stream of the unguided chain of n samples.
-template <int FORM, bool GD, bool MK, bool PHILOX>
+// DT (X0, MS): dynamic thresholding - float4 i lies in sample i / (per / 4) (per % 4 == 0: it never straddles two), whose
+// (s, r) x0_threshold_kernel wrote to s.thr before this launch.
+template <int FORM, bool GD, bool MK, bool PHILOX, bool DT = false>
 __global__ void pstep_kernel(float4* xo, const float4* x, const float4* __restrict__ out, int64_t n4, const PStep s) {
   const float4* __restrict__ z = (const float4*)s.z;
   const float4* __restrict__ known = (const float4*)s.known;
@@ -181,9 +183,13 @@ __global__ void pstep_kernel(float4* xo, const float4* x, const float4* __restri
   if (s.counter_dec && blockIdx.x == 0 && threadIdx.x == 0) *s.counter_dec = (int64_t)t - 1;
   const PRow r = pstep_row<FORM>(s.coef, t);
   const float w = s.w, lo = s.lo, hi = s.hi;
+  const float2* __restrict__ thr = (const float2*)s.thr;
+  const int64_t per4 = s.per >> 2;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
        i += (int64_t)gridDim.x * blockDim.x) {
     const float4 xv = x[i];
+    float2 sr = make_float2(0.f, 0.f);
+    if (DT) sr = thr[i / per4];
     float4 e = out[i], zh = make_float4(0.f, 0.f, 0.f, 0.f), kn = zh, mv = zh, o, h;
     if (FORM == TDX_STEP_MS) {
       if (r.e != 0.0f) zh = hist[i];
@@ -200,27 +206,38 @@ __global__ void pstep_kernel(float4* xo, const float4* x, const float4* __restri
       e.z = cfg_eps(e.z, eu.z, w);
       e.w = cfg_eps(e.w, eu.w, w);
     }
-    o.x = pstep_elem<FORM, MK>(xv.x, e.x, zh.x, kn.x, mv.x, r, lo, hi, &h.x);
-    o.y = pstep_elem<FORM, MK>(xv.y, e.y, zh.y, kn.y, mv.y, r, lo, hi, &h.y);
-    o.z = pstep_elem<FORM, MK>(xv.z, e.z, zh.z, kn.z, mv.z, r, lo, hi, &h.z);
-    o.w = pstep_elem<FORM, MK>(xv.w, e.w, zh.w, kn.w, mv.w, r, lo, hi, &h.w);
+    o.x = pstep_elem<FORM, MK, DT>(xv.x, e.x, zh.x, kn.x, mv.x, r, lo, hi, &h.x, s.c, sr.x, sr.y);
+    o.y = pstep_elem<FORM, MK, DT>(xv.y, e.y, zh.y, kn.y, mv.y, r, lo, hi, &h.y, s.c, sr.x, sr.y);
+    o.z = pstep_elem<FORM, MK, DT>(xv.z, e.z, zh.z, kn.z, mv.z, r, lo, hi, &h.z, s.c, sr.x, sr.y);
+    o.w = pstep_elem<FORM, MK, DT>(xv.w, e.w, zh.w, kn.w, mv.w, r, lo, hi, &h.w, s.c, sr.x, sr.y);
     xo[i] = o;
     if (GD) xo[i + n4] = o;
     if (FORM == TDX_STEP_MS) hist[i] = h;
   }
 }
 
-// the 16 live instantiations: EPS has no masked update, MS no noise (one value of PHILOX)
-template <int FORM, bool GD, bool MK>
-static void pstep_launch_noise(const PStep& s, float4* xo, const float4* x, const float4* out, int64_t n4, hipStream_t st) {
+// the 16 live instantiations: EPS has no masked update, MS no noise (one value of PHILOX); and the 12 of X0 and MS
+// once more with the thresholded clamp (s.thr)
+template <int FORM, bool GD, bool MK, bool PHILOX>
+static void pstep_launch_thr(const PStep& s, float4* xo, const float4* x, const float4* out, int64_t n4, hipStream_t st) {
   const int grid = ew_grid(n4, 256);
-  if constexpr (FORM != TDX_STEP_MS) {
-    if (s.philox) {
-      pstep_kernel<FORM, GD, MK, true><<<grid, 256, 0, st>>>(xo, x, out, n4, s);
+  if constexpr (FORM != TDX_STEP_EPS) {
+    if (s.thr) {
+      pstep_kernel<FORM, GD, MK, PHILOX, true><<<grid, 256, 0, st>>>(xo, x, out, n4, s);
       return;
     }
   }
-  pstep_kernel<FORM, GD, MK, false><<<grid, 256, 0, st>>>(xo, x, out, n4, s);
+  pstep_kernel<FORM, GD, MK, PHILOX><<<grid, 256, 0, st>>>(xo, x, out, n4, s);
+}
+template <int FORM, bool GD, bool MK>
+static void pstep_launch_noise(const PStep& s, float4* xo, const float4* x, const float4* out, int64_t n4, hipStream_t st) {
+  if constexpr (FORM != TDX_STEP_MS) {
+    if (s.philox) {
+      pstep_launch_thr<FORM, GD, MK, true>(s, xo, x, out, n4, st);
+      return;
+    }
+  }
+  pstep_launch_thr<FORM, GD, MK, false>(s, xo, x, out, n4, st);
 }
 template <int FORM>
 static void pstep_launch_form(const PStep& s, float4* xo, const float4* x, const float4* out, int64_t n4, hipStream_t st) {
@@ -264,6 +281,163 @@ extern "C" int tdx_p_sample_update(float* x_out, const float* x, const float* ou
   const PStep s = pstep_of(form, coef, t_idx, tau, z, use_philox, philox_seed, guided, w, lo, hi, hist, known, mask,
                            counter_dec);
   return tdx_pstep_launch(s, x_out, x, out, n, to_stream(stream)) ? TDX_E_BADARG : 0;
+}
+
+extern "C" int tdx_p_sample_update_dyn(float* x_out, const float* x, const float* out, int64_t n, int form,
+                                       const float* coef, const int32_t* t_idx, const int64_t* tau, const float* z,
+                                       int use_philox, uint64_t philox_seed, int guided, float w, float lo, float hi,
+                                       float* hist, const float* known, const float* mask, int64_t* counter_dec,
+                                       float* thr, int per, tdx_stream_t stream) {
+  if (!thr) return TDX_E_BADARG;
+  PStep s = pstep_of(form, coef, t_idx, tau, z, use_philox, philox_seed, guided, w, lo, hi, hist, known, mask,
+                     counter_dec);
+  s.thr = thr; s.per = per; s.c = dyn_centre(lo, hi);
+  return tdx_pstep_launch(s, x_out, x, out, n, to_stream(stream)) ? TDX_E_BADARG : 0;
+}
+
+// ------------------------------------------------------- dynamic thresholding
+// (s_b, r_b) of include/tdx.h for sample b = blockIdx.x: the key of element j is the bit pattern of |u_j| (ordered as the
+// floats are, a NaN last), and a[rank] is found by radix selection, most significant byte first.  Each of the four
+// passes recomputes the keys from x / out (a sample is L2-resident; keeping per / 256 keys per thread in registers would
+// fix `per` at compile time), counts the byte under inspection of the keys that match the bytes chosen so far in an
+// LDS histogram, and a block-wide scan of the 256 counts picks the bin that holds the rank.  Integer LDS adds only:
+// the result does not depend on the order of arrival.  A sample's keys crowd into a few bins (the exponent byte in the
+// first pass), so every bin is kept THR_REP times, in THR_REP different banks, lane % THR_REP choosing the copy: a wave's
+// adds to one bin serialise 64 / THR_REP deep, not 64.  a[rank + 1] comes from the last pass: it is a[rank] again when
+// the bins up to the chosen one hold more than the rank left over + 1 keys; otherwise the lowest occupied bin above
+// it or, when there is none, the smallest key with higher upper bytes (a minimum each thread keeps in that pass).
+// Thread t owns bin t: the block size is the number of bins.
+#define THR_BLOCK 256
+#define THR_REP 16
+
+template <bool GD>
+__device__ __forceinline__ void thr_keys(const float4* __restrict__ x, const float4* __restrict__ oc,
+                                         const float4* __restrict__ ou, int i, float p, float q, float c, float w,
+                                         uint32_t k[4]) {
+  const float4 xv = x[i];
+  float4 e = oc[i];
+  if (GD) {
+    const float4 eu = ou[i];
+    e.x = cfg_eps(e.x, eu.x, w);
+    e.y = cfg_eps(e.y, eu.y, w);
+    e.z = cfg_eps(e.z, eu.z, w);
+    e.w = cfg_eps(e.w, eu.w, w);
+  }
+  k[0] = __float_as_uint(x0_dyn_u(xv.x, e.x, p, q, c)) & 0x7fffffffu;
+  k[1] = __float_as_uint(x0_dyn_u(xv.y, e.y, p, q, c)) & 0x7fffffffu;
+  k[2] = __float_as_uint(x0_dyn_u(xv.z, e.z, p, q, c)) & 0x7fffffffu;
+  k[3] = __float_as_uint(x0_dyn_u(xv.w, e.w, p, q, c)) & 0x7fffffffu;
+}
+
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t u = (uint32_t)__shfl_xor((int)v, o, 64);
+    v = u < v ? u : v;
+  }
+  return v;
+}
+
+template <bool GD>
+__global__ void __launch_bounds__(THR_BLOCK)
+x0_threshold_kernel(const float* __restrict__ x, const float* __restrict__ out, int n_samples, int per,
+                    const float* __restrict__ coef5, const int32_t* __restrict__ t_idx, float w, float c, float h,
+                    int rank, float frac, float2* __restrict__ thr) {
+  __shared__ uint32_t hist[256 * THR_REP];
+  __shared__ uint32_t wtot[THR_BLOCK / 64], wmin[THR_BLOCK / 64];
+  __shared__ uint32_t sel[3];   // the chosen bin, the rank left inside it, whether the next key up equals the chosen one
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x;
+  const int t = *t_idx;
+  const float p = coef5[5 * t + 0], q = coef5[5 * t + 1];
+  const int per4 = per >> 2;
+  const float4* xs = (const float4*)(x + (int64_t)b * per);
+  const float4* oc = (const float4*)(out + (int64_t)b * per);
+  const float4* ou = (const float4*)(out + ((int64_t)n_samples + b) * per);   // read when GD only
+  uint32_t prefix = 0, left = (uint32_t)rank, cnt = 0;
+  uint32_t above = 0xffffffffu;   // last pass: the smallest key whose upper three bytes exceed the chosen ones
+  if (tid < 3) sel[tid] = 0;      // (every pass, one thread writes all three: valid arguments always select a bin)
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    for (int j = tid; j < 256 * THR_REP; j += THR_BLOCK) hist[j] = 0;
+    __syncthreads();
+    for (int i = tid; i < per4; i += THR_BLOCK) {
+      uint32_t k[4];
+      thr_keys<GD>(xs, oc, ou, i, p, q, c, w, k);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const uint32_t upper = pass ? k[e] >> (shift + 8) : 0u;
+        if (upper == prefix) atomicAdd(&hist[((k[e] >> shift) & 255u) * THR_REP + (lane & (THR_REP - 1))], 1u);
+        else if (pass == 3 && upper > prefix && k[e] < above) above = k[e];
+      }
+    }
+    __syncthreads();
+    cnt = 0;
+#pragma unroll
+    for (int r = 0; r < THR_REP; ++r) cnt += hist[tid * THR_REP + r];
+    uint32_t incl = cnt;   // inclusive scan over the bins: within the wave, then across the waves
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t v = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += v;
+    }
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    for (int v = 0; v < wave; ++v) incl += wtot[v];
+    const uint32_t excl = incl - cnt;
+    if (cnt && excl <= left && left < incl) {   // one thread: the counts of the matching keys sum to more than `left`
+      sel[0] = (uint32_t)tid;
+      sel[1] = left - excl;
+      sel[2] = incl > left + 1u;
+    }
+    __syncthreads();
+    prefix = (prefix << 8) | sel[0];
+    left = sel[1];
+  }
+  // prefix is the key a[rank]; the candidates for a[rank + 1] above it
+  const uint32_t bin = prefix & 255u;
+  uint32_t cand = above;
+  if ((uint32_t)tid > bin && cnt) cand = (prefix & ~255u) | (uint32_t)tid;   // below every key with higher upper bytes
+  cand = wave_min_u32(cand);
+  if (lane == 0) wmin[wave] = cand;
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t nxt = wmin[0];
+#pragma unroll
+    for (int v = 1; v < THR_BLOCK / 64; ++v) nxt = wmin[v] < nxt ? wmin[v] : nxt;
+    if (sel[2] || rank + 1 >= per || nxt == 0xffffffffu) nxt = prefix;
+    const float a0 = __uint_as_float(prefix), a1 = __uint_as_float(nxt);
+    const float sq = __fadd_rn(a0, __fmul_rn(frac, __fsub_rn(a1, a0)));
+    const float s = !(sq <= h) ? sq : h;   // max(s_q, h); a NaN quantile is written as it is
+    thr[b] = make_float2(s, __fdiv_rn(h, s));
+  }
+}
+
+int tdx_x0_threshold_launch(const PStep& s, const float* x, const float* out, int n_samples, int rank, float frac,
+                            hipStream_t st) {
+  if (!x || !out || !s.coef || !s.t_idx || !s.thr || n_samples <= 0 || s.per <= 0 || s.per % 4) return TDX_E_BADARG;
+  if (!(s.lo < s.hi) || !std::isfinite(s.lo) || !std::isfinite(s.hi) || !std::isfinite(s.hi - s.lo)) return TDX_E_BADARG;
+  if (rank < 0 || rank >= s.per || !(frac >= 0.0f && frac <= 1.0f)) return TDX_E_BADARG;
+  const float c = dyn_centre(s.lo, s.hi), h = dyn_half(s.lo, s.hi);
+  if (s.guided)
+    x0_threshold_kernel<true><<<n_samples, THR_BLOCK, 0, st>>>(x, out, n_samples, s.per, s.coef, s.t_idx, s.w, c, h,
+                                                               rank, frac, (float2*)s.thr);
+  else
+    x0_threshold_kernel<false><<<n_samples, THR_BLOCK, 0, st>>>(x, out, n_samples, s.per, s.coef, s.t_idx, s.w, c, h,
+                                                                rank, frac, (float2*)s.thr);
+  TDX_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tdx_x0_dyn_threshold(const float* x, const float* out, int n_samples, int per, const float* coef5,
+                                    const int32_t* t_idx, int guided, float w, float lo, float hi, int rank, float frac,
+                                    float* thr, tdx_stream_t stream) {
+  PStep s{};
+  s.coef = coef5; s.t_idx = t_idx;
+  s.guided = guided != 0; s.w = w;
+  s.lo = lo; s.hi = hi;
+  s.thr = thr; s.per = per;
+  return tdx_x0_threshold_launch(s, x, out, n_samples, rank, frac, to_stream(stream)) ? TDX_E_BADARG : 0;
 }
 
 // The entries of each form (include/tdx.h): the null checks that are the entry's own, then the one launcher.

@@ -1,5 +1,6 @@
 // Library-internal entry points (not part of the C ABI).
 #pragma once
+#include <cmath>
 #include "common.h"
 
 int tdx_copy_segments(const float* const* src, float* const* dst, const size_t* n, int count, hipStream_t st);
@@ -28,6 +29,8 @@ int tdx_final_conv_fwd(const void* in, const float* w, const float* bias, float*
 // guided: x and out hold two halves - the caller's condition, the null condition - that cfg_eps combines under w; the
 // one update is written to both halves of x, and z / hist / known / mask / Philox are those of the first half.
 // known / mask (X0, MS): x0 <- x0_blend(x0, known, mask) before the step (inpainting).
+// thr (X0, MS): dynamic thresholding - (s, r) per sample of `per` elements, written by tdx_x0_threshold_launch, drive
+// x0_thresholded in place of x0_clamped; [lo, hi] is then the finite data range and c its centre.
 struct PStep {
   int form; const float* coef; const int32_t* t_idx; const int64_t* tau;
   const float* z; int philox; uint64_t seed;   // philox: in-kernel noise, z ignored
@@ -40,6 +43,7 @@ struct PStep {
   // element's index in the whole batch (a half-batch launch keeps the batch's Philox stream; hist, known and mask are
   // indexed by it) and the elements of one guided half
   float* x; int64_t elem0, half;
+  float* thr; int per; float c;   // dynamic thresholding (never in the fused epilogue)
 };
 // 0, or the error of an update over n elements (guided: per half): TDX_E_SHAPE for an eps-form n % 4 != 0 with
 // nothing else wrong, as the eps-form entries have always answered; TDX_E_BADARG for every other broken rule
@@ -50,8 +54,17 @@ static inline int pstep_valid(const PStep& s, int64_t n) {
   if (s.form == TDX_STEP_MS && (!s.hist || s.z)) return TDX_E_BADARG;
   if ((s.known != nullptr) != (s.mask != nullptr) || (s.known && s.form == TDX_STEP_EPS)) return TDX_E_BADARG;
   if (n % 4) return s.form == TDX_STEP_EPS ? TDX_E_SHAPE : TDX_E_BADARG;
+  if (s.thr && (s.form == TDX_STEP_EPS || s.per <= 0 || s.per % 4 || n % s.per || !std::isfinite(s.lo) ||
+                !std::isfinite(s.hi) || !std::isfinite(s.hi - s.lo))) return TDX_E_BADARG;
   return 0;
 }
+// The centre and the half width of the data range, (lo + hi) / 2 and (hi - lo) / 2 in fp32
+static inline float dyn_centre(float lo, float hi) { return (lo + hi) / 2.0f; }
+static inline float dyn_half(float lo, float hi) { return (hi - lo) / 2.0f; }
+// (s_b, r_b) of s.thr for the n_samples samples of s.per elements of x / out (guided: out holds 2 n_samples rows), from
+// s.coef, s.t_idx, s.guided, s.w, s.lo, s.hi (x0_threshold_kernel, elementwise.hip); rank in [0, per), frac in [0, 1]
+int tdx_x0_threshold_launch(const PStep& s, const float* x, const float* out, int n_samples, int rank, float frac,
+                            hipStream_t st);
 // x_out may alias x (guided: it must); the fused-only fields of s are ignored
 int tdx_pstep_launch(const PStep& s, float* x_out, const float* x, const float* out, int64_t n, hipStream_t st);
 // final_conv forward with the update in its epilogue (sampling): s.x in place, the network's output still goes to eps_out

@@ -1288,10 +1288,13 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
 // schedule of n_steps steps - the counter is the step index k, the coefficient row, and the network runs at tau[k].
 // ps.guided: batch = 2n rows of x, the second half under the null condition, n_elems the first half's.  The head, the
 // counter and the half-batch logic do not know the update's form; a half-batch launch indexes the one history, known
-// and mask by the element's place in the whole batch (PStep::elem0).
+// and mask by the element's place in the whole batch (PStep::elem0).  ps.thr (dynamic thresholding, dyn_rank / dyn_frac
+// the quantile): the bound of a sample needs the whole output, so the epilogue is never armed - after the forward (whose
+// half-batch streams have joined) come the threshold launch and the update kernel, which advances the table-mode counter.
 static int eval_step_impl(tdx_unet* u, const void* const* params, void* const* buffers, float* x, const void* cond,
                           PStep ps, int n_steps, int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps,
-                          int64_t n_elems, void* workspace, size_t workspace_bytes, int batch, tdx_stream_t stream) {
+                          int64_t n_elems, void* workspace, size_t workspace_bytes, int batch, tdx_stream_t stream,
+                          int dyn_rank = 0, float dyn_frac = 0.f) {
   const int64_t* tau = ps.tau;
   const bool guided = ps.guided;
   if (!u || !params || !buffers || !x || !counter || !t_vec || !eps || !workspace || batch <= 0 || ps.t_idx != t_idx)
@@ -1338,7 +1341,7 @@ static int eval_step_impl(tdx_unet* u, const void* const* params, void* const* b
   u->skip_time_path = tab;
   u->whole_batch = guided;   // (set here, cleared below: no early return in between)
   // the UNets apply the update in final_conv's epilogue (one launch less); the latent MLP keeps the separate kernel
-  const bool fuse_ps = u->spec && (g_tdx_sample_fuse & 4) &&
+  const bool fuse_ps = u->spec && (g_tdx_sample_fuse & 4) && !ps.thr &&
                        (guided ? 2 : 1) * n_elems == (int64_t)batch * u->spec->in_ch * u->spec->out_hw * u->spec->out_hw;
   ps.counter_dec = tab ? counter : nullptr;
   if (fuse_ps) { u->ps = ps; u->ps.x = x; }
@@ -1348,6 +1351,7 @@ static int eval_step_impl(tdx_unet* u, const void* const* params, void* const* b
   u->whole_batch = false;
   u->ps = {};
   if (rc || fuse_ps) return rc;
+  if (ps.thr) RC(tdx_x0_threshold_launch(ps, x, eps, (int)(n_elems / ps.per), dyn_rank, dyn_frac, to_stream(stream)));
   // elementwise, so x is updated in place
   return tdx_pstep_launch(ps, x, x, eps, n_elems, to_stream(stream));
 }
@@ -1387,6 +1391,23 @@ extern "C" int tdx_unet_eval_step_update(tdx_unet* u, const void* const* params,
   if ((tau && S <= 0) || pstep_valid(ps, n_elems)) return TDX_E_BADARG;
   return eval_step_impl(u, params, buffers, x, cond, ps, tau ? S : 0, counter, t_idx, t_vec, eps, n_elems, workspace,
                         workspace_bytes, batch, stream);
+}
+
+extern "C" int tdx_unet_eval_step_update_dyn(tdx_unet* u, const void* const* params, void* const* buffers, float* x,
+                                             const void* cond, const float* z, const float* coef, const int64_t* tau,
+                                             int S, int64_t* counter, int32_t* t_idx, int64_t* t_vec, float* eps,
+                                             int64_t n_elems, void* workspace, size_t workspace_bytes, int batch,
+                                             uint64_t philox_seed, int form, int guided, float w, float lo, float hi,
+                                             float* hist, const float* known, const float* mask, int rank, float frac,
+                                             float* thr, tdx_stream_t stream) {
+  PStep ps = eval_pstep(form, coef, t_idx, tau, z, philox_seed, guided, w, lo, hi, hist, known, mask);
+  const int n = guided ? batch / 2 : batch;   // samples: the threshold buffer's rows
+  if (!thr || batch <= 0 || (guided && (batch & 1)) || n_elems <= 0 || n_elems % n || n_elems / n > INT32_MAX) return TDX_E_BADARG;
+  ps.thr = thr; ps.per = (int)(n_elems / n); ps.c = dyn_centre(lo, hi);
+  if ((tau && S <= 0) || pstep_valid(ps, n_elems)) return TDX_E_BADARG;
+  if (!(lo < hi) || rank < 0 || rank >= ps.per || !(frac >= 0.0f && frac <= 1.0f)) return TDX_E_BADARG;   // before the head kernel writes
+  return eval_step_impl(u, params, buffers, x, cond, ps, tau ? S : 0, counter, t_idx, t_vec, eps, n_elems, workspace,
+                        workspace_bytes, batch, stream, rank, frac);
 }
 
 // Build the sampling tables for the CURRENT INFER pack (call after tdx_unet_pack / the first INFER forward, once

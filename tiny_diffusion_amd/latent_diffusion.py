@@ -37,7 +37,10 @@ def sample(vae: VAE, noise_model: NoiseModel, diffusion: ForwardProcess, device,
     ``(n_samples, *(20,))``): inpainting - every step blends the implied z_0 with ``known`` where ``mask`` is 1 (a
     fraction: a soft edge) and the latent z handed to the decoder equals ``known`` there exactly; ``x_T`` stays pure noise - an
     image-to-image start composes from the existing ``x_T=`` and ``timesteps=`` arguments and is not part of this
-    (schedule.sample_loop).  ``ddim_sample`` and ``dpm_sample`` take the two keywords too."""
+    (schedule.sample_loop).  ``ddim_sample`` and ``dpm_sample`` take the two keywords too.  ``dynamic_threshold=q`` (through ``**kw``; q in (0, 1]): Imagen's dynamic thresholding on the range of
+    ``clip_denoised`` ((-1, 1) when that is off) - per sample and step the q-quantile s of ``|x0 - centre|`` bounds the
+    implied z_0 and, where it exceeds the half range h, scales it back by h / s (schedule.sample_loop); ``ddim_sample``
+    and ``dpm_sample`` take it too."""
     _check_labels(y, n_samples)
     vae.eval()
     z = sample_loop(noise_model, diffusion, device, n_samples, y, **kw)

@@ -47,6 +47,30 @@ def _clip_denoised(clip):
     return (float(clip[0]), float(clip[1]))
 
 
+def _dynamic_threshold(q, clip=None):
+    """The checked quantile of dynamic thresholding and its data range: ``None`` (off), or ``(q, (lo, hi))`` with q a
+    real number in (0, 1] - a bool, a NaN or anything outside is a ``ValueError`` - and the range the checked
+    ``clip_denoised`` (``_clip_denoised``'s result; ``None``: (-1, 1)), which must be finite: the bound of a sample is
+    measured against its half width."""
+    if q is None:
+        return None
+    if isinstance(q, (bool, np.bool_)) or not isinstance(q, numbers.Real) or math.isnan(q) or not 0 < q <= 1:
+        raise ValueError(f"dynamic_threshold must be None or a quantile in (0, 1], got {q!r}")
+    lo, hi = (-1.0, 1.0) if clip is None else clip
+    if math.isinf(lo) or math.isinf(hi):
+        raise ValueError(f"dynamic_threshold needs a finite data range: clip_denoised is ({lo}, {hi})")
+    return float(q), (lo, hi)
+
+
+def _quantile_rank(q: float, per: int):
+    """(rank, frac) of the q-quantile of ``per`` sorted values under linear interpolation, as ``torch.quantile``: in
+    fp64 ``pos = q (per - 1)``, ``rank = floor(pos)``, ``frac = float32(pos - rank)``; the quantile is
+    ``a[rank] + frac (a[min(rank + 1, per - 1)] - a[rank])``."""
+    pos = float(q) * (int(per) - 1)
+    rank = min(int(math.floor(pos)), int(per) - 1)
+    return rank, float(np.float32(pos - rank))
+
+
 class ForwardProcess:
     """diffusion.py:165-190.  ``betas`` / ``alphas`` / ``alphas_cumprod`` are CPU
     fp32 tensors computed with the reference's expressions (bit-identical); device
@@ -587,7 +611,7 @@ def ddim_sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: 
     replaces ``steps``.  The drop-in modules' ``ddim_sample`` functions call this (``guidance_scale`` and the other
     keywords of ``sample_loop`` pass through, ``prediction`` and ``known`` / ``mask`` among them)."""
     _prediction(kw.get("prediction", "eps"))
-    _clip_denoised(kw.get("clip_denoised"))
+    _dynamic_threshold(kw.get("dynamic_threshold"), _clip_denoised(kw.get("clip_denoised")))
     if kw.get("guidance_scale") is not None:
         _guidance_scale(noise_model, kw["guidance_scale"], y)   # an argument error comes before the schedule's
     _known_mask(kw.get("known"), kw.get("mask"), n_samples, _in_shape(noise_model))
@@ -603,7 +627,7 @@ def dpm_sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: i
     ``use_graph`` and ``philox_seed`` (which only selects the device-counter graph mode: there is no noise) pass
     through.  Every argument error comes before any GPU work."""
     _prediction(kw.get("prediction", "eps"))
-    _clip_denoised(kw.get("clip_denoised"))
+    _dynamic_threshold(kw.get("dynamic_threshold"), _clip_denoised(kw.get("clip_denoised")))
     if kw.get("guidance_scale") is not None:
         _guidance_scale(noise_model, kw["guidance_scale"], y)   # an argument error comes before the schedule's
     if kw.get("noises") is not None:
@@ -621,7 +645,7 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
                 x_T: Optional[torch.Tensor] = None, noises=None, use_graph: bool = False,
                 philox_seed: Optional[int] = None, schedule: Optional[TimestepSchedule] = None,
                 guidance_scale: Optional[float] = None, prediction: str = "eps", clip_denoised=None,
-                known=None, mask=None):
+                known=None, mask=None, dynamic_threshold=None):
     """Reverse process, diffusion.py:254-276.
 
     Default (``x_T is None and noises is None``): the reference's RNG consumption -
@@ -671,9 +695,24 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
     conditional UNet runs its time path as launches instead of the table look-up (which reassociates one sum).
     ``ValueError``, before any GPU work of the chain, for one without the other, a shape that does not broadcast, a
     non-finite ``known``, a ``mask`` outside [0, 1] or NaN.
+    ``dynamic_threshold``: ``None`` (the code paths above, unchanged - every launch, table and allocation) or a quantile
+    q in (0, 1] - Imagen's dynamic thresholding (Saharia et al. 2022, 2.3): on the data range [lo, hi] of
+    ``clip_denoised`` (``None`` / ``False``: (-1, 1) here), with c its centre and h its half width, every step takes per
+    sample the q-quantile s of ``|x0 - c|`` (linear interpolation, as ``torch.quantile``), and where s > h clamps
+    ``x0 - c`` to [-s, s] and scales it by h / s instead of pinning it to the ends of the range; where s <= h it is the
+    static clamp.  The chain runs in x0 form (or the multistep form, whose history is the thresholded value) like a
+    clipped one, in the same three modes, guided, masked (the blend comes after the threshold), for either
+    ``prediction`` and every model: one selection launch (``tdx_x0_dyn_threshold``) before the update
+    (``tdx_p_sample_update_dyn``), in the device-counter mode both behind ``tdx_unet_eval_step_update_dyn`` - the update
+    cannot run in final_conv's epilogue, since a sample's bound needs the whole output.  The (n, 2) buffer of bounds is
+    allocated once per call, outside every capture.  The returned sample lies in [lo, hi] exactly.  ``ValueError``,
+    before any GPU work, for a bool, a NaN, a q outside (0, 1] or an infinite bound.
     """
     prediction = _prediction(prediction)
     clip = _clip_denoised(clip_denoised)
+    dyn = _dynamic_threshold(dynamic_threshold, clip)
+    if dyn is not None:   # a thresholded chain runs in x0 form on its data range
+        clip = dyn[1]
     ms = isinstance(schedule, MultistepSchedule)
     if ms and noises is not None:
         raise ValueError("a multistep chain is deterministic: it takes no noises")
@@ -736,10 +775,29 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
         v.to(device).expand(n_samples, *shape).contiguous() for v in km)
 
     form = _lib.STEP_MS if ms else _lib.STEP_EPS if clip is None else _lib.STEP_X0
+    # Dynamic thresholding: the quantile's place among the sorted elements of one sample, and the (n, 2) buffer of
+    # bounds the selection kernel writes and the update reads - allocated here, outside every capture.
+    per = x[0].numel()
+    dyn_args = None if dyn is None else _quantile_rank(dyn[0], per) + (
+        torch.empty(n_samples, 2, dtype=torch.float32, device=device),)
+
+    def update_dyn(eps, z):
+        """``update`` with the thresholded clamp: the bounds of this step's x and eps, then the update that reads them."""
+        rank, frac, thr = dyn_args
+        check(lib.tdx_x0_dyn_threshold(x.data_ptr(), eps.data_ptr(), n_samples, per, coef.data_ptr(), t_idx.data_ptr(),
+                                       int(guided), w if guided else 0.0, lo, hi, rank, frac, thr.data_ptr(), st()),
+              "tdx_x0_dyn_threshold")
+        check(lib.tdx_p_sample_update_dyn(x.data_ptr(), x.data_ptr(), eps.data_ptr(), half if guided else x.numel(),
+                                          form, coef.data_ptr(), t_idx.data_ptr(), _lib.ptr(tau), None if ms else z,
+                                          int(philox_seed is not None), philox_seed or 0, int(guided),
+                                          w if guided else 0.0, lo, hi, _lib.ptr(hist), _lib.ptr(kn), _lib.ptr(mk), None,
+                                          thr.data_ptr(), per, st()), "tdx_p_sample_update_dyn")
 
     def update(eps, z):
         """x <- step(x, eps, z | hist), elementwise and in place (tdx_p_sample_update: the table's form, guided or
         not, masked or not); Philox noise in the kernel under a seed, none on a multistep chain."""
+        if dyn_args is not None:
+            return update_dyn(eps, z)
         check(lib.tdx_p_sample_update(x.data_ptr(), x.data_ptr(), eps.data_ptr(), half if guided else x.numel(), form,
                                       coef.data_ptr(), t_idx.data_ptr(), _lib.ptr(tau), None if ms else z,
                                       int(philox_seed is not None), philox_seed or 0, int(guided), w if guided else 0.0,
@@ -789,6 +847,8 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
                     if one_call:  # step counter + eps_theta + update behind one C-ABI entry
                         # (the two keywords only on a masked chain: an unmasked one makes the call it always made)
                         mkw = {} if kn is None else {"known": kn, "mask": mk}
+                        if dyn_args is not None:
+                            mkw["dyn"] = dyn_args
                         noise_model._run_eval_step(x, y_dev, coef, counter, t_idx, t_vec, eps_buf,
                                                    philox_seed=philox_seed, tau=tau, S=S, guidance_scale=w,
                                                    clip=clip, hist=hist, **mkw)

@@ -552,7 +552,7 @@ class NoiseModelBase(nn.Module):
 
     def _run_eval_step(self, x, y, coef, counter, t_idx, t_vec, eps, z=None, philox_seed: int = 0, tau=None,
                        S: int = 0, guidance_scale: Optional[float] = None, clip=None, hist=None, known=None,
-                       mask=None):
+                       mask=None, dyn=None):
         """One reverse step of sample() in place on ``x``: the step index is read from and decremented in device
         memory, so the call can sit in a HIP graph.  Nothing but ``z`` / ``philox_seed``: tdx_unet_eval_step, the
         reference's chain with ``coef`` its (T,3) table.  Anything else: tdx_unet_eval_step_update.  ``tau``: the device
@@ -561,7 +561,11 @@ class NoiseModelBase(nn.Module):
         x0 form, ``coef`` the (S,5) table of ``TimestepSchedule.x0_form``; with ``hist`` the multistep form against that
         history buffer, ``coef`` the (S,5) table of ``MultistepSchedule.multistep_form`` (no ``z``, no seed).
         ``known`` / ``mask`` (with ``clip``; both or neither): the masked step of inpainting - contiguous fp32 device
-        tensors of n rows."""
+        tensors of n rows.  ``dyn=(rank, frac, thr)`` (with a finite ``clip``, the data range): dynamic thresholding -
+        the quantile as ``schedule._quantile_rank`` gives it and the caller's (n, 2) fp32 device buffer; the step is
+        tdx_unet_eval_step_update_dyn (no fused epilogue)."""
+        if dyn is not None and clip is None:
+            raise ValueError("the thresholded step runs in x0 form: give clip, the data range")
         if (known is None) != (mask is None):
             raise ValueError("known and mask go together")
         if known is not None and clip is None:
@@ -572,7 +576,17 @@ class NoiseModelBase(nn.Module):
         lo, hi = (0.0, 0.0) if clip is None else (float(clip[0]), float(clip[1]))
         if form == _lib.STEP_MS:
             z, philox_seed = None, 0
-        if form == _lib.STEP_EPS and not g and tau is None:
+        if dyn is not None:
+            rank, frac, thr = dyn
+            check(lib.tdx_unet_eval_step_update_dyn(plan.handle, pptr, bptr, x.data_ptr(), _dptr(y), _dptr(z),
+                                                    coef.data_ptr(), _dptr(tau), int(S), counter.data_ptr(),
+                                                    t_idx.data_ptr(), t_vec.data_ptr(), eps.data_ptr(),
+                                                    x.numel() // 2 if g else x.numel(), plan.workspace.data_ptr(),
+                                                    plan.ws_bytes, x.shape[0], philox_seed, form, int(g),
+                                                    float(guidance_scale) if g else 0.0, lo, hi, _dptr(hist),
+                                                    _dptr(known), _dptr(mask), int(rank), float(frac), thr.data_ptr(),
+                                                    st), "tdx_unet_eval_step_update_dyn")
+        elif form == _lib.STEP_EPS and not g and tau is None:
             check(lib.tdx_unet_eval_step(plan.handle, pptr, bptr, x.data_ptr(), _dptr(y), _dptr(z), coef.data_ptr(),
                                          counter.data_ptr(), t_idx.data_ptr(), t_vec.data_ptr(), eps.data_ptr(),
                                          x.numel(), plan.workspace.data_ptr(), plan.ws_bytes, x.shape[0], philox_seed,
