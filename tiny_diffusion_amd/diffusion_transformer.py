@@ -12,9 +12,7 @@ the reference's names (``nn.MultiheadAttention.in_proj_weight`` etc.) and give t
 default initialisation; their torch ``forward`` is never called."""
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
-import math
 from typing import Optional, Tuple
 
 import torch
@@ -22,10 +20,10 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import check, lib
-from .schedule import (ForwardProcess, _prediction, _snr_gamma, ddim_sample_loop, dpm_sample_loop, loss_weights,
-                       sample_loop)
-from .train import cosine_annealing_lr, ema_decay_at
-from .vae import VAE, VAEConfig, _f32, _number
+from ._flat_step import (FlatStep, _betas_arg, _ema_args, _max_grad_norm_arg, _number, _seed_arg, cosine_annealing_lr,
+                         ema_decay_at)
+from .schedule import ForwardProcess, ddim_sample_loop, dpm_sample_loop, sample_loop
+from .vae import VAE, VAEConfig
 
 __all__ = ["TransformerBlock", "NoiseModel", "ForwardProcess", "sample", "ddim_sample", "dpm_sample", "VAE", "VAEConfig",
            "TransformerTrainStep", "cosine_annealing_lr", "ema_decay_at"]
@@ -179,18 +177,12 @@ class _TShape(C.Structure):
                 ("num_layers", C.c_int), ("num_classes", C.c_int), ("dropout_p", C.c_float), ("ln_eps", C.c_float)]
 
 
-def _seed_arg(v, what):
-    if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 64):
-        raise ValueError(f"{what} must be None or an integer in [0, 2**64)")
-    return v
-
-
 def _i64(v: int) -> int:
     """A uint64 as the int64 with the same bits (torch has no uint64 arithmetic; the kernels read the words as uint64)."""
     return v - 2 ** 64 if v >= 2 ** 63 else v
 
 
-class TransformerTrainStep:
+class TransformerTrainStep(FlatStep):
     """The optimisation step of the transformer's training loop (diffusion_transformer.py:193-202: ``randint``,
     ``q_sample``, forward, ``F.mse_loss``, ``zero_grad``, ``backward``, ``optimizer.step``) as one short chain of libtdx
     launches with no autograd graph:
@@ -202,16 +194,13 @@ class TransformerTrainStep:
                 loss = step.step(z_0, labels)                          # device tensor, not synchronised
             model.eval(); val = step.evaluate(z_0, labels); model.train()
 
-    ``tdx_transformer_loss_grads`` runs forward, loss and backward (csrc/transformer.hip); the parameters become views
-    of one flat fp32 buffer in ``state_dict()`` order with the gradient, Adam's two moments and the optional average
-    beside it, so the optimizer is one ``tdx_adam_step*`` / ``tdx_adam_ema_step*`` launch (``max_grad_norm``:
-    ``clip_grad_norm_`` fused into it).  ``state_dict()`` / ``load_state_dict()`` of the module keep working (in-place
-    copies land in the flat buffer); moving the module afterwards (``.to``, ``.cpu``) detaches it and the next call raises.
-
-    ``prediction`` / ``loss_weighting`` / ``snr_gamma`` / ``set_objective`` and ``ema_decay`` / ``ema_warmup`` /
-    ``ema_weights()`` / ``ema_state_dict()`` / ``load_ema_state_dict()`` / ``reset_ema()`` behave as in
-    ``train.TrainStep``.  ``lr`` is a plain attribute read at every step (a captured step reads it through its device
-    scalars).
+    ``tdx_transformer_loss_grads`` runs forward, loss and backward (csrc/transformer.hip) on the parameters in
+    ``state_dict()`` order; the flat buffers, the one optimizer launch (``max_grad_norm``: ``clip_grad_norm_`` fused into
+    it), the objective (``prediction`` / ``loss_weighting`` / ``snr_gamma`` / ``set_objective``), the average
+    (``ema_decay`` / ``ema_warmup`` / ``ema_weights()`` ...) and the capture protocol are ``_flat_step.FlatStep``'s and
+    behave as in ``train.TrainStep``.  ``state_dict()`` / ``load_state_dict()`` of the module keep working (in-place
+    copies land in the flat buffer); moving the module afterwards (``.to``, ``.cpu``) detaches it and the next call
+    raises.  ``lr`` is a plain attribute read at every step (a captured step reads it through its device scalars).
 
     Noise: ``noise`` given - used; else with ``philox_seed`` drawn in the q_sample kernel, keyed by ``(philox_seed,
     step_count)``; else ``torch.randn_like``.  ``t=None`` draws ``torch.randint`` on the device as the reference does.
@@ -238,26 +227,11 @@ class TransformerTrainStep:
             raise ValueError("TransformerTrainStep needs a diffusion_transformer.NoiseModel")
         if not isinstance(diffusion, ForwardProcess):
             raise ValueError("diffusion must be a ForwardProcess")
-        self.lr = _number(lr, "lr")
-        if not isinstance(betas, (tuple, list)) or len(betas) != 2:
-            raise ValueError("betas must be a pair of numbers")
-        self.betas = (_number(betas[0], "betas[0]"), _number(betas[1], "betas[1]"))
-        if not (0.0 <= self.betas[0] < 1.0 and 0.0 <= self.betas[1] < 1.0):
-            raise ValueError("betas must lie in [0, 1)")
-        self.eps = _number(eps, "eps")
-        if max_grad_norm is not None and not _number(max_grad_norm, "max_grad_norm") > 0:
-            raise ValueError("max_grad_norm must be None or > 0")
-        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        lr, betas, eps = _number(lr, "lr"), _betas_arg(betas), _number(eps, "eps")
+        max_grad_norm = _max_grad_norm_arg(max_grad_norm)
         self.model, self.diffusion = model, diffusion
-        self._w_table = None
         self._check_objective(prediction, loss_weighting, snr_gamma)
-        if ema_decay is None:
-            if ema_warmup:
-                raise ValueError("ema_warmup=True needs an ema_decay")
-        elif isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 <= ema_decay <= 1.0:
-            raise ValueError("ema_decay must be None or a number in [0, 1]")
-        self.ema_decay = None if ema_decay is None else float(ema_decay)
-        self.ema_warmup = bool(ema_warmup)
+        self._init_optimizer(lr, betas, eps, max_grad_norm, *_ema_args(ema_decay, ema_warmup), use_graph=bool(use_graph))
         self.philox_seed = _seed_arg(philox_seed, "philox_seed")
         self.dropout_seed = _seed_arg(dropout_seed, "dropout_seed")
         blocks = list(model.transformer_blocks)
@@ -274,89 +248,21 @@ class TransformerTrainStep:
         self.num_layers, self.num_heads = len(blocks), int(heads.pop())
         self.num_classes = int(model.class_embedding.num_embeddings)
         self._ln_eps = epss.pop()
-        self.use_graph = bool(use_graph)
-        self.step_count = 0
-        self.ema = None
-        self._ema_swapped = False
         self.last_dropout_seed = self.last_dropout_offset = None
         # ---- device work from here on
-        self._flatten()
-        dev = self.device
-        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._ws = {}            # batch size -> workspace of tdx_transformer_loss_grads
-        self._clip_scratch = None
-        self._graph = self._graph_key = self._hyper = self._grng = None
-        self._gz = self._gy = self._gt = self._gnoise = None
-        self._gws = None         # the workspace whose address the captured graph holds: owned by the graph's owner
+        named = self._params()
+        if len(named) != 12 + 12 * self.num_layers:
+            raise ValueError("unexpected parameter list: the fused step knows NoiseModel's 12 + 12 L tensors")
+        self._require_fp32_cuda(named, "the model's")
+        self._flatten(named)
+        self._upload_weights()
+        self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._gz = self._gy = self._gt = self._gnoise = self._grng = None
 
     # ------------------------------------------------------------------ setup
     def _params(self):
         named = dict(self.model.named_parameters())
         return [(k, named[k]) for k in self.model.state_dict().keys()]
-
-    def _flatten(self):
-        named = self._params()
-        if len(named) != 12 + 12 * self.num_layers:
-            raise ValueError("unexpected parameter list: the fused step knows NoiseModel's 12 + 12 L tensors")
-        dev = named[0][1].device
-        for k, p in named:
-            if p.device.type != "cuda" or p.device != dev or p.dtype != torch.float32:
-                raise _lib.TdxError("TransformerTrainStep needs the model's fp32 parameters on one CUDA (ROCm) device "
-                                    f"(call .to('cuda') first): {k} is {p.dtype} on {p.device}")
-        self.device = dev
-        total = sum(p.numel() for _, p in named)
-        flat = torch.empty(total, dtype=torch.float32, device=dev)
-        self.flat_grad = torch.zeros_like(flat)
-        self.offsets, self.grad_views = {}, {}
-        o = 0
-        for k, p in named:
-            n = p.numel()
-            flat[o:o + n].copy_(p.detach().reshape(-1))
-            p.data = flat[o:o + n].view(p.shape)      # parameters become views of the flat buffer
-            self.grad_views[k] = self.flat_grad[o:o + n].view(p.shape)
-            self.offsets[k] = (o, o + n)
-            o += n
-        self.flat_param = flat
-        self.exp_avg = torch.zeros_like(flat)
-        self.exp_avg_sq = torch.zeros_like(flat)
-        if self.ema_decay is not None:
-            self.ema = flat.clone()
-        base, gbase = flat.data_ptr(), self.flat_grad.data_ptr()
-        n = len(named)
-        self._p_ptrs = (C.c_void_p * n)(*[base + 4 * self.offsets[k][0] for k, _ in named])
-        self._g_ptrs = (C.c_void_p * n)(*[gbase + 4 * self.offsets[k][0] for k, _ in named])
-        self._upload_weights()
-
-    def _check_attached(self):
-        for (k, p), want in zip(self._params(), self._p_ptrs):
-            if p.data_ptr() != want:
-                raise _lib.TdxError(f"{k} no longer lives in TransformerTrainStep's flat parameter buffer: the module was "
-                                    "moved or its parameters were replaced after the step was built (build a new one)")
-
-    # -------------------------------------------------------------- objective
-    def _check_objective(self, prediction, loss_weighting, snr_gamma):
-        prediction, gamma = _prediction(prediction), _snr_gamma(snr_gamma)
-        w_cpu = None if loss_weighting is None else loss_weights(self.diffusion, prediction, loss_weighting, gamma)
-        named = loss_weighting is None or isinstance(loss_weighting, str)
-        self.prediction, self.snr_gamma = prediction, gamma
-        self.loss_weighting = loss_weighting if named else "table"
-        self._w_cpu = None if named else w_cpu
-
-    def _upload_weights(self):
-        if self.loss_weighting is None:
-            self._w_table = None
-        elif self._w_cpu is not None:
-            self._w_table = self._w_cpu.to(self.device)
-        else:
-            self._w_table = self.diffusion.loss_weight_table(self.device, self.prediction, self.loss_weighting,
-                                                             self.snr_gamma)
-
-    def set_objective(self, prediction: str = "eps", loss_weighting=None, snr_gamma: float = 5.0):
-        """Change the training objective of an existing step (the constructor's three keywords, same errors): parameters
-        and optimizer state stay; a captured step is dropped and captured again on the next calls."""
-        self._check_objective(prediction, loss_weighting, snr_gamma)
-        self._upload_weights()
-        self._graph = self._graph_key = self._gws = None
 
     # ------------------------------------------------------------- validation
     def _check_batch(self, z_0, y, t, noise):
@@ -386,17 +292,12 @@ class TransformerTrainStep:
         m = self.model
         return _TShape(B, m.latent_dim, m.time_dim, self.num_heads, self.num_layers, self.num_classes, self.p, self._ln_eps)
 
-    def _workspace(self, B):
-        ws = self._ws.get(B)
-        if ws is None:
-            n = lib.tdx_transformer_train_workspace_floats(C.byref(self._shape(B)))
-            if n == 0:
-                raise _lib.TdxError("tdx_transformer_train_workspace_floats: shape not covered (dim % 64, dim <= 1024, "
-                                    "dim % num_heads)")
-            if len(self._ws) >= 4:   # small cache; the workspace a captured graph replays into is never evicted
-                self._ws = {k: v for k, v in self._ws.items() if v is self._gws}
-            ws = self._ws[B] = torch.empty(n, dtype=torch.float32, device=self.device)
-        return ws
+    def _workspace_floats(self, B):
+        n = lib.tdx_transformer_train_workspace_floats(C.byref(self._shape(B)))
+        if n == 0:
+            raise _lib.TdxError("tdx_transformer_train_workspace_floats: shape not covered (dim % 64, dim <= 1024, "
+                                "dim % num_heads)")
+        return n
 
     def _next_rng(self):
         """(seed, offset) of the dropout masks of the step about to run (see the class docstring)."""
@@ -404,17 +305,6 @@ class TransformerTrainStep:
             return self.dropout_seed, self.step_count * 4 * self.num_layers
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.model.training else 0   # NoiseModel._rng_factory
         return seed, 0
-
-    def _q_sample(self, z_0, t, noise):
-        """(z_t, target) from the existing forward-process entries."""
-        fp, dev = self.diffusion, self.device
-        if self.prediction != "eps":
-            if noise is None and self.philox_seed is not None:
-                return fp.q_sample_target_philox(z_0, t, self.philox_seed, self.step_count, self.prediction)
-            return fp.q_sample_target(dev, z_0, t, noise=noise, prediction=self.prediction)
-        if noise is None and self.philox_seed is not None:
-            return fp.q_sample_philox(z_0, t, self.philox_seed, self.step_count)
-        return fp.q_sample(dev, z_0, t, noise=noise)
 
     def _loss_grads(self, z_t, t, y, target, B, loss, grads: bool, train: bool, rng, rng_dev=None, eps_hat=None):
         st = torch.cuda.current_stream(self.device).cuda_stream
@@ -426,51 +316,10 @@ class TransformerTrainStep:
                                              None if eps_hat is None else eps_hat.data_ptr(),
                                              self._workspace(B).data_ptr(), st), "tdx_transformer_loss_grads")
 
-    def _ema_a(self) -> float:
-        return 1.0 - ema_decay_at(self.step_count - 1, self.ema_decay, self.ema_warmup)
-
-    def _adam_hyper(self):
-        """{lr / bc1, 1 / sqrt(bc2), grad_scale[, 1 - decay]} of the step ``step_count`` counts, with tdx_adam_step's
-        own arithmetic (fp32 arguments widened to double), so a captured step and an eager one update bit-identically."""
-        b1, b2 = _f32(self.betas[0]), _f32(self.betas[1])
-        bc1, bc2 = 1.0 - math.pow(b1, self.step_count), 1.0 - math.pow(b2, self.step_count)
-        hyper = [_f32(self.lr) / bc1, 1.0 / math.sqrt(bc2), 1.0]
-        return hyper if self.ema is None else hyper + [self._ema_a()]
-
-    def _adam(self, hyper=None):
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        bufs = [self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr()]
-        n = self.flat_param.numel()
-        b1, b2 = self.betas
-        hyp = None if hyper is None else hyper.data_ptr()
-        if self.ema is not None:
-            bufs.append(self.ema.data_ptr())
-        if self.max_grad_norm is not None:
-            if self._clip_scratch is None:
-                self._clip_scratch = torch.empty(lib.tdx_adam_clip_scratch_bytes(), dtype=torch.uint8, device=self.device)
-            if self.ema is not None:
-                check(lib.tdx_adam_ema_step_clip(*bufs, n, self.lr, b1, b2, self.eps, self.step_count, 1.0,
-                                                 self.max_grad_norm, self._ema_a(), hyp, self._clip_scratch.data_ptr(), st),
-                      "tdx_adam_ema_step_clip")
-            else:
-                check(lib.tdx_adam_step_clip(*bufs, n, self.lr, b1, b2, self.eps, self.step_count, 1.0,
-                                             self.max_grad_norm, hyp, self._clip_scratch.data_ptr(), st),
-                      "tdx_adam_step_clip")
-        elif hyper is not None:
-            if self.ema is not None:
-                check(lib.tdx_adam_ema_step_dev(*bufs, n, hyp, b1, b2, self.eps, st), "tdx_adam_ema_step_dev")
-            else:
-                check(lib.tdx_adam_step_dev(*bufs, n, hyp, b1, b2, self.eps, st), "tdx_adam_step_dev")
-        elif self.ema is not None:
-            check(lib.tdx_adam_ema_step(*bufs, n, self.lr, b1, b2, self.eps, self.step_count, 1.0, self._ema_a(), st),
-                  "tdx_adam_ema_step")
-        else:
-            check(lib.tdx_adam_step(*bufs, n, self.lr, b1, b2, self.eps, self.step_count, 1.0, st), "tdx_adam_step")
-
     def _eager_step(self, z_0, y, t, noise, B, rng, hyper=None, rng_dev=None):
         if t is None:
             t = torch.randint(0, self.diffusion.num_timesteps, (B,), device=self.device)   # line 193
-        z_t, target = self._q_sample(z_0, t, noise)                                          # line 196
+        z_t, target = self._q_sample(z_0, t, noise, self.step_count)                         # line 196
         self._loss_grads(z_t, t, y, target, B, self.loss, True, self.model.training, rng, rng_dev)   # lines 197-201
         self.last_dropout_seed, self.last_dropout_offset = rng
         self.step_count += 1
@@ -490,34 +339,8 @@ class TransformerTrainStep:
         return self._eager_step(z_0, y, t, noise, B, self._next_rng())
 
     def _graph_step(self, z_0, y, t, noise, B):
-        dev, Ld = self.device, self.model.latent_dim
-        key = (B, self.model.training)
-        if key != self._graph_key:
-            if self._graph_key != ("warm",) + key:
-                # the first step with this batch size runs eagerly (workspace, first-launch set-up); the next captures
-                self._graph, self._gws, self._graph_key = None, None, ("warm",) + key
-                return self._eager_step(z_0, y, t, noise, B, self._next_rng())
-            self._gz = torch.empty(B, Ld, dtype=torch.float32, device=dev)
-            self._gnoise = torch.empty(B, Ld, dtype=torch.float32, device=dev)
-            self._gy = torch.empty(B, dtype=torch.int64, device=dev)
-            self._gt = torch.zeros(B, dtype=torch.int64, device=dev)
-            self._grng = torch.zeros(2, dtype=torch.int64, device=dev)
-            self._hyper = torch.zeros(3 if self.ema is None else 4, dtype=torch.float32, device=dev)
-            # the graph holds the workspace's raw address and replays never pass through _workspace(): keep it alive
-            # (and cached under B) for as long as the graph, whatever other batch sizes evaluate() / step() see
-            self._graph = None
-            self._gws = self._workspace(B)
-            if self.max_grad_norm is not None and self._clip_scratch is None:
-                self._clip_scratch = torch.empty(lib.tdx_adam_clip_scratch_bytes(), dtype=torch.uint8, device=dev)
-            self.diffusion.tables(dev)
-            keep = (self.last_dropout_seed, self.last_dropout_offset)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._eager_step(self._gz, self._gy, self._gt, self._gnoise, B, (0, 0), hyper=self._hyper,
-                                 rng_dev=self._grng)
-            self.step_count -= 1   # the capture ran the host bookkeeping once without executing anything
-            self.last_dropout_seed, self.last_dropout_offset = keep
-            self._graph, self._graph_key = g, key
+        if not self._graph_ready((B, self.model.training), B):   # the first step with this batch size: workspace, set-up
+            return self._eager_step(z_0, y, t, noise, B, self._next_rng())
         rng = self._next_rng()
         self._gz.copy_(z_0)
         self._gy.copy_(y)
@@ -531,10 +354,25 @@ class TransformerTrainStep:
             self._gnoise.copy_(noise)
         self._grng.copy_(torch.tensor([_i64(rng[0]), _i64(rng[1])], dtype=torch.int64))
         self.last_dropout_seed, self.last_dropout_offset = rng
-        self.step_count += 1
-        self._hyper.copy_(torch.tensor(self._adam_hyper(), dtype=torch.float32))
-        self._graph.replay()
-        return self.loss
+        return self._replay()
+
+    def _alloc_static(self, B):
+        dev, Ld = self.device, self.model.latent_dim
+        self._gz = torch.empty(B, Ld, dtype=torch.float32, device=dev)
+        self._gnoise = torch.empty(B, Ld, dtype=torch.float32, device=dev)
+        self._gy = torch.empty(B, dtype=torch.int64, device=dev)
+        self._gt = torch.zeros(B, dtype=torch.int64, device=dev)
+        self._grng = torch.zeros(2, dtype=torch.int64, device=dev)
+        # the graph holds the workspace's raw address and replays never pass through _workspace(): keep it alive
+        # (and cached under B) for as long as the graph, whatever other batch sizes evaluate() / step() see
+        self._gws = self._workspace(B)
+        self.diffusion.tables(dev)
+
+    def _static_step(self, hyper):
+        keep = (self.last_dropout_seed, self.last_dropout_offset)
+        self._eager_step(self._gz, self._gy, self._gt, self._gnoise, self._gz.shape[0], (0, 0), hyper=hyper,
+                         rng_dev=self._grng)
+        self.last_dropout_seed, self.last_dropout_offset = keep
 
     @torch.no_grad()
     def evaluate(self, z_0: torch.Tensor, y: torch.Tensor, t: Optional[torch.Tensor] = None,
@@ -546,55 +384,7 @@ class TransformerTrainStep:
         self._check_attached()
         if t is None:
             t = torch.randint(0, self.diffusion.num_timesteps, (B,), device=self.device)
-        z_t, target = self._q_sample(z_0, t, noise)
+        z_t, target = self._q_sample(z_0, t, noise, self.step_count)
         out = torch.empty(1, dtype=torch.float32, device=self.device)
         self._loss_grads(z_t, t, y, target, B, out, False, False, (0, 0))
         return out[0]
-
-    # -------------------------------------------------------------------- EMA
-    def _need_ema(self, what: str):
-        if self.ema is None:
-            raise RuntimeError(f"{what} needs TransformerTrainStep(ema_decay=...)")
-        if self._ema_swapped:
-            raise RuntimeError(f"{what} inside ema_weights(): the average and the parameters have traded places")
-
-    def reset_ema(self):
-        """The average starts again from the current parameters."""
-        self._need_ema("reset_ema()")
-        self.ema.copy_(self.flat_param)
-
-    def ema_state_dict(self):
-        """The model's ``state_dict()`` with the averaged parameters (clones of the slices of ``self.ema``)."""
-        self._need_ema("ema_state_dict()")
-        out = type(self.model.state_dict())()
-        for k, v in self.model.state_dict().items():
-            lo, hi = self.offsets[k]
-            out[k] = self.ema[lo:hi].view(v.shape).clone()
-        return out
-
-    def load_ema_state_dict(self, sd):
-        """Inverse of ``ema_state_dict()``."""
-        self._need_ema("load_ema_state_dict()")
-        for k, (lo, hi) in self.offsets.items():
-            if sd[k].numel() != hi - lo:
-                raise ValueError(f"{k}: {tuple(sd[k].shape)} does not fit the parameter's {hi - lo} elements")
-        for k, (lo, hi) in self.offsets.items():
-            self.ema[lo:hi].copy_(sd[k].detach().reshape(-1))
-
-    def _swap_ema(self):
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        check(lib.tdx_swap_f32(self.flat_param.data_ptr(), self.ema.data_ptr(), self.flat_param.numel(), st),
-              "tdx_swap_f32")
-        self._ema_swapped = not self._ema_swapped
-
-    @contextlib.contextmanager
-    def ema_weights(self):
-        """Inside the block the module IS the averaged model: one ``tdx_swap_f32`` launch exchanges ``flat_param`` and
-        ``ema`` on entry and again on exit (also when the body raises).  ``step()`` and a nested ``ema_weights()`` raise
-        inside."""
-        self._need_ema("ema_weights()")
-        self._swap_ema()
-        try:
-            yield self.model
-        finally:
-            self._swap_ema()

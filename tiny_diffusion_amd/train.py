@@ -22,15 +22,14 @@ statistics stay rank-local (DistributedDataParallel semantics).
 """
 from __future__ import annotations
 
-import contextlib
-import math
 import os
 from typing import List, Optional, Tuple
 
 import torch
 
+from ._flat_step import FlatStep, _ema_args, cosine_annealing_lr, ema_decay_at  # noqa: F401  (re-exported)
 from ._lib import lib, check
-from .schedule import ForwardProcess, _prediction, _snr_gamma, loss_weights
+from .schedule import ForwardProcess
 from .unet import KIND_LAION, KIND_MNIST, MODE_TRAIN, MODE_EVAL_GRAD, NoiseModelBase, _cond_tensor, backward_stage_params
 
 
@@ -96,26 +95,7 @@ class BucketedAllReduce:
         return 1.0 / self.world
 
 
-def cosine_annealing_lr(step: int, base_lr: float, T_max: int, eta_min: float = 0.0) -> float:
-    """Learning rate after ``step`` calls of ``CosineAnnealingLR(T_max, eta_min).step()``
-    (conditional_diffusion_laion.py:436-438, 473: stepped once per BATCH although T_max counts
-    epochs, so the rate swings between base_lr and eta_min with period 2*T_max batches -
-    reproduced as written; the closed form equals torch's chained recursion)."""
-    return eta_min + (base_lr - eta_min) * (1.0 + math.cos(math.pi * step / T_max)) / 2.0
-
-
-def ema_decay_at(step_index: int, decay: float, warmup: bool) -> float:
-    """Decay of the parameter average at optimizer step ``step_index`` (0 at the first one): ``decay``, or with
-    ``warmup`` ``min(decay, (1 + k) / (10 + k))`` - the average follows the parameters closely while they still move
-    fast (0.1 at the first step, 2/11 at the second) and reaches ``decay`` from the first k with
-    ``(1 + k) / (10 + k) >= decay`` on."""
-    if not warmup:
-        return decay
-    k = int(step_index)
-    return min(decay, (1 + k) / (10 + k))
-
-
-class TrainStep:
+class TrainStep(FlatStep):
     def __init__(self, model: NoiseModelBase, diffusion: ForwardProcess, lr: float = 1e-3,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  process_group=None, bucket_floats: int = 1 << 20, philox_seed: Optional[int] = None,
@@ -158,17 +138,10 @@ class TrainStep:
         effect at every forward)."""
         self.model = model
         self.diffusion = diffusion
-        self._w_table = None     # device (T,) fp32 loss weights; None: unweighted, the existing loss entry
-        self._check_objective(prediction, loss_weighting, snr_gamma)   # the table is uploaded by _flatten
-        if ema_decay is None:
-            if ema_warmup:
-                raise ValueError("ema_warmup=True needs an ema_decay")
-        elif isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 <= ema_decay <= 1.0:
-            raise ValueError("ema_decay must be None or a number in [0, 1]")
-        self.ema_decay = None if ema_decay is None else float(ema_decay)
-        self.ema_warmup = bool(ema_warmup)
-        self.ema = None          # flat average of flat_param (_flatten)
-        self._ema_swapped = False   # inside ema_weights(): flat_param holds the average, ema the parameters
+        self._check_objective(prediction, loss_weighting, snr_gamma)   # the table is uploaded after _flatten
+        # max_grad_norm: torch.nn.utils.clip_grad_norm_(parameters, max_norm) between backward and the
+        # optimizer step (conditional_diffusion_laion.py:469); None = no clipping (MNIST scripts)
+        self._init_optimizer(lr, betas, eps, max_grad_norm, *_ema_args(ema_decay, ema_warmup), use_graph=use_graph)
         if isinstance(cond_drop_prob, bool) or not isinstance(cond_drop_prob, (int, float)) \
                 or not 0.0 <= cond_drop_prob <= 1.0:
             raise ValueError("cond_drop_prob must be in [0, 1]")
@@ -178,14 +151,14 @@ class TrainStep:
         self.cond_drop_prob, self.cond_drop_seed = float(cond_drop_prob), int(cond_drop_seed)
         # CosineAnnealingLR(optimizer, T_max, eta_min) stepped after every optimizer step
         self.base_lr, self.cosine_T_max, self.cosine_eta_min = lr, cosine_T_max, cosine_eta_min
-        # torch.nn.utils.clip_grad_norm_(parameters, max_norm) between backward and the
-        # optimizer step (conditional_diffusion_laion.py:469); None = no clipping (MNIST scripts)
-        self.max_grad_norm = max_grad_norm
-        self.lr, self.betas, self.eps = lr, betas, eps
-        self.step_count = 0
         self.pg = process_group
         self.philox_seed = philox_seed
-        self._flatten()
+        named = self._params()
+        if named[0][1].device.type != "cuda":
+            raise RuntimeError("TrainStep needs the model on a CUDA (ROCm) device")
+        self._flatten(named, model._grad_buffers)
+        self._upload_weights()
+        self.n_stages = lib.tdx_unet_backward_stages()
         a = model._arch
         self.buckets = plan_buckets(self.offsets, model.num_classes > 0, bucket_floats, a.time_name, a.init_name,
                                     a.final_name)
@@ -213,76 +186,24 @@ class TrainStep:
         # decay does not freeze at its capture-time value).  Measured on MI355X it buys little: the small-batch steps
         # are bound by the GPU-side cost of ~100-170 tiny dependent kernels, not by host launches
         # (LAION B=8: 2.18 -> 2.05 ms/step; latent MLP B=128: 0.62 -> 0.68), so it is off by default.
-        self.use_graph = use_graph
         # (a captured step keeps the model's stream schedule: libtdx notices the capture and avoids the one
         # cross-helper-stream wait pattern that crashes hipStreamEndCapture on ROCm 7.2 - csrc/unet.hip,
         # tools/micro/capture_fork_probe.hip)
-        self._graph = None
-        self._graph_key = None
         self._graph_plan = None   # the plan whose workspace / packs / streams the captured graph refers to
         self._last_plan = None
-        self._hyper = None
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self._clip_scratch = None
         self._mse_scratch = None
 
-    # ------------------------------------------------------------------ setup
-    def _flatten(self):
-        m = self.model
-        named = dict(m.named_parameters())
-        order = m._param_order
-        dev = named[order[0]].device
-        if dev.type != "cuda":
-            raise RuntimeError("TrainStep needs the model on a CUDA (ROCm) device")
-        self.device = dev
-        total = sum(named[n].numel() for n in order)
-        flat = torch.empty(total, dtype=torch.float32, device=dev)
-        self.offsets = {}
-        o = 0
-        for n in order:
-            p = named[n]
-            k = p.numel()
-            flat[o:o + k].copy_(p.detach().reshape(-1))
-            p.data = flat[o:o + k].view(p.shape)   # parameters become views of the flat buffer
-            self.offsets[n] = (o, o + k)
-            o += k
-        self.flat_param = flat
-        self.flat_grad, self.grad_views = m._grad_buffers(dev)
-        self.exp_avg = torch.zeros_like(flat)
-        self.exp_avg_sq = torch.zeros_like(flat)
-        if self.ema_decay is not None:
-            self.ema = flat.clone()
-        self._upload_weights()
-        self.n_stages = lib.tdx_unet_backward_stages()
+    def _params(self):
+        named = dict(self.model.named_parameters())
+        return [(n, named[n]) for n in self.model._param_order]
 
-    # -------------------------------------------------------------- objective
-    def _check_objective(self, prediction, loss_weighting, snr_gamma):
-        """Validate and record the objective (``ValueError`` before anything changes).  What ``_eager_step`` reads of it:
-        ``self.prediction`` (which q_sample entry) and ``self._w_table`` (None: the unweighted loss entry)."""
-        prediction, gamma = _prediction(prediction), _snr_gamma(snr_gamma)
-        w_cpu = None if loss_weighting is None else loss_weights(self.diffusion, prediction, loss_weighting, gamma)
-        named = loss_weighting is None or isinstance(loss_weighting, str)
-        self.prediction, self.snr_gamma = prediction, gamma
-        self.loss_weighting = loss_weighting if named else "table"
-        self._w_cpu = None if named else w_cpu      # a user table, checked and rounded; named tables: the diffusion's
+    def _drop_graph(self):
+        super()._drop_graph()
+        self._graph_plan = None
 
-    def _upload_weights(self):
-        if self.loss_weighting is None:
-            self._w_table = None
-        elif self._w_cpu is not None:
-            self._w_table = self._w_cpu.to(self.device)
-        else:   # the diffusion's per-device copy, shared by every step on it
-            self._w_table = self.diffusion.loss_weight_table(self.device, self.prediction, self.loss_weighting,
-                                                             self.snr_gamma)
-
-    def set_objective(self, prediction: str = "eps", loss_weighting=None, snr_gamma: float = 5.0):
-        """Change the training objective of an existing step (the constructor's three keywords, same errors): the
-        parameters, optimizer state and plans stay; a captured step is dropped and captured again on the next calls,
-        because the graph holds the launches of the objective it was captured with.  The defaults give back exactly the
-        default step's launches (``tools/gpu_objective_cost.py`` alternates the two on one step)."""
-        self._check_objective(prediction, loss_weighting, snr_gamma)
-        self._upload_weights()
-        self._graph = self._graph_key = self._graph_plan = None
+    def _params_swapped(self):
+        self.model._buf_epoch += 1   # the packed inference weights of every plan are stale
 
     # ------------------------------------------------------------------- step
     def step(self, x_0: torch.Tensor, y: Optional[torch.Tensor] = None,
@@ -321,54 +242,36 @@ class TrainStep:
         same noise for their shards (the global batch would hold ``world`` copies of every eps)."""
         return self.step_count * self.world + self.rank
 
-    def _adam_hyper(self, gscale: float):
-        bc1 = 1.0 - self.betas[0] ** self.step_count
-        bc2 = 1.0 - self.betas[1] ** self.step_count
-        hyper = [self.lr / bc1, 1.0 / math.sqrt(bc2), gscale]
-        return hyper if self.ema is None else hyper + [self._ema_a()]
-
-    def _ema_a(self) -> float:
-        """1 - decay of the optimizer step that ``step_count`` (already incremented) counts, in double: the
-        conversion to the kernel's fp32 scalar is its one rounding."""
-        return 1.0 - ema_decay_at(self.step_count - 1, self.ema_decay, self.ema_warmup)
-
     def _graph_step(self, x_0, y):
         m = self.model
         dev = x_0.device
         if self.cond_drop_prob > 0.0 and y is not None:
             y = _cond_tensor(m._arch.kind, y.to(dev))   # the dtype the dropout kernel writes into _gy
         key = (tuple(x_0.shape), None if y is None else (tuple(y.shape), y.dtype), m.training)
-        if key != self._graph_key:
-            if self._graph_key is None or self._graph_key[1:] != ("warm",) + key:
-                # first step with these shapes runs eagerly (creates the plan, first-launch set-up);
-                # the next one captures
-                self._graph = self._graph_plan = None
-                self._graph_key = ("pending", "warm") + key
-                return self._eager_step(x_0, self._drop_cond(y), None, None)
-            self._gx0 = x_0.detach().clone().contiguous().float()
-            self._gy = None if y is None else y.detach().clone().contiguous()
-            self._hyper = torch.zeros(3 if self.ema is None else 4, dtype=torch.float32, device=dev)
-            # (a plan whose finalizer runs inside the capture is parked, not destroyed: unet._Plan.__del__)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._eager_step(self._gx0, self._gy, None, None, hyper=self._hyper)
-            self.step_count -= 1  # capture ran the host bookkeeping once without executing anything
-            # The graph holds raw pointers into the plan (workspace, weight packs, helper streams and events) and
-            # replays never pass through NoiseModelBase._plan(), so the module's LRU would age the plan out and
-            # destroy it under the graph: the graph's owner keeps it alive (an evicted plan is only destroyed
-            # when its last reference goes).
-            self._graph, self._graph_key, self._graph_plan = g, key, self._last_plan
+        if not self._graph_ready(key, x_0, y):   # first step with these shapes: creates the plan, first-launch set-up
+            return self._eager_step(x_0, self._drop_cond(y), None, None)
         self._gx0.copy_(x_0)
         if y is not None:
             self._gy.copy_(y)
             self._drop_cond(self._gy, out=self._gy)   # before the replay: the captured graph reads _gy as it always did
-        self.step_count += 1
-        self._hyper.copy_(torch.tensor(self._adam_hyper(1.0), dtype=torch.float32))
-        self._graph.replay()
+        self._replay()
         m._buf_epoch += 1  # BN running statistics changed on the device (invalidates inference packs)
         if self.cosine_T_max is not None:
             self.lr = cosine_annealing_lr(self.step_count, self.base_lr, self.cosine_T_max, self.cosine_eta_min)
         return self.loss
+
+    def _alloc_static(self, x_0, y):
+        self._gx0 = x_0.detach().clone().contiguous().float()
+        self._gy = None if y is None else y.detach().clone().contiguous()
+
+    def _static_step(self, hyper):
+        # (a plan whose finalizer runs inside the capture is parked, not destroyed: unet._Plan.__del__)
+        self._eager_step(self._gx0, self._gy, None, None, hyper=hyper)
+        # The graph holds raw pointers into the plan (workspace, weight packs, helper streams and events) and
+        # replays never pass through NoiseModelBase._plan(), so the module's LRU would age the plan out and
+        # destroy it under the graph: the graph's owner keeps it alive (an evicted plan is only destroyed
+        # when its last reference goes).
+        self._graph_plan = self._last_plan
 
     def _eager_step(self, x_0, y, t, noise, hyper=None):
         m, fp = self.model, self.diffusion
@@ -378,15 +281,7 @@ class TrainStep:
         if t is None:
             t = torch.randint(0, fp.num_timesteps, (B,), device=dev)          # diffusion.py:220-222
         # `noise` is the loss target from here on: the noise itself, or v (written by the same launch)
-        if self.prediction != "eps":
-            if noise is None and self.philox_seed is not None:
-                x_t, noise = fp.q_sample_target_philox(x_0, t, self.philox_seed, self._philox_offset(), self.prediction)
-            else:
-                x_t, noise = fp.q_sample_target(dev, x_0, t, noise=noise, prediction=self.prediction)
-        elif noise is None and self.philox_seed is not None:
-            x_t, noise = fp.q_sample_philox(x_0, t, self.philox_seed, self._philox_offset())
-        else:
-            x_t, noise = fp.q_sample(dev, x_0, t, noise=noise)                 # diffusion.py:225
+        x_t, noise = self._q_sample(x_0, t, noise, self._philox_offset())     # diffusion.py:225
         mode = MODE_TRAIN if m.training else MODE_EVAL_GRAD
         eps_hat, plan, _ = m._run_forward(x_t, t, y, mode=mode)               # diffusion.py:228
         self._last_plan = plan
@@ -457,47 +352,11 @@ class TrainStep:
             cur.wait_stream(self.comm)
         gscale = self.reducer.finish()
         self.step_count += 1
-        bufs = (self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr())
-        n = self.flat_param.numel()
-        if self.max_grad_norm is not None:
-            # clip_grad_norm_ fused into the optimizer pass (conditional_diffusion_laion.py:469-472): the
-            # flat buffer holds every gradient, so one sum of squares gives the total norm, and the
-            # Adam kernel applies the clip coefficient on the fly
-            if self._clip_scratch is None:
-                self._clip_scratch = torch.empty(lib.tdx_adam_clip_scratch_bytes(), dtype=torch.uint8, device=dev)
-            hyp = None if hyper is None else hyper.data_ptr()
-            if self.ema is not None:
-                check(lib.tdx_adam_ema_step_clip(*bufs, self.ema.data_ptr(), n, self.lr, self.betas[0], self.betas[1],
-                                                 self.eps, self.step_count, gscale, float(self.max_grad_norm),
-                                                 self._ema_a(), hyp, self._clip_scratch.data_ptr(), st),
-                      "tdx_adam_ema_step_clip")
-            else:
-                check(lib.tdx_adam_step_clip(*bufs, n, self.lr, self.betas[0], self.betas[1], self.eps, self.step_count,
-                                             gscale, float(self.max_grad_norm), hyp, self._clip_scratch.data_ptr(), st),
-                      "tdx_adam_step_clip")
-            m._buf_epoch += 1
-            if hyper is None and self.cosine_T_max is not None:
-                self.lr = cosine_annealing_lr(self.step_count, self.base_lr, self.cosine_T_max, self.cosine_eta_min)
-            return self.loss
-        if hyper is not None:  # being captured: scalars come from device memory at replay time
-            if self.ema is not None:
-                check(lib.tdx_adam_ema_step_dev(*bufs, self.ema.data_ptr(), n, hyper.data_ptr(), self.betas[0],
-                                                self.betas[1], self.eps, st), "tdx_adam_ema_step_dev")
-            else:
-                check(lib.tdx_adam_step_dev(*bufs, n, hyper.data_ptr(), self.betas[0], self.betas[1], self.eps, st),
-                      "tdx_adam_step_dev")
-            m._buf_epoch += 1
-            return self.loss
-        if self.ema is not None:
-            check(lib.tdx_adam_ema_step(*bufs, self.ema.data_ptr(), n, self.lr, self.betas[0], self.betas[1], self.eps,
-                                        self.step_count, gscale, self._ema_a(), st), "tdx_adam_ema_step")
-        else:
-            check(lib.tdx_adam_step(*bufs, n, self.lr, self.betas[0], self.betas[1], self.eps, self.step_count, gscale,
-                                    st), "tdx_adam_step")                      # diffusion.py:236
+        self._adam(hyper, gscale, st)                                          # diffusion.py:236
         # the kernel wrote the parameters through raw pointers (no torch version bump): packed
         # inference weights of every plan are stale now, whatever mode this step ran in
         m._buf_epoch += 1
-        if self.cosine_T_max is not None:
+        if hyper is None and self.cosine_T_max is not None:   # (a captured step: _graph_step, after each replay)
             self.lr = cosine_annealing_lr(self.step_count, self.base_lr, self.cosine_T_max, self.cosine_eta_min)
         return self.loss
 
@@ -516,62 +375,3 @@ class TrainStep:
                 torch.distributed.broadcast(self.ema, src, group=self.pg)
             for b in self.model.buffers():
                 torch.distributed.broadcast(b, src, group=self.pg)
-
-    # -------------------------------------------------------------------- EMA
-    def _need_ema(self, what: str):
-        if self.ema is None:
-            raise RuntimeError(f"{what} needs TrainStep(ema_decay=...)")
-        if self._ema_swapped:
-            raise RuntimeError(f"{what} inside ema_weights(): the average and the parameters have traded places")
-
-    def reset_ema(self):
-        """The average starts again from the current parameters (after loading a checkpoint into the model of a
-        step that already exists)."""
-        self._need_ema("reset_ema()")
-        self.ema.copy_(self.flat_param)
-
-    def ema_state_dict(self):
-        """The model's ``state_dict()`` with the averaged parameters: the same keys, clones of the slices of ``self.ema``
-        for the parameters and clones of the live BatchNorm buffers (running statistics are averages already, and
-        shared).  Loads into the reference's modules unchanged."""
-        self._need_ema("ema_state_dict()")
-        out = type(self.model.state_dict())()
-        for k, v in self.model.state_dict().items():
-            if k in self.offsets:
-                lo, hi = self.offsets[k]
-                out[k] = self.ema[lo:hi].view(v.shape).clone()
-            else:
-                out[k] = v.detach().clone()
-        return out
-
-    def load_ema_state_dict(self, sd):
-        """Inverse of ``ema_state_dict()`` for the parameter entries (buffers belong to the model)."""
-        self._need_ema("load_ema_state_dict()")
-        for k, (lo, hi) in self.offsets.items():
-            v = sd[k]
-            if v.numel() != hi - lo:
-                raise ValueError(f"{k}: {tuple(v.shape)} does not fit the parameter's {hi - lo} elements")
-        for k, (lo, hi) in self.offsets.items():
-            self.ema[lo:hi].copy_(sd[k].detach().reshape(-1))
-
-    def _swap_ema(self):
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        check(lib.tdx_swap_f32(self.flat_param.data_ptr(), self.ema.data_ptr(), self.flat_param.numel(), st),
-              "tdx_swap_f32")
-        # the launch went in: from here on the two buffers hold each other's contents.  Written through raw pointers,
-        # so the packed inference weights of every plan are stale
-        self._ema_swapped = not self._ema_swapped
-        self.model._buf_epoch += 1
-
-    @contextlib.contextmanager
-    def ema_weights(self):
-        """Inside the block the module IS the averaged model: one ``tdx_swap_f32`` launch exchanges the contents of
-        ``flat_param`` and ``ema`` on entry and again on exit (also when the body raises), so ``forward``, ``sample``,
-        ``ddim_sample``, guidance and ``state_dict()`` see the averaged weights, and no pointer that a plan or a
-        captured step holds changes.  ``step()`` and a nested ``ema_weights()`` raise inside."""
-        self._need_ema("ema_weights()")
-        self._swap_ema()     # flips _ema_swapped once its launch is in; nothing may come between it and the try
-        try:
-            yield self.model
-        finally:
-            self._swap_ema()

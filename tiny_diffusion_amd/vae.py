@@ -8,8 +8,6 @@ files) is not reproduced.  Unlike the reference module, importing this one has n
 from __future__ import annotations
 
 import ctypes as C
-import math
-import struct
 from dataclasses import dataclass
 from typing import Any, Optional, Tuple
 
@@ -17,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._flat_step import FlatStep, _betas_arg, _max_grad_norm_arg, _number, _seed_arg
 from ._lib import lib, check
 
 __all__ = ["VAE", "VAEConfig", "VAETrainStep"]
@@ -123,18 +122,7 @@ class VAE(nn.Module):
         return self.decode(z), mu, logvar
 
 
-def _f32(v: float) -> float:
-    """``v`` rounded to fp32, as a C ``float`` argument is: the host arithmetic below then repeats libtdx's."""
-    return struct.unpack("f", struct.pack("f", v))[0]
-
-
-def _number(v, what):
-    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
-        raise ValueError(f"{what} must be a finite number, got {v!r}")
-    return float(v)
-
-
-class VAETrainStep:
+class VAETrainStep(FlatStep):
     """The VAE's optimisation step (vae.py:110-115: ``zero_grad``, forward, ``loss_function``, ``backward``,
     ``optimizer.step``) as one chain of libtdx launches, no autograd graph:
 
@@ -144,16 +132,15 @@ class VAETrainStep:
 
     ``tdx_vae_loss_grads`` runs the forward (the last layer without its sigmoid), the BCE on the logits, the KLD and
     the backward of the five Linear layers; the loss is the reference's ``BCE + kld_weight * KLD``, sum-reduced
-    (``kld_weight=1``: vae.py:76).  The ten parameters become views of one flat fp32 buffer (``fc1.w fc1.b fc21.w
-    fc21.b fc22.w fc22.b fc3.w fc3.b fc4.w fc4.b``), with the gradient and the two Adam moments in three more, so the
-    optimizer is one ``tdx_adam_step*`` launch (``max_grad_norm``: ``clip_grad_norm_`` fused, ``tdx_adam_step_clip``).
-    ``state_dict()`` / ``load_state_dict()`` of the module keep working (in-place copies land in the flat buffer);
-    moving the module afterwards (``.to``, ``.cpu``) detaches it from the buffer and the next call raises.
+    (``kld_weight=1``: vae.py:76).  The ten parameters (``fc1.w fc1.b fc21.w fc21.b fc22.w fc22.b fc3.w fc3.b fc4.w
+    fc4.b``) live in ``_flat_step.FlatStep``'s flat buffers, which also owns the one optimizer launch (``max_grad_norm``:
+    ``clip_grad_norm_`` fused into it) and the capture protocol.  ``state_dict()`` / ``load_state_dict()`` of the module
+    keep working (in-place copies land in the flat buffer); moving the module afterwards (``.to``, ``.cpu``) detaches it
+    from the buffer and the next call raises.
 
     Noise: ``eps`` given - used; else with ``philox_seed`` drawn in the reparameterisation kernel, keyed by
-    ``(philox_seed, step_count)``; else ``torch.randn``.  ``use_graph=True``: the first step with a batch size runs
-    eagerly, the second is captured into a HIP graph, later ones replay it (inputs and noise copied into static
-    buffers, Adam's step-dependent scalars in a device tensor); with ``philox_seed`` the step stays eager.
+    ``(philox_seed, step_count)``; else ``torch.randn``.  ``use_graph=True``: inputs and noise are copied into static
+    buffers before each replay; with ``philox_seed`` the step stays eager.
 
     Not covered: data parallelism, EMA, the bf16 mode (fp32 only)."""
 
@@ -162,34 +149,19 @@ class VAETrainStep:
     def __init__(self, vae: "VAE", lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  kld_weight: float = 1.0, max_grad_norm: Optional[float] = None, philox_seed: Optional[int] = None,
                  use_graph: bool = False):
-        self.lr = _number(lr, "lr")
-        if not isinstance(betas, (tuple, list)) or len(betas) != 2:
-            raise ValueError("betas must be a pair of numbers")
-        self.betas = (_number(betas[0], "betas[0]"), _number(betas[1], "betas[1]"))
-        if not (0.0 <= self.betas[0] < 1.0 and 0.0 <= self.betas[1] < 1.0):
-            raise ValueError("betas must lie in [0, 1)")
-        self.eps = _number(eps, "eps")
+        lr, betas, eps = _number(lr, "lr"), _betas_arg(betas), _number(eps, "eps")
         self.kld_weight = _number(kld_weight, "kld_weight")
         if self.kld_weight < 0:
             raise ValueError("kld_weight must be >= 0")
-        if max_grad_norm is not None and not _number(max_grad_norm, "max_grad_norm") > 0:
-            raise ValueError("max_grad_norm must be None or > 0")
-        if philox_seed is not None and (isinstance(philox_seed, bool) or not isinstance(philox_seed, int)
-                                        or not 0 <= philox_seed < 2 ** 64):
-            raise ValueError("philox_seed must be None or an integer in [0, 2**64)")
-        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
-        self.philox_seed = philox_seed
-        self.use_graph = bool(use_graph)
+        self._init_optimizer(lr, betas, eps, _max_grad_norm_arg(max_grad_norm), use_graph=bool(use_graph))
+        self.philox_seed = _seed_arg(philox_seed, "philox_seed")
         self.vae = vae
-        self.step_count = 0
-        self._flatten()
-        dev = self.device
-        self._out = torch.zeros(3, dtype=torch.float32, device=dev)
+        named = self._params()
+        self._require_fp32_cuda(named, "the VAE's")
+        self._flatten(named)
+        self._out = torch.zeros(3, dtype=torch.float32, device=self.device)
         self.loss, self.bce, self.kld = self._out[0], self._out[1], self._out[2]
-        self._ws = {}             # batch size -> workspace of tdx_vae_loss_grads
-        self._clip_scratch = None
-        self._graph = self._graph_key = self._hyper = self._gx = self._geps = None
-        self._gws = None          # the workspace whose address the captured graph holds: owned by the graph's owner
+        self._gx = self._geps = None
 
     # ------------------------------------------------------------------ setup
     def _params(self):
@@ -198,39 +170,6 @@ class VAETrainStep:
             lin = getattr(self.vae, n)
             out += [(n + ".weight", lin.weight), (n + ".bias", lin.bias)]
         return out
-
-    def _flatten(self):
-        named = self._params()
-        dev = named[0][1].device
-        for k, p in named:
-            if p.device.type != "cuda" or p.device != dev or p.dtype != torch.float32:
-                raise _lib.TdxError("VAETrainStep needs the VAE's fp32 parameters on one CUDA (ROCm) device "
-                                    f"(call .to('cuda') first): {k} is {p.dtype} on {p.device}")
-        self.device = dev
-        total = sum(p.numel() for _, p in named)
-        flat = torch.empty(total, dtype=torch.float32, device=dev)
-        self.flat_grad = torch.zeros_like(flat)
-        self.offsets, self.grad_views = {}, {}
-        o = 0
-        for k, p in named:
-            n = p.numel()
-            flat[o:o + n].copy_(p.detach().reshape(-1))
-            p.data = flat[o:o + n].view(p.shape)      # parameters become views of the flat buffer
-            self.grad_views[k] = self.flat_grad[o:o + n].view(p.shape)
-            self.offsets[k] = (o, o + n)
-            o += n
-        self.flat_param = flat
-        self.exp_avg = torch.zeros_like(flat)
-        self.exp_avg_sq = torch.zeros_like(flat)
-        base, gbase = flat.data_ptr(), self.flat_grad.data_ptr()
-        self._p_ptrs = (C.c_void_p * 10)(*[base + 4 * self.offsets[k][0] for k, _ in named])
-        self._g_ptrs = (C.c_void_p * 10)(*[gbase + 4 * self.offsets[k][0] for k, _ in named])
-
-    def _check_attached(self):
-        for (k, p), want in zip(self._params(), self._p_ptrs):
-            if p.data_ptr() != want:
-                raise _lib.TdxError(f"{k} no longer lives in VAETrainStep's flat parameter buffer: the module was moved or "
-                                    "its parameters were replaced after the step was built (build a new VAETrainStep)")
 
     # ------------------------------------------------------------- validation
     @staticmethod
@@ -249,15 +188,9 @@ class VAETrainStep:
         return B, x, eps
 
     # ------------------------------------------------------------------- step
-    def _workspace(self, B):
-        ws = self._ws.get(B)
-        if ws is None:
-            c = self.vae.config
-            n = lib.tdx_vae_train_workspace_floats(B, c.input_dim, c.hidden_dim, c.latent_dim)
-            if len(self._ws) >= 4:   # small cache; the workspace a captured graph replays into is never evicted
-                self._ws = {k: v for k, v in self._ws.items() if v is self._gws}
-            ws = self._ws[B] = torch.empty(n, dtype=torch.float32, device=self.device)
-        return ws
+    def _workspace_floats(self, B):
+        c = self.vae.config
+        return lib.tdx_vae_train_workspace_floats(B, c.input_dim, c.hidden_dim, c.latent_dim)
 
     def _loss_grads(self, x, eps, B, out, grads: bool):
         c = self.vae.config
@@ -268,30 +201,6 @@ class VAETrainStep:
                                      None if eps is None else eps.data_ptr(), self.philox_seed or 0, self.step_count,
                                      self.kld_weight, 1.0, out.data_ptr(), self._workspace(B).data_ptr(), B,
                                      c.input_dim, c.hidden_dim, c.latent_dim, st), "tdx_vae_loss_grads")
-
-    def _adam_hyper(self):
-        """{lr / bc1, 1 / sqrt(bc2), grad_scale} of the step ``step_count`` counts, with tdx_adam_step's own arithmetic
-        (fp32 arguments widened to double), so a captured step and an eager one update bit-identically."""
-        b1, b2 = _f32(self.betas[0]), _f32(self.betas[1])
-        bc1, bc2 = 1.0 - math.pow(b1, self.step_count), 1.0 - math.pow(b2, self.step_count)
-        return [_f32(self.lr) / bc1, 1.0 / math.sqrt(bc2), 1.0]
-
-    def _adam(self, hyper=None):
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        bufs = (self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr())
-        n = self.flat_param.numel()
-        if self.max_grad_norm is not None:
-            if self._clip_scratch is None:
-                self._clip_scratch = torch.empty(lib.tdx_adam_clip_scratch_bytes(), dtype=torch.uint8, device=self.device)
-            check(lib.tdx_adam_step_clip(*bufs, n, self.lr, self.betas[0], self.betas[1], self.eps, self.step_count, 1.0,
-                                         self.max_grad_norm, None if hyper is None else hyper.data_ptr(),
-                                         self._clip_scratch.data_ptr(), st), "tdx_adam_step_clip")
-        elif hyper is not None:
-            check(lib.tdx_adam_step_dev(*bufs, n, hyper.data_ptr(), self.betas[0], self.betas[1], self.eps, st),
-                  "tdx_adam_step_dev")
-        else:
-            check(lib.tdx_adam_step(*bufs, n, self.lr, self.betas[0], self.betas[1], self.eps, self.step_count, 1.0, st),
-                  "tdx_adam_step")
 
     def _eager_step(self, x, eps, B, hyper=None):
         self._loss_grads(x, eps, B, self._out, grads=True)      # vae.py:111-113
@@ -310,35 +219,25 @@ class VAETrainStep:
         return self._eager_step(x, eps, B)
 
     def _graph_step(self, x, eps, B):
-        c = self.vae.config
-        if B != self._graph_key:
-            if self._graph_key != ("warm", B):
-                # the first step with this batch size runs eagerly (workspace, first-launch set-up); the next captures
-                self._graph, self._gws, self._graph_key = None, None, ("warm", B)
-                return self._eager_step(x, eps, B)
-            self._gx = torch.empty(B, c.input_dim, dtype=torch.float32, device=self.device)
-            self._geps = torch.empty(B, c.latent_dim, dtype=torch.float32, device=self.device)
-            self._hyper = torch.zeros(3, dtype=torch.float32, device=self.device)
-            # the graph holds the workspace's raw address and replays never pass through _workspace(): keep it alive
-            # (and cached under B) for as long as the graph, whatever other batch sizes evaluate() / step() see
-            self._graph = None
-            self._gws = self._workspace(B)
-            if self.max_grad_norm is not None and self._clip_scratch is None:
-                self._clip_scratch = torch.empty(lib.tdx_adam_clip_scratch_bytes(), dtype=torch.uint8, device=self.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._eager_step(self._gx, self._geps, B, hyper=self._hyper)
-            self.step_count -= 1   # the capture ran the host bookkeeping once without executing anything
-            self._graph, self._graph_key = g, B
+        if not self._graph_ready((B,), B):   # the first step with this batch size: workspace, first-launch set-up
+            return self._eager_step(x, eps, B)
         self._gx.copy_(x)
         if eps is None:
             self._geps.normal_()     # outside the graph: torch's generator advances as in the eager step
         else:
             self._geps.copy_(eps)
-        self.step_count += 1
-        self._hyper.copy_(torch.tensor(self._adam_hyper(), dtype=torch.float32))
-        self._graph.replay()
-        return self.loss
+        return self._replay()
+
+    def _alloc_static(self, B):
+        c = self.vae.config
+        self._gx = torch.empty(B, c.input_dim, dtype=torch.float32, device=self.device)
+        self._geps = torch.empty(B, c.latent_dim, dtype=torch.float32, device=self.device)
+        # the graph holds the workspace's raw address and replays never pass through _workspace(): keep it alive
+        # (and cached under B) for as long as the graph, whatever other batch sizes evaluate() / step() see
+        self._gws = self._workspace(B)
+
+    def _static_step(self, hyper):
+        self._eager_step(self._gx, self._geps, self._gx.shape[0], hyper=hyper)
 
     @torch.no_grad()
     def evaluate(self, x: torch.Tensor, eps: Optional[torch.Tensor] = None):
