@@ -895,6 +895,10 @@ int tdx_unet_pack(tdx_unet* u, const void* const* params, void* const* buffers,
  * 1 128x128 | 2 128x64 | 3 64x64; "wgrad_target" workgroups aimed at by the wgrad pixel split;
  * "splitk" 0 | 1; the rest are listed in INTEGRATION.md.  An unknown key returns TDX_E_BADARG. */
 int tdx_tune_set(const char* key, int value);
+/* Additions within ABI 400: the value a key holds now (as tdx_tune_set normalised it; TDX_E_BADARG for a null or
+ * unknown key or a null `value`), and the index-th key of the table, NULL past its end. */
+int tdx_tune_get(const char* key, int* value);
+const char* tdx_tune_name(int index);
 
 /* Diagnostics (tools/gpu_clock_probe.py, ...): device buffer of `bytes` bytes that the instrumented
  * kernels (knob "conv_stamp") record into; NULL disables it.

@@ -133,7 +133,6 @@ def test_bf16_conv_fwd_dgrad_wgrad(tdx, B, H, cin, cout):
 IO16_VARIANTS = {"default": {}, "ring": {"bf16_ring": 1, "bf16_thin": 0}, "per_tap": {"bf16_wgrad9": 0},
                  "round2": {"bf16_wgrad9": 0, "bf16_wgrad_swz": 0}, "wgs256": {"wgrad9_wgs": 256},
                  "thin2": {"bf16_thin": 2}, "thin1": {"bf16_thin": 1}, "thin0": {"bf16_thin": 0}}
-IO16_KNOB_DEFAULTS = {"bf16_ring": 0, "bf16_wgrad9": 1, "bf16_wgrad_swz": 1, "wgrad9_wgs": 0, "bf16_thin": 3}
 IO16_CASES = [
     # B, H, cin, cout, in_bn: M % 256 == 0 (ring) and ragged M; 4x4 .. 64x64 maps (the padded-slot ring of the nine-tap
     # kernel: 64 slots span 2.5 samples at 4x4, its halo 4 blocks at 64x64); 64- and 128-wide tiles; BN+ReLU on load
@@ -181,9 +180,7 @@ def test_bf16_storage_kernels(tdx, variant, B, H, cin, cout, in_bn):
     osc, osh = torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g) * 0.3
     oscd, oshd = osc.cuda(), osh.cuda()
     dw = torch.empty((cout, cin, 3, 3), device="cuda")
-    try:
-        for k, v in knobs.items():
-            check(lib.tdx_tune_set(k.encode(), v))
+    with tdx.tuned(**knobs):
         splits = lib.tdx_conv3x3_wgrad_splits_bf16(B, H, H, cin, cout)   # (the split plan follows wgrad9_wgs)
         slabs = torch.full((splits, cout, 9, cin), float("nan"), device="cuda")
         check(lib.tdx_conv3x3_fwd_bf16_io(xin.data_ptr(), wf16.data_ptr(), bd.data_ptr(), out.data_ptr(), B, H, H, cin, cout,
@@ -198,9 +195,6 @@ def test_bf16_storage_kernels(tdx, variant, B, H, cin, cout, in_bn):
                                             1 if in_bn else 0, scp, shp, 1, st()))
         check(lib.tdx_conv3x3_wgrad_reduce(slabs.data_ptr(), dw.data_ptr(), splits, cout, cin, st()))
         torch.cuda.synchronize()
-    finally:
-        for k in knobs:
-            check(lib.tdx_tune_set(k.encode(), IO16_KNOB_DEFAULTS[k]))
     # outputs are rounded to bf16 once: 2^-9 relative per element at most
     assert torch.isfinite(out.float()).all() and torch.isfinite(gin.float()).all()
     assert rel_err(nchw(out.float()), ref.detach()) < 3e-3
@@ -289,12 +283,9 @@ def test_bf16_mnist_unet_against_fp32_golden(golden_dir, tdx, materialize):
     m.set_compute_dtype(torch.bfloat16)
     x_t, t, noise = torch.from_numpy(d["x_t"]), torch.from_numpy(d["t"]), torch.from_numpy(d["noise"])
     _, _, g32, _ = R.train_step_grads(sd, x_t, t, noise)
-    tdx.check(tdx.lib.tdx_tune_set(b"bf16_materialize", materialize))
-    try:
+    with tdx.tuned(bf16_materialize=materialize):
         _check_against_fp32(m, (x_t.cuda(), t.cuda()), noise, torch.from_numpy(d["eps_hat"]), float(d["loss"]), g32,
                             f"mnist B64 materialize={materialize}", AutocastYardstick("mnist_B64"))
-    finally:
-        tdx.check(tdx.lib.tdx_tune_set(b"bf16_materialize", 1))
     # and back: the same module in fp32 mode reproduces the fp32 vectors exactly as before
     m.set_compute_dtype(torch.float32)
     m.load_state_dict(sd)

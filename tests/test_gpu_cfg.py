@@ -18,7 +18,7 @@ from oracle import ref_laion as RLA  # noqa: E402
 from oracle.weights import make_state_dict, make_state_dict_laion  # noqa: E402
 from parity_helpers import gpu_pool_routing, gpu_relu_masks, grad_precision_failures, rel_mse  # noqa: E402
 
-from tiny_diffusion_amd._lib import check, lib  # noqa: E402
+from tiny_diffusion_amd._lib import check, lib, tuned  # noqa: E402
 from tiny_diffusion_amd.schedule import GRAPH_STEPS, ForwardProcess, ddim_schedule, sample_loop  # noqa: E402
 
 NUM_CLASSES = 10
@@ -31,10 +31,6 @@ def _amp(w):
     """How e = eps_u + w (eps_c - eps_u) = w eps_c + (1 - w) eps_u amplifies an error in either prediction
     (squared: the tolerances are mean squares)."""
     return (abs(w) + abs(w - 1.0)) ** 2
-
-
-def _tune(key, value):
-    check(lib.tdx_tune_set(key.encode(), value))
 
 
 def _model(kind, seed=0, time_dim=None):
@@ -390,11 +386,8 @@ def test_guided_fused_update_equals_separate_kernel(kind, bf16):
     sched = ddim_schedule(fp, steps=S, eta=0.5)
     kw = dict(x_T=x_T, schedule=sched, guidance_scale=2.5, use_graph=True, philox_seed=9)
     fused = sample_loop(m, fp, "cuda", n, y, **kw)
-    try:
-        _tune("sample_fuse", 2)
+    with tuned(sample_fuse=2):
         separate = sample_loop(m, fp, "cuda", n, y, **kw)
-    finally:
-        _tune("sample_fuse", 6)
     assert torch.isfinite(fused).all()
     assert torch.equal(fused, separate), rel_mse(fused, separate)
 

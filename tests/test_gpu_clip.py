@@ -20,7 +20,7 @@ from oracle.weights import (make_state_dict, make_state_dict_laion, make_state_d
 from inpaint_helpers import cpu_x0_step as _cpu_x0_step, spy_entries  # noqa: E402
 from parity_helpers import rel_mse  # noqa: E402
 
-from tiny_diffusion_amd._lib import check, lib  # noqa: E402
+from tiny_diffusion_amd._lib import check, lib, tuned  # noqa: E402
 from tiny_diffusion_amd.schedule import (GRAPH_STEPS, ForwardProcess, ddim_schedule, ddpm_schedule,  # noqa: E402
                                          sample_loop)
 
@@ -39,10 +39,6 @@ def _amp(w):
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
-
-
-def _tune(key, value):
-    check(lib.tdx_tune_set(key.encode(), value))
 
 
 def _model(kind, seed=0):
@@ -327,14 +323,10 @@ def test_clipped_fused_update_equals_separate_kernel(kind, w, bf16):
             t_idx = torch.empty(1, dtype=torch.int32, device="cuda")
             t_vec = torch.empty(rows, dtype=torch.int64, device="cuda")
             out = torch.empty_like(x)
-            try:
-                _tune("sample_fuse", 6 if fused else 2)
-                with torch.no_grad():
-                    m._run_eval_step(x, y2, coef, counter, t_idx, t_vec, out, z=z, philox_seed=9, tau=tau, S=S,
-                                     guidance_scale=w, clip=(-1.0, 1.0))
+            with tuned(sample_fuse=6 if fused else 2), torch.no_grad():
+                m._run_eval_step(x, y2, coef, counter, t_idx, t_vec, out, z=z, philox_seed=9, tau=tau, S=S,
+                                 guidance_scale=w, clip=(-1.0, 1.0))
                 torch.cuda.synchronize()
-            finally:
-                _tune("sample_fuse", 6)
             assert counter.item() == 0 and t_idx.item() == 1 and int(t_vec[-1]) == 700
             res[(z is None, fused)] = (x.clone(), out.clone())
         (xf, of), (xs, os_) = res[(z is None, True)], res[(z is None, False)]
@@ -416,11 +408,8 @@ def test_clipped_philox_graph_equals_eager(kind, w, prediction):
     kw = dict(x_T=x_T, schedule=sched, guidance_scale=w, prediction=prediction, clip_denoised=True, philox_seed=4)
     pe = sample_loop(m, fp, "cuda", n, y, **kw)
     pt = sample_loop(m, fp, "cuda", n, y, use_graph=True, **kw)
-    try:
-        _tune("sample_tables", 0)
+    with tuned(sample_tables=0):
         pg = sample_loop(m, fp, "cuda", n, y, use_graph=True, **kw)
-    finally:
-        _tune("sample_tables", 1)
     assert torch.isfinite(pe).all() and pe.min() >= -1 and pe.max() <= 1
     assert torch.equal(pg, pe)
     r = rel_mse(pt, pe)

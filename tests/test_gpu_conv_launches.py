@@ -154,15 +154,11 @@ def test_edge_launches(tdx):
         for role in ("fwd", "dgrad", "infer"):
             entries.append((B, H, cin, cin, cout, role, "wino", f"{tile_blocks(B, H)} tile blocks"))
     assert sorted({tile_blocks(e[0], e[1]) for e in entries}) == [63, 64, 65, 66]
-    default_target = 512
-    try:
-        tdx.check(lib.tdx_tune_set(b"wino_wgrad_target", 1))
+    with tdx.tuned(wino_wgrad_target=1):
         for B, H, cin, cout in ((11, 28, 64, 128), (70, 7, 64, 64)):
             nt = B * ((H + 1) // 2) ** 2
             assert lib.tdx_conv3x3_wgrad_wino_splits(B, H, H, cin, cout) == -(-nt // 1024) and nt % 1024
             entries.append((B, H, cin, cin, cout, "wgrad", "wino", f"{nt} tiles in chunks of 1024"))
         failures = run_table(tdx, entries)
-    finally:
-        tdx.check(lib.tdx_tune_set(b"wino_wgrad_target", default_target))
     assert lib.tdx_conv3x3_wgrad_wino_splits(256, 28, 28, 64, 128) == 251   # the default plan is back
     assert not failures, failures

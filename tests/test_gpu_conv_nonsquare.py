@@ -23,8 +23,6 @@ of the slot window's fit and of W <= 95 of the nine-tap weight gradient; BN + Re
 Boundary convolutions: (3,6,5), (2,9,4) at the minimal W, (2,4,9), (5,7,8); W = 3 refused by the backward entries and
 computed by the others; (33,40,50) = 129 partial rows -> the fold level; (66,40,50) = 8250 groups of 16 pixels > 8192
 and (263,40,50) = 4110 tiles of 128 pixels > 4096 -> the grid-stride wraps."""
-from contextlib import contextmanager
-
 import pytest
 import torch
 
@@ -36,8 +34,6 @@ from conv_helpers import (ELEM_DIRECT, ELEM_WINO, REL_DIRECT, REL_WINO, TDX_E_SH
 pytestmark = pytest.mark.gpu
 
 CIN, COUT = 64, 128
-KNOB_DEFAULTS = {"wino_rows": 1, "wino_rows_min_stages": 16, "conv_tile": 0, "infer_stages": 4, "bf16_wgrad9": 1,
-                 "bf16_thin": 3}
 SMALLP_W = 2368   # floats per partial row of the boundary weight gradients (csrc/edge_conv.hip)
 
 
@@ -47,17 +43,6 @@ def tdx():
 
     assert torch.cuda.is_available()
     return L
-
-
-@contextmanager
-def tuned(tdx, **knobs):
-    try:
-        for k, v in knobs.items():
-            tdx.check(tdx.lib.tdx_tune_set(k.encode(), v))
-        yield
-    finally:
-        for k in knobs:
-            tdx.check(tdx.lib.tdx_tune_set(k.encode(), KNOB_DEFAULTS[k]))
 
 
 def _id(s):
@@ -135,7 +120,7 @@ def test_wino_nonsquare(tdx, shape):
     o = Operands(B, H, CIN, CIN, COUT, seed, W=W, fenced=True)
     res = {}
     for rows in (0, 1):
-        with tuned(tdx, wino_rows=rows, wino_rows_min_stages=1):
+        with tdx.tuned(wino_rows=rows, wino_rows_min_stages=1):
             res[rows] = (_wino_fwd(tdx, o, 4, G), _wino_fwd(tdx, o, 0, G)[0], run_dgrad(tdx, o, "wino", G))
         torch.cuda.synchronize()
     (y_c, st_c), y0_c, g_c = res[0]
@@ -240,7 +225,7 @@ def test_direct_nonsquare(tdx, shape):
     tdx.check(lib.tdx_pack_conv3x3_tiled(p(o.w), p(wt), COUT, CIN, stream()))
     need = lib.tdx_conv3x3_infer_scratch_floats(B, H, W, CIN, COUT)
     for stages in (3, 4):
-        with tuned(tdx, infer_stages=stages):
+        with tdx.tuned(infer_stages=stages):
             for scr in ((G.new((need,)) if need else None), None):
                 out = G.new((B, H, W, COUT))
                 tdx.check(lib.tdx_conv3x3_fwd_infer(p(o.x), p(wt), p(o.b), p(out), B, H, W, CIN, COUT, p(o.osc), p(o.osh),
@@ -267,7 +252,7 @@ def test_direct_forward_tile_templates(tdx):
     o = Operands(B, H, CIN, CIN, COUT, 300, W=W, fenced=True)
     ref, mag, K = CH.role_reference(o, "fwd")
     for force, want in ((1, 128128), (2, 128064), (3, 64064)):
-        with tuned(tdx, conv_tile=force):
+        with tdx.tuned(conv_tile=force):
             assert lib.tdx_conv3x3_tile_shape(B, H, W, CIN, COUT, 0) == want
             tiles, rows = lib.tdx_conv3x3_stat_tiles(B, H, W, CIN, COUT), lib.tdx_conv3x3_stat_tile_rows(B, H, W, CIN, COUT)
             out, stats = G.new((B, H, W, COUT)), G.new((tiles, 2, COUT))
@@ -411,7 +396,7 @@ def _bf16_io16(tdx, B, H, W, seed, in_bn, knobs, G, fails):
     out, stats = G.new((B, H, W, COUT), torch.bfloat16), G.new((tiles, 2, COUT))
     gin = G.new((B, H, W, CIN), torch.bfloat16)
     dw = G.new((COUT, CIN, 3, 3))
-    with tuned(tdx, **knobs):
+    with tdx.tuned(**knobs):
         splits = lib.tdx_conv3x3_wgrad_splits_bf16(B, H, W, CIN, COUT)
         slabs = G.new((splits, COUT, 9, CIN))
         tdx.check(lib.tdx_conv3x3_fwd_bf16_io(p(x16), p(wf16), p(o.b), p(out), B, H, W, CIN, COUT, 4 | (1 if in_bn else 0),

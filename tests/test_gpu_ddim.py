@@ -17,6 +17,7 @@ from oracle.weights import (make_state_dict, make_state_dict_latent, make_state_
                             make_state_dict_transformer, make_state_dict_vae)
 from parity_helpers import rel_mse  # noqa: E402
 
+from tiny_diffusion_amd._lib import tuned  # noqa: E402
 from tiny_diffusion_amd.schedule import ForwardProcess, ddim_schedule, ddpm_schedule, sample_loop  # noqa: E402
 
 
@@ -61,11 +62,6 @@ def _inputs(kind, n, T, seed=0):
 
 
 MODES = {"eager": dict(use_graph=False), "graph": dict(use_graph=True), "philox": dict(use_graph=True, philox_seed=7)}
-
-
-def _tune(key, value):
-    from tiny_diffusion_amd._lib import check, lib
-    check(lib.tdx_tune_set(key.encode(), value))
 
 
 # ---------------------------------------------------------------- 1. the identity schedule is the existing sampler
@@ -163,11 +159,8 @@ def test_ddim_eta1_recorded_noise_against_fp64():
     # bit for bit, and the table-mode graph equals it up to the reassociation of the projection sums
     pe = sample_loop(m, fp, "cuda", n, None, x_T=x_T, schedule=sched, philox_seed=4)
     pt = sample_loop(m, fp, "cuda", n, None, x_T=x_T, schedule=sched, philox_seed=4, use_graph=True)
-    try:
-        _tune("sample_tables", 0)
+    with tuned(sample_tables=0):
         pg = sample_loop(m, fp, "cuda", n, None, x_T=x_T, schedule=sched, philox_seed=4, use_graph=True)
-    finally:
-        _tune("sample_tables", 1)
     assert torch.isfinite(pe).all() and not torch.equal(pe, eager)
     assert torch.equal(pg, pe)
     assert rel_mse(pt, pe) < 1e-10
@@ -190,11 +183,8 @@ def test_schedules_not_multiple_of_graph_steps(kind, S):
     assert torch.equal(sample_loop(m, fp, "cuda", n, y, x_T=x_T, noises=junk, schedule=sched), eager)
     assert torch.equal(sample_loop(m, fp, "cuda", n, y, x_T=x_T, noises=junk, schedule=sched, use_graph=True), eager)
     pe = sample_loop(m, fp, "cuda", n, y, x_T=x_T, schedule=sched, philox_seed=2)
-    try:
-        _tune("sample_tables", 0)
+    with tuned(sample_tables=0):
         pg = sample_loop(m, fp, "cuda", n, y, x_T=x_T, schedule=sched, philox_seed=2, use_graph=True)
-    finally:
-        _tune("sample_tables", 1)
     assert torch.equal(pg, pe)
     if kind == "transformer":
         return

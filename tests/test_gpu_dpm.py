@@ -22,7 +22,7 @@ from oracle.weights import (make_state_dict, make_state_dict_laion, make_state_d
 from inpaint_helpers import cpu_ms_step as _cpu_ms_step, spy_entries  # noqa: E402
 from parity_helpers import rel_mse  # noqa: E402
 
-from tiny_diffusion_amd._lib import check, lib  # noqa: E402
+from tiny_diffusion_amd._lib import check, lib, tuned  # noqa: E402
 from tiny_diffusion_amd.schedule import (GRAPH_STEPS, ForwardProcess, ddim_sample_loop, dpm_sample_loop,  # noqa: E402
                                          dpm_solver_schedule, logsnr_timesteps, sample_loop)
 
@@ -42,10 +42,6 @@ def _amp(w):
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
-
-
-def _tune(key, value):
-    check(lib.tdx_tune_set(key.encode(), value))
 
 
 def _model(kind, seed=0):
@@ -327,14 +323,10 @@ def test_multistep_fused_update_equals_separate_kernel(kind, w, n, bf16):
         t_idx = torch.empty(1, dtype=torch.int32, device="cuda")
         t_vec = torch.empty(rows, dtype=torch.int64, device="cuda")
         out = torch.empty_like(x)
-        try:
-            _tune("sample_fuse", 6 if fused else 2)
-            with torch.no_grad():
-                m._run_eval_step(x, y2, coef, counter, t_idx, t_vec, out, tau=tau, S=S, guidance_scale=w,
-                                 clip=(lo, hi), hist=hist)
+        with tuned(sample_fuse=6 if fused else 2), torch.no_grad():
+            m._run_eval_step(x, y2, coef, counter, t_idx, t_vec, out, tau=tau, S=S, guidance_scale=w,
+                             clip=(lo, hi), hist=hist)
             torch.cuda.synchronize()
-        finally:
-            _tune("sample_fuse", 6)
         assert counter.item() == 0 and t_idx.item() == 1 and int(t_vec[-1]) == 400
         res[fused] = (x.clone(), hist.clone(), out.clone())
     (xf, hf, of), (xs, hs, os_) = res[True], res[False]
@@ -431,11 +423,8 @@ def test_modes_agree_bit_for_bit(kind, w):
         pe = dpm_sample_loop(m, fp, "cuda", n, y, **kw)
         pg = dpm_sample_loop(m, fp, "cuda", n, y, use_graph=True, **kw)
         pt = dpm_sample_loop(m, fp, "cuda", n, y, use_graph=True, philox_seed=4, **kw)
-        try:
-            _tune("sample_tables", 0)
+        with tuned(sample_tables=0):
             pc = dpm_sample_loop(m, fp, "cuda", n, y, use_graph=True, philox_seed=4, **kw)
-        finally:
-            _tune("sample_tables", 1)
         assert torch.isfinite(pe).all() and pe.min() >= -1 and pe.max() <= 1
         assert torch.equal(pg, pe), (steps, rel_mse(pg, pe))
         assert torch.equal(pc, pe), (steps, rel_mse(pc, pe))
@@ -455,11 +444,8 @@ def test_half_batch_launches_index_one_history():
     x_T, _ = _inputs("uncond", n, seed=41)
     kw = dict(steps=S_CHAIN, x_T=x_T, use_graph=True, philox_seed=1, clip_denoised=True)
     base = dpm_sample_loop(_model("uncond", 3), fp, "cuda", n, None, **kw)
-    try:
-        _tune("sample_halves", 1)
+    with tuned(sample_halves=1):
         got = dpm_sample_loop(_model("uncond", 3), fp, "cuda", n, None, **kw)
-    finally:
-        _tune("sample_halves", 0)
     r = rel_mse(got, base)
     print(f"dpm half-batch launches vs whole batch: relative MSE {r:.3e}")
     assert r < 1e-9

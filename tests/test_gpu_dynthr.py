@@ -18,7 +18,7 @@ from inpaint_helpers import (INF, SHAPES, amp as _amp, block_mask, fp64_forward,
 from parity_helpers import rel_mse  # noqa: E402
 
 from tiny_diffusion_amd import _lib  # noqa: E402
-from tiny_diffusion_amd._lib import check, lib  # noqa: E402
+from tiny_diffusion_amd._lib import check, lib, tuned  # noqa: E402
 from tiny_diffusion_amd.schedule import (GRAPH_STEPS, ForwardProcess, ddim_schedule, dpm_sample_loop,  # noqa: E402
                                          dpm_solver_schedule, sample_loop)
 
@@ -32,10 +32,6 @@ S_K = 10
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
-
-
-def _tune(key, value):
-    check(lib.tdx_tune_set(key.encode(), value))
 
 
 def _p(t):
@@ -408,11 +404,8 @@ def test_thresholded_philox_graph_equals_eager(kind, w, prediction):
     kw = dict(x_T=x_T, schedule=sched, guidance_scale=w, prediction=prediction, dynamic_threshold=q, philox_seed=4)
     pe = sample_loop(m, fp, "cuda", n, y, **kw)
     pt = sample_loop(m, fp, "cuda", n, y, use_graph=True, **kw)
-    try:
-        _tune("sample_tables", 0)
+    with tuned(sample_tables=0):
         pg = sample_loop(m, fp, "cuda", n, y, use_graph=True, **kw)
-    finally:
-        _tune("sample_tables", 1)
     assert torch.isfinite(pe).all() and pe.min() >= -1 and pe.max() <= 1
     assert torch.equal(pg, pe), rel_mse(pg, pe)
     r = rel_mse(pt, pe)

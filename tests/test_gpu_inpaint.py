@@ -16,7 +16,7 @@ from inpaint_helpers import (INF, SHAPES, amp, block_mask, cpu_ms_masked_step, c
                              spy_entries)
 from parity_helpers import rel_mse  # noqa: E402
 
-from tiny_diffusion_amd._lib import check, lib  # noqa: E402
+from tiny_diffusion_amd._lib import check, lib, tuned  # noqa: E402
 from tiny_diffusion_amd.schedule import (GRAPH_STEPS, ForwardProcess, ddim_sample_loop, ddim_schedule,  # noqa: E402
                                          dpm_sample_loop, dpm_solver_schedule, sample_loop)
 
@@ -30,10 +30,6 @@ MASKED = ("tdx_p_sample_step_x0_masked", "tdx_p_sample_step_x0_guided_masked", "
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
-
-
-def _tune(key, value):
-    check(lib.tdx_tune_set(key.encode(), value))
 
 
 def _dev(t):
@@ -309,9 +305,8 @@ def test_masked_fused_update_equals_separate_kernel(kind, w, n, halves, bf16, fo
     y2 = y if w is None else torch.cat([y, null_cond(kind, y)]).contiguous()
     h0 = 0.5 * torch.randn(x_T.shape, generator=torch.Generator().manual_seed(3))
     res = {}
-    try:
-        _tune("sample_halves", halves)
-        for fused in (True, False):
+    for fused in (True, False):
+        with tuned(sample_halves=halves, sample_fuse=6 if fused else 2):
             x = _dev(torch.cat([x_T, x_T]) if w is not None else x_T)
             hist = _dev(h0) if form == "ms" else None
             kd, md = _dev(known), _dev(mask)
@@ -319,16 +314,12 @@ def test_masked_fused_update_equals_separate_kernel(kind, w, n, halves, bf16, fo
             t_idx = torch.empty(1, dtype=torch.int32, device="cuda")
             t_vec = torch.empty(rows, dtype=torch.int64, device="cuda")
             out = torch.empty_like(x)
-            _tune("sample_fuse", 6 if fused else 2)
             with torch.no_grad():
                 m._run_eval_step(x, y2, coef, counter, t_idx, t_vec, out, philox_seed=9, tau=tau, S=S, guidance_scale=w,
                                  clip=(lo, hi), hist=hist, known=kd, mask=md)
             torch.cuda.synchronize()
             assert counter.item() == 0 and t_idx.item() == 1 and int(t_vec[-1]) == 400
             res[fused] = (x.clone(), None if hist is None else hist.clone(), out.clone())
-    finally:
-        _tune("sample_fuse", 6)
-        _tune("sample_halves", 0)
     (xf, hf, of), (xs, hs, os_) = res[True], res[False]
     assert torch.isfinite(xf).all()
     assert torch.equal(of, os_) and torch.equal(xf, xs), rel_mse(xf, xs)
@@ -442,11 +433,8 @@ def test_masked_philox_graph_equals_eager(kind, w, form, tables):
         sched = dpm_solver_schedule(fp, steps=S, spacing="uniform")
         assert sched.steps == S
     pe = sample_loop(m, fp, "cuda", n, y, schedule=sched, **kw)
-    try:
-        _tune("sample_tables", tables)
+    with tuned(sample_tables=tables):
         pg = sample_loop(m, fp, "cuda", n, y, schedule=sched, use_graph=True, **kw)
-    finally:
-        _tune("sample_tables", 1)
     r = rel_mse(pg, pe)
     print(f"masked graph + Philox vs eager + Philox {kind} w={w} {form} tables={tables} S={S}: relative MSE {r:.3e}")
     if tables:      # the same pairing without known / mask, for the record: what the table mode itself costs

@@ -440,19 +440,14 @@ def test_conv3x3_fwd_infer(tdx, B, H, cin, cout):
     assert torch.equal(planned, run(big if need else None)) or need == 0   # same plan whenever the scratch suffices
     assert rel_err(nchw(run(None)), ref) < 3e-6                            # never split without scratch
     assert rel_err(nchw(run(None, scale=False)), conv) < 3e-6              # bias-only epilogue
-    try:
-        for stages in (3, 4):
-            check(lib.tdx_tune_set(b"infer_stages", stages))
+    for stages in (3, 4):
+        with tdx.tuned(infer_stages=stages):
             for sp in (2, 3, 5, 24):
-                check(lib.tdx_tune_set(b"infer_splits", sp))
-                o1, o2 = run(big), run(big)
+                with tdx.tuned(infer_splits=sp):
+                    o1, o2 = run(big), run(big)
                 assert rel_err(nchw(o1), ref) < 3e-6, (stages, sp)
                 assert torch.equal(o1, o2), (stages, sp)
-            check(lib.tdx_tune_set(b"infer_splits", 0))
             assert rel_err(nchw(run(big, scale=False)), conv) < 3e-6, stages
-    finally:
-        check(lib.tdx_tune_set(b"infer_splits", 0))
-        check(lib.tdx_tune_set(b"infer_stages", 4))
 
 
 @pytest.mark.parametrize("B,H,cin,cout,split", [(256, 4, 512, 512, True), (64, 4, 256, 256, True), (37, 4, 512, 512, True),
@@ -468,12 +463,8 @@ def test_conv3x3_fwd_train_splitk(tdx, B, H, cin, cout, split):
     wf, _ = _pack(tdx, w)
     xin, bd = dev(nhwc(x)), dev(b)
     hybrid = B * H * H > 16384      # the big shapes exercise the hybrid launch (off by default: knob conv_hybrid)
-    if hybrid:
-        tdx.check(tdx.lib.tdx_tune_set(b"conv_hybrid", 1))
-    try:
+    with tdx.tuned(**({"conv_hybrid": 1} if hybrid else {})):
         _fwd_train_checks(tdx, x, w, b, ref, wf, xin, bd, B, H, cin, cout, split)
-    finally:
-        tdx.check(tdx.lib.tdx_tune_set(b"conv_hybrid", 0))
 
 
 def _fwd_train_checks(tdx, x, w, b, ref, wf, xin, bd, B, H, cin, cout, split):

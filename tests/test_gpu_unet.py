@@ -251,7 +251,7 @@ def test_sample_chain_variants_built_and_off(golden_dir, cond, knobs):
     against the reference's T = 20 chain and the philox / table-mode path against the default build:
     sample_halves = 1 (the batch as two half-batches on two streams inside the captured graph) and infer_ring = 1
     (conv3x3_ring64_kernel on the tile-major pack)."""
-    from tiny_diffusion_amd._lib import lib, check
+    from tiny_diffusion_amd._lib import tuned
     name = "sample_T20_n4_cond" if cond else "sample_T20_n4_uncond"
     d = load(golden_dir, name)
     if cond:
@@ -261,12 +261,9 @@ def test_sample_chain_variants_built_and_off(golden_dir, cond, knobs):
     fp = ForwardProcess(num_timesteps=int(d["T"]))
     ykw = dict(y=torch.from_numpy(d["y"])) if cond else {}
     y5 = dict(y=torch.arange(5) % 10) if cond else {}
-    defaults = {"sample_halves": 0, "infer_ring": 0, "infer_stages": 4}
     x5 = torch.randn(5, 1, 28, 28, generator=torch.Generator().manual_seed(77))
     base = sample(build(cond, int(d["seed"])), fp, "cuda", n_samples=5, x_T=x5, use_graph=True, philox_seed=9, **y5)   # default build
-    try:
-        for k, v in knobs.items():
-            check(lib.tdx_tune_set(k.encode(), v))
+    with tuned(**knobs):
         m = build(cond, int(d["seed"]))
         for use_graph in (False, True):
             x = sample(m, fp, "cuda", n_samples=4, x_T=torch.from_numpy(d["x_T"]), noises=torch.from_numpy(d["zs"]),
@@ -276,9 +273,6 @@ def test_sample_chain_variants_built_and_off(golden_dir, cond, knobs):
         # to the summation order of the split-K plans (a half-batch keeps the whole batch's Philox indexing)
         got = sample(m, fp, "cuda", n_samples=5, x_T=x5, use_graph=True, philox_seed=9, **y5)
         assert rel_mse(got, base) < 1e-9
-    finally:
-        for k in knobs:
-            check(lib.tdx_tune_set(k.encode(), defaults[k]))
 
 
 def test_sample_default_rng_consumption():
@@ -562,14 +556,11 @@ def test_benchmarked_batch_256_direct_kernels_against_oracle():
     """The same B = 256 step on the direct kernels (knob wino = 0: every forward, input and weight gradient on the
     implicit GEMMs of conv3x3.hip), gated at the round-3 floor of 1e-4 for every parameter.  The run has its own ReLU
     masks and pooling routes, and its own oracle passes given them."""
-    from tiny_diffusion_amd._lib import check, lib
+    from tiny_diffusion_amd._lib import lib, tuned
 
-    check(lib.tdx_tune_set(b"wino", 0))
-    try:
+    with tuned(wino=0):
         assert all(lib.tdx_conv3x3_train_algo(256, 28, 28, 64, 128, r) == 0 for r in range(3))
         _batch_256_against_oracle(False, wino=False)
-    finally:
-        check(lib.tdx_tune_set(b"wino", 1))
     assert lib.tdx_conv3x3_train_algo(256, 28, 28, 64, 128, 0) == 1
 
 
@@ -869,7 +860,7 @@ def test_bn_backward_fused_partials_match_reduction_pass(cond, training, B):
     default is 6, the two spatial producers: the convolution form measured slower) against the separate reduction
     pass over (g, y) they replace (bnbwd_fused = 0): the same sums in another grouping, so every parameter
     gradient agrees to fp32 rounding (and both runs are deterministic)."""
-    from tiny_diffusion_amd._lib import lib
+    from tiny_diffusion_amd._lib import tuned
 
     g = torch.Generator().manual_seed(900 + B)
     x = torch.randn(B, 1, 28, 28, generator=g).cuda()
@@ -878,18 +869,15 @@ def test_bn_backward_fused_partials_match_reduction_pass(cond, training, B):
     y = torch.randint(0, 10, (B,), generator=g).cuda() if cond else None
     args = (x, t) + ((y,) if cond else ())
     grads = {}
-    try:
-        for fused in (7, 0, 7):
-            assert lib.tdx_tune_set(b"bnbwd_fused", fused) == 0
+    for fused in (7, 0, 7):
+        with tuned(bnbwd_fused=fused):
             m = build(cond, 17).train(training)
             F.mse_loss(m(*args), noise).backward()
-            cur = {k: p.grad.clone() for k, p in m.named_parameters()}
-            if fused in grads:   # the fused path is reproducible bit for bit
-                for k in cur:
-                    assert torch.equal(cur[k], grads[fused][k]), k
-            grads[fused] = cur
-    finally:
-        lib.tdx_tune_set(b"bnbwd_fused", 6)
+        cur = {k: p.grad.clone() for k, p in m.named_parameters()}
+        if fused in grads:   # the fused path is reproducible bit for bit
+            for k in cur:
+                assert torch.equal(cur[k], grads[fused][k]), k
+        grads[fused] = cur
     worst = 0.0
     for k in grads[0]:
         if training and is_pre_bn_bias(k):

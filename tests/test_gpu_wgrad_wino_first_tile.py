@@ -74,14 +74,10 @@ def test_wgrad_wino_first_tile(tdx, B, H, cin, cout, target, want_splits):
     g = torch.Generator(device="cuda").manual_seed(B * 1000 + H * 10 + cin + cout)
     x = torch.randn(B, H, H, cin, generator=g, device="cuda")
     dy = torch.randn(B, H, H, cout, generator=g, device="cuda")
-    try:
-        if target is not None:
-            tdx.check(lib.tdx_tune_set(b"wino_wgrad_target", target))
+    with tdx.tuned(**({} if target is None else {"wino_wgrad_target": target})):
         assert lib.tdx_conv3x3_wgrad_wino_splits(B, H, H, cin, cout) == want_splits
         s1, splits = launch(tdx, x, dy)
         s2, _ = launch(tdx, x, dy)
-    finally:
-        tdx.check(lib.tdx_tune_set(b"wino_wgrad_target", 512))
     torch.cuda.synchronize()
     assert not torch.isnan(s1).any(), "slab elements left unwritten"
     assert torch.equal(s1, s2), "two launches differ"

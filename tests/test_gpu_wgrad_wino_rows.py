@@ -65,16 +65,12 @@ def test_wgrad_wino_rows(tdx, B, H, cin, cout, target):
     g = torch.Generator(device="cuda").manual_seed(B * 1000 + H * 10 + cin + cout)
     x = torch.randn(B, H, H, cin, generator=g, device="cuda")
     dy = torch.randn(B, H, H, cout, generator=g, device="cuda")
-    try:
-        if target is not None:
-            tdx.check(lib.tdx_tune_set(b"wino_wgrad_target", target))
+    with tdx.tuned(**({} if target is None else {"wino_wgrad_target": target})):
         nt = B * ((H + 1) // 2) ** 2
         if target is not None:
             assert lib.tdx_conv3x3_wgrad_wino_splits(B, H, H, cin, cout) == -(-nt // 1024) and nt % 1024
         s1, splits = launch(tdx, x, dy, B, H, cin, cout)
         s2, _ = launch(tdx, x, dy, B, H, cin, cout)
-    finally:
-        tdx.check(lib.tdx_tune_set(b"wino_wgrad_target", 512))
     torch.cuda.synchronize()
     assert not torch.isnan(s1).any(), "slab elements left unwritten"
     assert torch.equal(s1, s2), "two launches differ"

@@ -15,7 +15,6 @@ from test_gpu_conv_launches import model_units, tile_blocks
 pytestmark = pytest.mark.gpu
 
 B_TRAIN = 256
-MIN_STAGES_DEFAULT = 16  # knob wino_rows_min_stages as the library starts
 
 EDGE = [   # (B, H, cin, cout)
     (64, 7, 64, 128),     # 7x7: four whole images per workgroup, odd maps
@@ -93,16 +92,11 @@ def test_rows_bit_identical_to_channel_split(tdx):
         b = torch.randn(cout, generator=g, device="cuda") * 0.1
         u = torch.full((cout * cin * 16,), float("nan"), device="cuda")
         tdx.check(lib.tdx_pack_conv3x3_wino(w.data_ptr(), u.data_ptr(), None, cout, cin, stream()))
-        try:
-            tdx.check(lib.tdx_tune_set(b"wino_rows_min_stages", 1))
-            tdx.check(lib.tdx_tune_set(b"wino_rows", 0))
+        with tdx.tuned(wino_rows_min_stages=1, wino_rows=0):
             ref, ref_st = run(tdx, x, u, b, B, H, cin, cout, role)
-            tdx.check(lib.tdx_tune_set(b"wino_rows", 1))
+        with tdx.tuned(wino_rows_min_stages=1, wino_rows=1):
             got, got_st = run(tdx, x, u, b, B, H, cin, cout, role)
             again, again_st = run(tdx, x, u, b, B, H, cin, cout, role)
-        finally:
-            tdx.check(lib.tdx_tune_set(b"wino_rows", 1))
-            tdx.check(lib.tdx_tune_set(b"wino_rows_min_stages", MIN_STAGES_DEFAULT))
         torch.cuda.synchronize()
         tag = f"B{B} {H}x{H} {cin}->{cout} {'fwd' if role == 0 else 'dgrad'} ({cin // 8} stages, {tile_blocks(B, H)} blocks)"
         bad = []

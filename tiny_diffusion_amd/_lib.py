@@ -7,6 +7,7 @@ the one libtdx binds to - streams and device pointers are then shared.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -234,6 +235,8 @@ _SIGS = {
     "tdx_unet_pack": (C.c_int, [_ptr, _ptr, _ptr, _ptr]),
     "tdx_unet_tensor": (C.c_int, [_ptr, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "tdx_tune_set": (C.c_int, [C.c_char_p, C.c_int]),
+    "tdx_tune_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
+    "tdx_tune_name": (C.c_char_p, [C.c_int]),
     "tdx_diag_set_buffer": (C.c_int, [_ptr, C.c_size_t]),
     "tdx_probe_mfma_f32": (C.c_int, [_ptr, C.c_int, C.c_int, _ptr]),
     "tdx_probe_stream_copy": (C.c_int, [_ptr, _ptr, C.c_int64, _ptr]),
@@ -276,6 +279,27 @@ def check(code: int, what: str = "tdx"):
     if code != 0:
         msg = lib.tdx_error_string(code)
         raise TdxError(f"{what} failed: {msg.decode() if msg else code} ({code})")
+
+
+def tune_get(key: str) -> int:
+    value = C.c_int()
+    if lib.tdx_tune_get(key.encode(), C.byref(value)) != 0:
+        raise TdxError(f"unknown tuning knob {key!r}")
+    return value.value
+
+
+@contextlib.contextmanager
+def tuned(**knobs):
+    """Run the body under these tuning knobs, then put back the values they held, last set first.
+    An unknown key raises TdxError before any knob is set."""
+    old = [(key, tune_get(key)) for key in knobs]
+    try:
+        for key, value in knobs.items():
+            check(lib.tdx_tune_set(key.encode(), int(value)), f"tdx_tune_set({key})")
+        yield
+    finally:
+        for key, value in reversed(old):
+            check(lib.tdx_tune_set(key.encode(), value), f"tdx_tune_set({key})")
 
 
 def ptr(t):

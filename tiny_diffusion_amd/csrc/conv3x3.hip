@@ -18,7 +18,6 @@
 // 32-63 take k+4..k+7) and issues four MFMAs from it; A and B use the same
 // permutation of k, so the sum over k is unchanged.
 #include "internal.h"
-#include <cstring>
 
 #define BK 32   // K-tile: 32 channels of one tap
 #define BKP 36  // padded LDS row (floats)
@@ -819,45 +818,7 @@ static int lds_slots_per_cu(int lds_bytes) {
   return n < 1 ? 1 : n > 8 ? 8 : n;
 }
 
-// tuning knobs (tdx_tune_set): 0 = heuristic
-static int g_force_tile = 0;          // 1: 128x128, 2: 128x64, 3: 64x64
-static int g_min_tiles = 256;         // smallest grid a 128-row tile may have (knob conv_min_tiles)
-static int g_conv_dbg = 0;
-int tdx_conv_dbg_get() { return g_conv_dbg; }
-static int g_conv_stamp = 0;           // diagnostics: LDS-DMA forward kernels stamp their main loop into the diag buffer
-extern unsigned* g_tdx_diag_buffer;    // time_embed.hip (tdx_diag_set_buffer)
-extern size_t g_tdx_diag_bytes;
-extern int g_tdx_probe_stamp;
-static int g_splitk = 1;              // 0: never split K; 1: split K when the grid would not fill the chip
-static int g_splitk_tiles = 260;      // split K when the 64x64 grid has fewer tiles than this (sweep on
-                                      // MI355X: 192 -> 260 is neutral at n=16 and 4 % faster at n=64)
-static int g_splitk_target = 512;     // ... into about this many workgroups
-static int g_wgrad_target = 2048;     // workgroups aimed at by the wgrad pixel split
-static int g_wgrad_target_big = 1024; // the same for 128x128 tiles (0: g_wgrad_target): at most two of them fit a
-                                      // CU (64 KiB of LDS each), so fewer, longer workgroups halve the slab traffic
-static int g_conv_hybrid = 0;        // 1: training convolutions K-slice the tiles beyond the last whole round (plan_hybrid).
-                                      // OFF: isolated it gains 1 % on the roofline leg (120.9 -> 121.7 TFLOP/s), inside the step
-                                      // nothing (the reduction launch it adds sits in the forward's dependent chain: 15.53 vs
-                                      // 15.56 ms), and it adds 16 % HBM traffic per launch (221.9 -> 257.7 MB, PMC)
-static int g_splitk_train = 1;       // training convolutions of latency-bound shapes split K (plan_splitk_train)
-static int g_splitk_train_t64 = 1024;   // ... when the 64x64 grid has fewer tiles than this
-static int g_splitk_train_target = 1536;  // ... into about this many workgroups
 #define TDX_CONV_OUT_BNBWD 8   /* internal flag: the epilogue emits BatchNorm-backward partial sums (ConvArgs::bw_*) */
-static int g_wgrad9_wgs = 0;          // bf16 mode: workgroups of the nine-tap kernel aimed at by the split (0: the per-tap plan's splits)
-static int g_wgrad_small = 1;         // 64x64 wgrad tiles for big-weight / few-pixel layers
-// inference (sampling) convolution, variant 4 (conv3x3_ring64_kernel): knobs "infer_ring" (0: variant 3 on the
-// K-contiguous pack), "infer_stages" (3 | 4 LDS stages), "infer_splits" (> 0: force that split count where K allows),
-// "infer_ovh" / "infer_red" (plan_infer's per-workgroup and per-reduction costs, in K-tile units), "infer_cus"
-// (compute units one launch may count on: 256, or 128 when two half-batches run side by side)
-int g_tdx_infer_ring = 0;   // OFF: measured slower than variant 3 (comment at conv3x3_ring64_kernel)
-static int g_infer_stages = 4;
-static int g_infer_splits = 0;
-static int g_infer_ovh = 4;
-static int g_infer_red = 12;
-int g_tdx_infer_cus = 256;
-int g_tdx_wino_infer = 1;
-static int g_wino_infer_ovh = 2;   // plan of the Winograd inference launch: a workgroup's non-loop time in stages (ring fill + epilogue ~ 4 us of 2.3)
-static int g_wino_infer_red = 3;   // ... and the dependent reduction launch
 
 // diagnostics: resident workgroups per CU the runtime computes for the LDS-DMA forward kernel of a tile
 // (bm*1000 + bn; training epilogue) and for the weight-gradient kernel (negative argument)
@@ -872,58 +833,6 @@ extern "C" int tdx_diag_conv_occupancy(int tile) {
   return e == hipSuccess ? n : -(int)e;
 }
 
-extern "C" int tdx_tune_set(const char* key, int value) {
-  if (!key) return TDX_E_BADARG;
-  if (!strcmp(key, "conv_tile")) { g_force_tile = value; return 0; }
-  if (!strcmp(key, "conv_min_tiles")) { g_min_tiles = value > 0 ? value : 256; return 0; }
-  if (!strcmp(key, "splitk")) { g_splitk = value; return 0; }
-  if (!strcmp(key, "splitk_tiles")) { g_splitk_tiles = value; return 0; }
-  if (!strcmp(key, "splitk_target")) { g_splitk_target = value; return 0; }
-  if (!strcmp(key, "streams")) { g_tdx_streams = value; return 0; }
-  if (!strcmp(key, "materialize")) { g_tdx_materialize = value; return 0; }
-  if (!strcmp(key, "stats_epi")) { g_conv_dbg = value ? (g_conv_dbg | 8) : (g_conv_dbg & ~8); return 0; }   // 1: one-pass (Chan) statistics epilogue
-  if (!strcmp(key, "bf16_storage")) { g_tdx_bf16_storage = value != 0; return 0; }
-  if (!strcmp(key, "sample_fuse")) { g_tdx_sample_fuse = value & 7; return 0; }
-  if (!strcmp(key, "sample_defer_max")) { g_tdx_sample_defer_max = value; return 0; }
-  if (!strcmp(key, "sample_tables")) { g_tdx_sample_tables = value != 0; return 0; }
-  if (!strcmp(key, "sample_halves")) { g_tdx_sample_halves = value != 0; return 0; }
-  if (!strcmp(key, "sample_halves_min")) { g_tdx_sample_halves_min = value > 2 ? value : 2; return 0; }
-  if (!strcmp(key, "bnbwd_fused")) { g_tdx_bnbwd_fused = value & 7; return 0; }
-  if (!strcmp(key, "conv_hybrid")) { g_conv_hybrid = value != 0; return 0; }
-  if (!strcmp(key, "splitk_train")) { g_splitk_train = value != 0; return 0; }
-  if (!strcmp(key, "splitk_train_t64")) { g_splitk_train_t64 = value > 0 ? value : 1024; return 0; }
-  if (!strcmp(key, "splitk_train_target")) { g_splitk_train_target = value > 0 ? value : 1536; return 0; }
-  if (!strcmp(key, "conv_dbg")) { g_conv_dbg = value; return 0; }
-  if (!strcmp(key, "bf16_materialize")) { g_tdx_bf16_materialize = value ? 1 : 0; return 0; }   // plans run afterwards
-  if (!strcmp(key, "bf16_thin")) { g_tdx_bf16_thin = value < 0 ? 0 : value; return 0; }   // 0 | 1 | 2: conv3x3_bf16_thin_kernel
-  if (!strcmp(key, "bf16_ring")) { g_tdx_bf16_ring = value ? 1 : 0; return 0; }   // 0: 128-row register-staging bf16 GEMM everywhere
-  if (!strcmp(key, "bf16_wgrad9")) { g_tdx_wgrad9 = value ? 1 : 0; return 0; }   // 0: one workgroup per tap (conv3x3_wgrad_bf16s_kernel)
-  if (!strcmp(key, "bf16_wgrad_swz")) { g_tdx_wgrad_bf16s = value ? 1 : 0; return 0; }   // 0: the round-2 staging (8-way LDS store conflicts)
-  if (!strcmp(key, "conv_stamp")) { g_conv_stamp = value; g_tdx_probe_stamp = value; return 0; }
-  if (!strcmp(key, "wgrad_small")) { g_wgrad_small = value; return 0; }
-  if (!strcmp(key, "wino")) { g_tdx_wino = value != 0; return 0; }                 // plans created / steps run afterwards
-  if (!strcmp(key, "wino_infer")) { g_tdx_wino_infer = value != 0; return 0; }   // (INFER packs written afterwards follow)
-  if (!strcmp(key, "wino_infer_min_units")) { g_tdx_wino_infer_min_units = value >= 0 ? value : 700; return 0; }
-  if (!strcmp(key, "wino_infer_ovh")) { g_wino_infer_ovh = value >= 0 ? value : 2; return 0; }
-  if (!strcmp(key, "wino_infer_red")) { g_wino_infer_red = value >= 0 ? value : 3; return 0; }
-  if (!strcmp(key, "wino_wgrad")) { g_tdx_wino_wgrad = value != 0; return 0; }
-  if (!strcmp(key, "wino_wgrad_min_tiles")) { g_tdx_wino_wgrad_min_tiles = value > 0 ? value : 1024; return 0; }
-  if (!strcmp(key, "wino_wgrad_target")) { g_tdx_wino_wgrad_target = value > 0 ? value : 512; return 0; }
-  if (!strcmp(key, "wino_min_wgs")) { g_tdx_wino_min_wgs = value > 0 ? value : 1; return 0; }
-  if (!strcmp(key, "wino_rows")) { g_tdx_wino_rows = value != 0; return 0; }
-  if (!strcmp(key, "wino_rows_min_stages")) { g_tdx_wino_rows_min_stages = value > 0 ? value : 16; return 0; }
-  if (!strcmp(key, "infer_ring")) { g_tdx_infer_ring = value != 0; return 0; }
-  if (!strcmp(key, "infer_stages")) { g_infer_stages = value == 3 ? 3 : 4; return 0; }
-  if (!strcmp(key, "infer_splits")) { g_infer_splits = value > 0 ? value : 0; return 0; }
-  if (!strcmp(key, "infer_ovh")) { g_infer_ovh = value >= 0 ? value : 4; return 0; }
-  if (!strcmp(key, "infer_red")) { g_infer_red = value >= 0 ? value : 12; return 0; }
-  if (!strcmp(key, "infer_cus")) { g_tdx_infer_cus = value > 0 && value <= 256 ? value : 256; return 0; }
-  if (!strcmp(key, "wgrad9_wgs")) { g_wgrad9_wgs = value > 0 ? value : 0; return 0; }
-  if (!strcmp(key, "wgrad_target")) { g_wgrad_target = value > 0 ? value : 2048; return 0; }
-  if (!strcmp(key, "wgrad_target_big")) { g_wgrad_target_big = value > 0 ? value : 0; return 0; }
-  return TDX_E_BADARG;
-}
-
 // Tile choice.  A CU retires tiles one after another at a fixed MFMA rate, so what matters
 // after per-tile efficiency (bigger is better: 128x128 runs ~8 % faster than 64x64 on a
 // perfectly balanced grid) is how evenly the tiles divide over the 256 CUs: 1568 tiles of
@@ -931,13 +840,13 @@ extern "C" int tdx_tune_set(const char* key, int value) {
 // grid is within 3.5 % of an even split; the smallest tile is the fallback.
 static TileCfg pick_tile(int64_t M, int cout) {
   const TileCfg cands[3] = {{128, 128}, {128, 64}, {64, 64}};
-  if (g_force_tile >= 1 && g_force_tile <= 3 && cout % cands[g_force_tile - 1].bn == 0)
-    return cands[g_force_tile - 1];
+  if (g_knobs.conv_tile >= 1 && g_knobs.conv_tile <= 3 && cout % cands[g_knobs.conv_tile - 1].bn == 0)
+    return cands[g_knobs.conv_tile - 1];
   for (int i = 0; i < 3; ++i) {
     if (cout % cands[i].bn) continue;
     if (i == 2) return cands[i];
     const int64_t tiles = ((M + cands[i].bm - 1) / cands[i].bm) * (cout / cands[i].bn);
-    if (tiles < g_min_tiles) continue;  // would leave CUs idle (or one lone workgroup per CU): try a smaller tile
+    if (tiles < g_knobs.conv_min_tiles) continue;  // would leave CUs idle (or one lone workgroup per CU): try a smaller tile
     const int64_t rounds = (tiles + 255) / 256;
     if ((double)(rounds * 256) <= 1.035 * (double)tiles) return cands[i];
   }
@@ -995,8 +904,8 @@ static int plan_splitk(int64_t M, int cin, int cout, int* kt_per_split, size_t c
   const int64_t tiles = ((M + c.bm - 1) / c.bm) * (cout / c.bn);
   const int nk = 9 * (cin / BK);
   *kt_per_split = nk;
-  if (!g_splitk || c.bm != 64 || tiles >= g_splitk_tiles) return 1;
-  int s = (int)((g_splitk_target + tiles - 1) / tiles);
+  if (!g_knobs.splitk || c.bm != 64 || tiles >= g_knobs.splitk_tiles) return 1;
+  int s = (int)((g_knobs.splitk_target + tiles - 1) / tiles);
   if (s > nk / 6) s = nk / 6;
   const size_t fit = cap_floats / ((size_t)M * cout);  // never ask for more scratch than there is
   if ((size_t)s > fit) s = (int)fit;
@@ -1023,10 +932,10 @@ static int plan_splitk_train(int64_t M, int cin, int cout, int* kt_per_split, si
   const TileCfg c = pick_tile(M, cout);
   const int nk = 9 * (cin / BK);
   *kt_per_split = nk;
-  if (!g_splitk_train || (c.bm == 128 && c.bn == 128) || nk < 24) return 1;
+  if (!g_knobs.splitk_train || (c.bm == 128 && c.bn == 128) || nk < 24) return 1;
   const int64_t t64 = ((M + 63) / 64) * (cout / 64);
-  if (t64 >= g_splitk_train_t64) return 1;
-  int s = (int)((g_splitk_train_target + t64 - 1) / t64);
+  if (t64 >= g_knobs.splitk_train_t64) return 1;
+  int s = (int)((g_knobs.splitk_train_target + t64 - 1) / t64);
   if (s > nk / 6) s = nk / 6;
   const size_t fit = cap_floats / ((size_t)M * cout);
   if ((size_t)s > fit) s = (int)fit;
@@ -1097,7 +1006,7 @@ static bool plan_hybrid(int64_t M, int cin, int cout, TileCfg c, HybridPlan* h) 
   // and 256->512 @7 261 -> 254; the 28x28 layers do not move (530: they are held back by their 103 MB inputs coming
   // from HBM - 460 back to back out of the MALL - not by the 0.125 of a round they spill), and the 128x64-tile
   // decoder layers lose 4-10 % (their last round is two thirds full).  Inside the step the total is unchanged.
-  if (!g_conv_hybrid || c.bm != 64 || c.bn != 64) return false;
+  if (!g_knobs.conv_hybrid || c.bm != 64 || c.bn != 64) return false;
   const int64_t tilesM = (M + c.bm - 1) / c.bm, tilesN = cout / c.bn, group = 8 * tilesN;
   const int64_t S = 256 * (int64_t)lds_slots_per_cu(2 * (c.bm + c.bn) * BK * 4);
   const int64_t T = tilesM * tilesN;
@@ -1154,7 +1063,7 @@ static int launch_hybrid(ConvArgs a, const HybridPlan& h, float* scratch, bool s
 template <int EPI_>
 static int splitk_finish(const ConvArgs& a, float* final_out, float* scratch, int splits, hipStream_t st,
                          TdxSplitDefer* defer, float* pool_out, bool* pooled) {
-  if (EPI_ == EPI_BNRELU && defer && splits <= g_tdx_sample_defer_max) {   // the consumer of this tensor reduces on load (spatial.hip, ResizeSrc)
+  if (EPI_ == EPI_BNRELU && defer && splits <= g_knobs.sample_defer_max) {   // the consumer of this tensor reduces on load (spatial.hip, ResizeSrc)
     *defer = TdxSplitDefer{scratch, splits, (size_t)a.M * a.Cout, a.bias, a.out_scale, a.out_shift};
     return 0;
   }
@@ -1243,17 +1152,17 @@ extern "C" int tdx_conv3x3_shape_ok(int B, int H, int W, int cin, int cout) {
 static unsigned long long* pick_stamps(const ConvArgs& a, const float* stats_partial) {
   // 1 = every LDS-DMA forward/dgrad launch stamps; M = only training-forward launches of M pixels;
   // -M = only plain-epilogue (dgrad) launches of M pixels
-  const bool stamp = g_conv_stamp == 1 || (g_conv_stamp > 1 && g_conv_stamp == a.M && stats_partial) ||
-                     (g_conv_stamp < 0 && -g_conv_stamp == a.M && !stats_partial);
+  const bool stamp = g_knobs.conv_stamp == 1 || (g_knobs.conv_stamp > 1 && g_knobs.conv_stamp == a.M && stats_partial) ||
+                     (g_knobs.conv_stamp < 0 && -g_knobs.conv_stamp == a.M && !stats_partial);
   // 2 = every training-forward launch, each into its own region of 8192 workgroup records (a per-process
   // slot counter: the tool resets it with conv_stamp = 0)
   static int slot = 0;
-  if (g_conv_stamp == 0) slot = 0;
+  if (g_knobs.conv_stamp == 0) slot = 0;
   // a workgroup writes one 64-byte record at index blockIdx.x; no launch has more workgroups than 64x64 tiles
   const size_t max_wgs = (size_t)cdiv(a.M, 64) * (size_t)(a.Cout / 64), rec = 8 * sizeof(unsigned long long);
   unsigned long long* stamps = stamp && g_tdx_diag_buffer && max_wgs * rec <= g_tdx_diag_bytes
                                    ? reinterpret_cast<unsigned long long*>(g_tdx_diag_buffer) : nullptr;
-  if (g_conv_stamp == 2 && stats_partial && g_tdx_diag_buffer && slot < 16 && max_wgs <= 8192 &&
+  if (g_knobs.conv_stamp == 2 && stats_partial && g_tdx_diag_buffer && slot < 16 && max_wgs <= 8192 &&
       (size_t)(slot + 1) * 8192 * rec <= g_tdx_diag_bytes)
     stamps = reinterpret_cast<unsigned long long*>(g_tdx_diag_buffer) + (size_t)(slot++) * 8 * 8192;
   return stamps;
@@ -1284,7 +1193,7 @@ static int conv3x3_fwd_impl(const FwdRequest& r, tdx_stream_t stream) {
   a.tilesN = cout / c.bn;
   a.splits = 1;
   a.kt_per_split = 9 * (cin / BK);
-  a.dbg = g_conv_dbg;
+  a.dbg = g_knobs.conv_dbg;
   a.stamps = pick_stamps(a, r.stats_partial);
   hipStream_t st = to_stream(stream);
   if (r.train && r.scratch && !(flags & (TDX_CONV_IN_BNRELU | TDX_CONV_OUT_BNRELU))) {
@@ -1382,8 +1291,8 @@ int tdx_conv3x3_dgrad_bnbwd(const float* in, const float* wpk, float* out, int B
   const int64_t M = (int64_t)B * H * W;
   int per;
   FwdRequest r = fwd_request(in, wpk, nullptr, out, B, H, W, cin, cout, 0);
-  if (!(g_tdx_bnbwd_fused & 1) || !y || !partial || cin % BK || cout % 64 || M >= (1ll << 31) ||
-      plan_splitk_train(M, cin, cout, &per, scratch_floats) > 1 || g_conv_hybrid) {
+  if (!(g_knobs.bnbwd_fused & 1) || !y || !partial || cin % BK || cout % 64 || M >= (1ll << 31) ||
+      plan_splitk_train(M, cin, cout, &per, scratch_floats) > 1 || g_knobs.conv_hybrid) {
     r.scratch = scratch; r.scratch_floats = scratch_floats;
     r.train = true;
     return conv3x3_fwd_impl(r, stream);
@@ -1425,21 +1334,21 @@ static int plan_infer(int64_t M, int cin, int cout, int* kt_per_split, size_t ca
   const size_t fit = cap_floats / ((size_t)M * cout);
   if ((size_t)smax > fit) smax = (int)fit;
   if (smax < 2) return 1;
-  if (g_infer_splits > 0) {
-    const int sf = g_infer_splits > smax ? smax : g_infer_splits;
+  if (g_knobs.infer_splits > 0) {
+    const int sf = g_knobs.infer_splits > smax ? smax : g_knobs.infer_splits;
     if (sf < 2) return 1;
     const int per = (nk + sf - 1) / sf;
     *kt_per_split = per;
     return (nk + per - 1) / per;
   }
-  const int C = g_tdx_infer_cus;
+  const int C = g_knobs.infer_cus;
   int best_s = 1, best_per = nk;
-  int64_t best = ((tiles + C - 1) / C) * (int64_t)(nk + g_infer_ovh);
+  int64_t best = ((tiles + C - 1) / C) * (int64_t)(nk + g_knobs.infer_ovh);
   for (int sp = 2; sp <= smax; ++sp) {
     const int per = (nk + sp - 1) / sp;
     const int real = (nk + per - 1) / per;
     if (real != sp) continue;   // the same launch as a smaller sp
-    const int64_t cost = ((tiles * real + C - 1) / C) * (int64_t)(per + g_infer_ovh) + g_infer_red;
+    const int64_t cost = ((tiles * real + C - 1) / C) * (int64_t)(per + g_knobs.infer_ovh) + g_knobs.infer_red;
     if (cost < best) { best = cost; best_s = real; best_per = per; }
   }
   *kt_per_split = best_per;
@@ -1502,12 +1411,12 @@ int tdx_conv3x3_fwd_infer_ex(const float* in, const float* w_tiled, const float*
   a.tilesN = cout / 64;
   a.splits = 1;
   a.kt_per_split = 9 * (cin / BK);
-  a.dbg = g_conv_dbg;
+  a.dbg = g_knobs.conv_dbg;
   int per = a.kt_per_split;
   const int splits = scratch ? plan_infer(M64, cin, cout, &per, scratch_floats) : 1;
   bool pooled = false;
   float* pool_out = pool ? pool->pooled : nullptr;
-  const int rc = g_infer_stages == 3
+  const int rc = g_knobs.infer_stages == 3
                      ? launch_infer<3>(a, splits, per, scratch, to_stream(stream), defer, pool_out, &pooled)
                      : launch_infer<4>(a, splits, per, scratch, to_stream(stream), defer, pool_out, &pooled);
   if (pool && !pooled) pool->pooled = nullptr;   // not split: the caller runs the pooling kernel
@@ -1523,13 +1432,13 @@ static int plan_wino_infer(int64_t wgs, int ns, int64_t M, int cout, int* per, s
   int smax = ns / 2;   // at least two stages per workgroup
   const size_t fit = cap_floats / ((size_t)M * cout);
   if ((size_t)smax > fit) smax = (int)fit;
-  const int C = g_tdx_infer_cus;
+  const int C = g_knobs.infer_cus;
   int best_s = 1;
-  int64_t best = ((wgs + C - 1) / C) * (int64_t)(ns + g_wino_infer_ovh);
+  int64_t best = ((wgs + C - 1) / C) * (int64_t)(ns + g_knobs.wino_infer_ovh);
   for (int sp = 2; sp <= smax; ++sp) {
     const int p2 = (ns + sp - 1) / sp, real = (ns + p2 - 1) / p2;
     if (real != sp) continue;
-    const int64_t cost = ((wgs * real + C - 1) / C) * (int64_t)(p2 + g_wino_infer_ovh) + g_wino_infer_red;
+    const int64_t cost = ((wgs * real + C - 1) / C) * (int64_t)(p2 + g_knobs.wino_infer_ovh) + g_knobs.wino_infer_red;
     if (cost < best) { best = cost; best_s = real; *per = p2; }
   }
   return best_s;
@@ -1963,9 +1872,9 @@ static WgradCfg pick_wgrad(int64_t M, int cin, int cout, bool bf16 = false) {
   // reduce (140 MB per layer).  64x64 tiles give 4x the workgroups from the weights alone.
   // Not in bf16 mode: there a 64x64 tile (16 FLOP per operand byte from L2) is L2-bound at ~175 TFLOP/s -
   // the four deep layers of the MNIST UNet ran at exactly that - and the bigger tile wins despite the slabs.
-  if (!bf16 && g_wgrad_small && (int64_t)cout * cin >= (1 << 17) && M <= 16384) { c.bm = 64; c.bn = 64; }
+  if (!bf16 && g_knobs.wgrad_small && (int64_t)cout * cin >= (1 << 17) && M <= 16384) { c.bm = 64; c.bn = 64; }
   int64_t tiles = (int64_t)(cout / c.bm) * (cin / c.bn) * 9;
-  const int target = (c.bm == 128 && c.bn == 128 && g_wgrad_target_big > 0) ? g_wgrad_target_big : g_wgrad_target;
+  const int target = (c.bm == 128 && c.bn == 128 && g_knobs.wgrad_target_big > 0) ? g_knobs.wgrad_target_big : g_knobs.wgrad_target;
   int64_t s = (target + tiles - 1) / tiles;
   if (!bf16 && c.bm == c.bn) {
     // Both targets are two rounds of the chip's workgroup slots (64x64: 4 per CU, 128x128: 2; lds_slots_per_cu),
@@ -1978,8 +1887,8 @@ static WgradCfg pick_wgrad(int64_t M, int cin, int cout, bool bf16 = false) {
     const int64_t two_rounds = 2 * 256 * (int64_t)lds_slots_per_cu(2 * 32 * (c.bm + c.bn) * 4);
     if (two_rounds / tiles >= 8) s = two_rounds / tiles;
   }
-  // bf16 mode with the nine-tap kernel (64 x 64 tiles, all taps in one workgroup): aim at g_wgrad9_wgs workgroups
-  if (bf16 && g_wgrad9_wgs > 0) s = g_wgrad9_wgs / ((int64_t)(cout / 64) * (cin / 64));
+  // bf16 mode with the nine-tap kernel (64 x 64 tiles, all taps in one workgroup): aim at g_knobs.wgrad9_wgs workgroups
+  if (bf16 && g_knobs.wgrad9_wgs > 0) s = g_knobs.wgrad9_wgs / ((int64_t)(cout / 64) * (cin / 64));
   int64_t smax = (M + 255) / 256;
   if (s > smax) s = smax;
   if (s < 1) s = 1;

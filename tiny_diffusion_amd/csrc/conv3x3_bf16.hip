@@ -1398,11 +1398,8 @@ static int launch_bf16(const ConvArgs& a, int flags, hipStream_t st) {
   return 0;
 }
 
-// conv3x3_bf16_ring_kernel: 256-row tiles, 512 threads, three DMA stages (+ 8 KB for the BN scale / shift copy)
-// Off by default: isolated, the ring kernel is 6-9 % faster over the MNIST launches (forward 1109 -> 1043 us, input
-// gradient 955 -> 865), but one 155 KB workgroup per CU shares a CU with nothing, and inside the three-stream step it
-// measured SLOWER (MNIST bf16 4.50 vs 4.40 ms, LAION 64x64 10.29 vs 10.12).  tdx_tune_set("bf16_ring", 1) selects it.
-int g_tdx_bf16_ring = 0;
+// conv3x3_bf16_ring_kernel: 256-row tiles, 512 threads, three DMA stages (+ 8 KB for the BN scale / shift copy).
+// tdx_tune_set("bf16_ring", 1) selects it (off by default: knobs.h).
 template <int BN>
 static int launch_bf16_ring(const ConvArgs& a, int flags, hipStream_t st) {
   const size_t lds = (size_t)3 * (256 + BN) * 64 * sizeof(__bf16) + 8192;
@@ -1435,15 +1432,7 @@ static int launch_bf16_ring(const ConvArgs& a, int flags, hipStream_t st) {
   return 0;
 }
 
-// conv3x3_bf16_thin_kernel: 256-row x 64-column tiles, 512 threads, 80 KB of LDS.  tdx_tune_set("bf16_thin", v):
-// 0 off | 1 layers with 64 output channels | 2 also layers with 64 input channels | 3 (default) every raw-input launch
-// whose rows are a multiple of 256 (wider layers run one workgroup per 64 output channels, each with its own copy of
-// the window).  Measured, B = 256: isolated (LAION 64x64) 64 -> 64 forward 201 -> 129 us, its input gradient 151-193 ->
-// 104-144, 192 -> 64 forward 428 -> 273, its input gradient (64 -> 192) 473 -> 335; steps in ms, knob 0 / 1 / 2 / 3:
-// LAION 64x64 9.34 / 8.84 / 8.65 / 8.49, LAION 32x32 3.24 / 3.11 / 3.08 / 2.96, MNIST 4.27 / 4.16 / 4.13 / 3.98.  Still
-// 3-4x the thin layers' HBM time: a workgroup's 72 MFMAs per wave (1 us) wait for nine weight tiles one L2 round trip
-// each - keeping the 72 KB of weights resident across tiles is the next step.
-int g_tdx_bf16_thin = 3;
+// conv3x3_bf16_thin_kernel: 256-row x 64-column tiles, 512 threads, 80 KB of LDS; the layers that run it: knob "bf16_thin" (knobs.h)
 static bool thin_window_fits(int H, int W) {   // the largest window of any 256-pixel tile: its slots + the halo, exactly
   const int PW = W + 1, PP = (H + 1) * PW, HW = H * W;
   auto slot_of = [&](int p) { const int n = p / HW, r = p - n * HW; const int oh = r / W; return n * PP + oh * PW + (r - oh * W); };
@@ -1507,15 +1496,15 @@ extern "C" int tdx_conv3x3_fwd_bf16_io(const void* in_, const void* wpk_bf16, co
   a.in_scale = in_scale; a.in_shift = in_shift; a.out_scale = out_scale; a.out_shift = out_shift;
   a.stats = stats_partial;
   a.B = B; a.H = H; a.W = W; a.Cin = cin; a.Cout = cout; a.M = (int)((int64_t)B * H * W);
-  a.splits = 1; a.kt_per_split = 0; a.dbg = tdx_conv_dbg_get(); a.stamps = nullptr;
+  a.splits = 1; a.kt_per_split = 0; a.dbg = g_knobs.conv_dbg; a.stamps = nullptr;
   a.out_bf16 = io16 ? 1 : 0;
   hipStream_t st = to_stream(stream);
   if (io16 && !(flags & TDX_CONV_IN_BNRELU) && a.M % 256 == 0 && thin_window_fits(H, W) &&
-      ((g_tdx_bf16_thin >= 1 && cout == 64) || (g_tdx_bf16_thin >= 2 && cin == 64) || g_tdx_bf16_thin >= 3)) {
+      ((g_knobs.bf16_thin >= 1 && cout == 64) || (g_knobs.bf16_thin >= 2 && cin == 64) || g_knobs.bf16_thin >= 3)) {
     a.tilesN = cout / 64;
     return launch_bf16_thin(a, flags, st);
   }
-  if (io16 && g_tdx_bf16_ring && a.M % 256 == 0 && cin <= 1024) {
+  if (io16 && g_knobs.bf16_ring && a.M % 256 == 0 && cin <= 1024) {
     a.tilesN = cout % 128 == 0 ? cout / 128 : cout / 64;
     return cout % 128 == 0 ? launch_bf16_ring<128>(a, flags, st) : launch_bf16_ring<64>(a, flags, st);
   }
@@ -1552,7 +1541,6 @@ static int launch_wgrad_bf16(const WgradArgs& a, bool in_bn, hipStream_t st) {
 }
 
 // bf16-storage form (conv3x3_wgrad_bf16s_kernel); tdx_tune_set("bf16_wgrad_swz", 0) goes back to the IO16 variant above
-int g_tdx_wgrad_bf16s = 1;
 template <int BM, int BN>
 static int launch_wgrad_bf16s(const WgradArgs& a, bool in_bn, hipStream_t st) {
   const size_t lds = (size_t)2 * (BM + BN) * KTW * sizeof(__bf16);   // 80 KB for 128 x 128: two workgroups fill the CU's 160 KB
@@ -1578,7 +1566,6 @@ static int launch_wgrad_bf16s(const WgradArgs& a, bool in_bn, hipStream_t st) {
 
 // conv3x3_wgrad9_bf16_kernel: one workgroup per (pixel chunk, 64 x 64 tile), all nine taps; same chunks and slabs as
 // the per-tap kernels (tdx_wgrad_plan), 2.25-4.5x fewer workgroups.  tdx_tune_set("bf16_wgrad9", 0) switches it off.
-int g_tdx_wgrad9 = 1;
 static int launch_wgrad9_bf16(WgradArgs a, int splits, bool in_bn, hipStream_t st) {
   a.tilesCo = a.Cout / 64;
   a.tilesCi = a.Cin / 64;
@@ -1628,11 +1615,11 @@ extern "C" int tdx_conv3x3_wgrad_bf16_io(const void* in_, const void* dy_, float
   a.B = B; a.H = H; a.W = W; a.Cin = cin; a.Cout = cout; a.M = (int)M64;
   a.tilesCi = cin / bn; a.tilesCo = cout / bm; a.chunk = chunk;
   a.groups = a.tilesCi * a.tilesCo * splits;
-  a.adv_q = 0; a.adv_s = 0; a.dbg = tdx_conv_dbg_get();
+  a.adv_q = 0; a.adv_s = 0; a.dbg = g_knobs.conv_dbg;
   hipStream_t st = to_stream(stream);
-  if (io16 && g_tdx_wgrad9 && W <= 95) return launch_wgrad9_bf16(a, splits, in_bn, st);   // (ring of <= 7 blocks: 96 KB of LDS)
+  if (io16 && g_knobs.bf16_wgrad9 && W <= 95) return launch_wgrad9_bf16(a, splits, in_bn, st);   // (ring of <= 7 blocks: 96 KB of LDS)
 #define TDX_WG(BM_, BN_)                                                                        \
-  (io16 ? (g_tdx_wgrad_bf16s ? launch_wgrad_bf16s<BM_, BN_>(a, in_bn, st) : launch_wgrad_bf16<BM_, BN_, true>(a, in_bn, st)) \
+  (io16 ? (g_knobs.bf16_wgrad_swz ? launch_wgrad_bf16s<BM_, BN_>(a, in_bn, st) : launch_wgrad_bf16<BM_, BN_, true>(a, in_bn, st)) \
         : launch_wgrad_bf16<BM_, BN_, false>(a, in_bn, st))
   if (bm == 128 && bn == 128) return TDX_WG(128, 128);
   if (bm == 128 && bn == 64) return TDX_WG(128, 64);

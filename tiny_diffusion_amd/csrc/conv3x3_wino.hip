@@ -30,9 +30,6 @@
 #include "internal.h"
 #include "conv_shared.h"
 
-extern unsigned* g_tdx_diag_buffer;    // time_embed.hip (tdx_diag_set_buffer)
-extern size_t g_tdx_diag_bytes;
-extern int g_tdx_probe_stamp;          // knob conv_stamp
 
 constexpr int WT = 64;    // tiles per workgroup
 constexpr int WN = 64;    // output channels per workgroup
@@ -658,10 +655,6 @@ extern "C" int tdx_pack_conv3x3_wino(const float* w_oihw, float* u_fwd, float* u
   return tdx_pack_conv3x3_wino_pad(w_oihw, u_fwd, u_dgrad, cout, cin, cin, stream);
 }
 
-int g_tdx_wino_rows = 1;              // knob "wino_rows": training launches on the row-split main loop (0: the channel split)
-int g_tdx_wino_rows_min_stages = 16;  // knob "wino_rows_min_stages": ... of at least this many K-stages (the 8-stage input gradients lost
-                                      // more to the exchange than their loop saved: profiles/r06_wino_phases.txt)
-
 // splits > 1: K (input channels) cut into `splits` ranges of `per` stages, raw partials to out[split][M][cout]
 // (flags, bias, scale / shift then belong to the caller's reduction)
 int tdx_conv3x3_wino_launch(const float* in, const float* u, const float* bias, float* out, int B, int H, int W,
@@ -685,7 +678,7 @@ int tdx_conv3x3_wino_launch(const float* in, const float* u, const float* bias, 
   a.per = per;
   a.compact = cdiv(a.NT, WT) < 64;
   const dim3 grid(a.compact ? cdiv(a.NT, WT) * a.tilesN : (cdiv(a.NT, WT) + 7) / 8 * 8 * a.tilesN, splits);
-  a.stamps = g_tdx_probe_stamp == 3 && g_tdx_diag_buffer && (size_t)grid.x * grid.y * 64 <= g_tdx_diag_bytes
+  a.stamps = g_knobs.conv_stamp == 3 && g_tdx_diag_buffer && (size_t)grid.x * grid.y * 64 <= g_tdx_diag_bytes
                  ? reinterpret_cast<unsigned long long*>(g_tdx_diag_buffer) : nullptr;   // diagnostic knob conv_stamp = 3
   const size_t lds = (size_t)2 * STAGE * sizeof(float) + WT * 2 * sizeof(unsigned);   // two stages + the tile table
   hipStream_t st = to_stream(stream);
@@ -701,7 +694,7 @@ int tdx_conv3x3_wino_launch(const float* in, const float* u, const float* bias, 
     }                                                                                                            \
     kern<<<grid, 256, lds, st>>>(a);                                                                             \
   } while (0)
-  const bool rows = g_tdx_wino_rows && cin / WK >= g_tdx_wino_rows_min_stages;   // the training launches' loop
+  const bool rows = g_knobs.wino_rows && cin / WK >= g_knobs.wino_rows_min_stages;   // the training launches' loop
   if (splits > 1) TDX_WINO_LAUNCH(EPI_PLAIN, true, false);
   else if (flags & TDX_CONV_OUT_BNRELU) TDX_WINO_LAUNCH(EPI_BNRELU, false, false);
   else if (flags & TDX_CONV_OUT_STATS) {
@@ -1099,10 +1092,9 @@ conv3x3_wgrad_wino_kernel(WinoWgArgs a) {
 }
 
 // pixel chunks (in tiles, a multiple of 8) of the Winograd weight gradient: about `target` workgroups of 64 x 64 channels
-int g_tdx_wino_wgrad_target = 512;   // knob "wino_wgrad_target": workgroups the pixel split of the Winograd weight gradient aims at
 static int wino_wgrad_plan(int NT, int cin, int cout, int* chunk) {
   const int ntile = (cout / 64) * (cin / 64);
-  const int target = g_tdx_wino_wgrad_target;
+  const int target = g_knobs.wino_wgrad_target;
   int splits = (target + ntile - 1) / ntile;
   int ch = (NT + splits - 1) / splits;
   ch = (ch + GT8 - 1) / GT8 * GT8;
@@ -1140,7 +1132,7 @@ extern "C" int tdx_conv3x3_wgrad_wino(const float* in, const float* dy, float* d
     if (e != hipSuccess) return (int)e;
     attr_set = true;
   }
-  a.stamps = g_tdx_probe_stamp == 3 && g_tdx_diag_buffer && (size_t)splits * a.tilesCo * a.tilesCi * 64 <= g_tdx_diag_bytes
+  a.stamps = g_knobs.conv_stamp == 3 && g_tdx_diag_buffer && (size_t)splits * a.tilesCo * a.tilesCi * 64 <= g_tdx_diag_bytes
                  ? reinterpret_cast<unsigned long long*>(g_tdx_diag_buffer) : nullptr;   // diagnostic knob conv_stamp = 3
   const dim3 grid(splits * a.tilesCo * a.tilesCi);
   conv3x3_wgrad_wino_kernel<<<grid, 256, WG_LDS, to_stream(stream)>>>(a);

@@ -2,6 +2,11 @@
 #pragma once
 #include <cmath>
 #include "common.h"
+#include "knobs.h"
+
+// the diagnostic buffer (tdx_diag_set_buffer, time_embed.hip): every path that stamps checks its records against the size
+extern unsigned* g_tdx_diag_buffer;
+extern size_t g_tdx_diag_bytes;
 
 int tdx_copy_segments(const float* const* src, float* const* dst, const size_t* n, int count, hipStream_t st);
 int tdx_pixel_sum(const void* g, float* out, int B, int HW, int C, hipStream_t st, int io16 = 0);
@@ -100,8 +105,6 @@ int tdx_conv3x3_fwd_splitk_fused(const float* in, const float* wpk, const float*
 int tdx_conv3x3_fwd_infer_ex(const float* in, const float* w_tiled, const float* bias, float* out, int B, int H, int W,
                              int cin, int cout, const float* out_scale, const float* out_shift, float* scratch,
                              size_t scratch_floats, tdx_stream_t stream, TdxSplitDefer* defer, TdxPoolFuse* pool);
-extern int g_tdx_infer_ring;   // knob "infer_ring": INFER-mode plans pack tile-major and run variant 4
-extern int g_tdx_infer_cus;    // knob "infer_cus": compute units one inference launch may count on (plan_infer)
 #define TDX_PACK_MAX 13
 struct TdxPackBatch {
   const float* w[TDX_PACK_MAX];
@@ -123,14 +126,9 @@ int tdx_pack_conv3x3_wino_batch(TdxWinoPackBatch* b, tdx_stream_t stream);
 extern "C" int tdx_conv3x3_wino_ok(int B, int H, int W, int cin, int cout);
 extern "C" int tdx_conv3x3_wino_stat_tiles(int B, int H, int W);
 extern "C" int tdx_conv3x3_wino_stat_tile_rows(int B, int H, int W);
-extern int g_tdx_wino, g_tdx_wino_min_wgs;   // knobs "wino" / "wino_min_wgs" (unet.hip)
-extern int g_tdx_wino_wgrad, g_tdx_wino_wgrad_min_tiles, g_tdx_wino_wgrad_target;
-extern int g_tdx_wino_rows, g_tdx_wino_rows_min_stages;   // knobs "wino_rows" / "wino_rows_min_stages" (conv3x3_wino.hip)
 extern "C" int tdx_conv3x3_wgrad_wino_splits(int B, int H, int W, int cin, int cout);
 extern "C" int tdx_conv3x3_wgrad_wino(const float* in, const float* dy, float* dw_slabs, int B, int H, int W, int cin, int cout,
                                       tdx_stream_t stream);
-extern int g_tdx_wino_infer_min_units;
-extern int g_tdx_wino_infer;                 // knob "wino_infer": INFER-mode plans run Winograd with split-K (conv3x3.hip: tdx_conv3x3_fwd_wino_infer_ex)
 int tdx_conv3x3_wino_launch(const float* in, const float* u, const float* bias, float* out, int B, int H, int W,
                             int cin, int cout, int flags, const float* out_scale, const float* out_shift,
                             float* stats_partial, int splits, int per, tdx_stream_t stream);
@@ -184,25 +182,8 @@ int tdx_latent_forward(const float* const* P, void* const* buffers, const float*
 int tdx_latent_backward(const float* const* P, float* const* G, const float* d_out, float* ws, int B,
                         int training, int stage_lo, int stage_hi, int ncls, hipStream_t st, int bf16 = 0);
 int tdx_latent_tensor(int B, const char* name, size_t* off, size_t* numel);
-// tuning knob "streams" (A/B experiments): -1 per-network default, 0 / 1 = plans created afterwards
-// run training on one stream / on the three-stream schedule
-extern int g_tdx_streams;
 int tdx_bn_relu_apply(const float* y, float* out, int64_t rows, int C, const float* scale, const float* shift,
                       hipStream_t st, int io16 = 0);
-// tuning knob "bf16_materialize": the same in bf16 storage mode (0: BN + ReLU while the consuming GEMMs stage their tiles)
-extern int g_tdx_bf16_materialize;
-// tuning knob "materialize": 1 = the activation feeding the second convolution of a stage is
-// written out (post BN+ReLU) so that convolution and its wgrad run on the LDS-DMA kernels
-extern int g_tdx_materialize;
-// tuning knob "bnbwd_fused": 1 = the kernel that PRODUCES dL/d(activation) of a unit (the input-gradient
-// convolution of the unit above, the resize adjoint or the max-pool backward) also emits the partial sums of that
-// unit's BatchNorm backward, and the separate reduction pass is skipped (unet.hip, tdx_unet_backward)
-extern int g_tdx_bnbwd_fused;
-extern int g_tdx_sample_tables;
-extern int g_tdx_sample_halves, g_tdx_sample_halves_min;   // unet.hip: half-batch inference
-extern int g_tdx_bf16_storage;
-extern int g_tdx_sample_fuse;       // bit 0 defer split-K reductions into the resize kernels, 1 pool in the reduction, 2 update in final_conv
-extern int g_tdx_sample_defer_max;
 int tdx_conv3x3_dgrad_bnbwd(const float* in, const float* wpk, float* out, int B, int H, int W, int cin, int cout,
                             const float* y, const float* scale, const float* shift, const float* mean,
                             const float* rstd, float* partial, int* nblk, float* scratch, size_t scratch_floats,

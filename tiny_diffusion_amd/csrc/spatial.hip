@@ -195,7 +195,7 @@ int tdx_maxpool2_ceil_bwd_bn(const void* y, const float* scale, const float* shi
                              const void* skip_grad, void* g_in, int B, int H, int W, int C, const float* bn_mean,
                              const float* bn_rstd, float* partial, int* nblk, tdx_stream_t stream, int io16) {
   *nblk = 0;
-  if (!(g_tdx_bnbwd_fused & 4) || !scale || !partial || C % 4 || C > 1024 || 256 % (C / 4))
+  if (!(g_knobs.bnbwd_fused & 4) || !scale || !partial || C % 4 || C > 1024 || 256 % (C / 4))
     return maxpool_bwd_t(y, scale, shift, g_out, skip_grad, g_in, B, H, W, C, io16, stream);
   if (!y || !g_out || !g_in || !bn_mean || !bn_rstd || B <= 0 || H <= 0 || W <= 0) return TDX_E_BADARG;
   const int64_t n = (int64_t)B * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);
@@ -602,7 +602,7 @@ int tdx_bilinear_ac_bwd_bn(const void* g_out, void* g_in, int B, int Hi, int Wi,
                            int* nblk, tdx_stream_t stream, int io16) {
   *nblk = 0;
   const bool rows_form = Wi <= BIL_ROW_MAXW && Hi <= BIL_ROW_MAXW && (int64_t)B * Hi < (1 << 30);
-  if (!(g_tdx_bnbwd_fused & 2) || !bn_y || !partial || !rows_form || C % 4 || C > 1024 || 256 % (C / 4))
+  if (!(g_knobs.bnbwd_fused & 2) || !bn_y || !partial || !rows_form || C % 4 || C > 1024 || 256 % (C / 4))
     return bilinear_ac_bwd_t(g_out, g_in, B, Hi, Wi, Ho, Wo, C, g_cstride, g_coff, io16, stream);
   if (!g_out || !g_in || !bn_scale || !bn_shift || !bn_mean || !bn_rstd || B <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 ||
       Wo <= 0)

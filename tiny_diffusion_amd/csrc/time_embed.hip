@@ -369,7 +369,6 @@ time_l1_bwd_kernel(const float* __restrict__ g_h, const float* __restrict__ pre,
   }
 }
 
-int g_tdx_probe_stamp = 0;
 unsigned* g_tdx_diag_buffer = nullptr;  // set by tdx_diag_set_buffer together with its size:
 size_t g_tdx_diag_bytes = 0;            // every diagnostic path checks what it is about to write against it
 extern "C" int tdx_diag_set_buffer(void* p, size_t bytes) {

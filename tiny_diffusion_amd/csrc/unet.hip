@@ -165,42 +165,6 @@ Layout make_layout(const NetSpec& S, int B) {
 
 }  // namespace
 
-int g_tdx_materialize = 1;
-int g_tdx_bf16_materialize = 1;
-int g_tdx_bf16_storage = 1;     // knob "bf16_storage": plans switched to bf16 afterwards keep their activation tensors in bf16 too
-// Sampling (INFER forward) launch fusions, knob "sample_fuse": bit 0 a split-K result consumed only by a resize is left
-// unreduced and summed by that resize on load (splits <= "sample_defer_max"), bit 1 the reduction of units 3 / 5 also
-// does the max-pool that follows, bit 2 final_conv applies the reverse-process update in its epilogue.  Measured at
-// n = 16 (tools/gpu_ab.py, ms per reverse step, tables on): none 0.565, pool 0.564, update 0.561, both 0.562, + deferral
-// of 2-way splits 0.561, of <= 4-way 0.571, of <= 8-way 0.575.  A launch removed this way gives back 1-4 us, not the
-// 5-6 us the trace shows per small kernel: that time is the dependent pass itself (partials written behind eight L2s
-// are read back through the fabric), which the fused kernel still makes - and the deferred form re-reads every
-// partial ~4 times.  Pool and update fusion stay on (neutral to -4 us, two launches fewer); deferral is off.
-int g_tdx_sample_defer_max = 2;
-int g_tdx_sample_fuse = 6;
-// knob "sample_halves": INFER forwards of >= "sample_halves_min" samples run as two half-batches side by side (tdx_unet_forward).
-// Built, parity-tested, measured, OFF: whether the two branches of the captured step overlap at all depends on which
-// hardware queues the runtime gives them (tools/micro/graph_branch_probe.py: the same two-branch graph replays in 0.50x
-// or in 0.74x the one-chain time from process to process; tools/micro/halves_matrix.sh: reverse step at n = 16 / 64,
-// ms: whole batch 0.61 / 1.75, halves 1.65 / 2.12 with the default 4 hardware queues, 0.62 / 1.61 with
-// GPU_MAX_HW_QUEUES=8) - at best -8 % at n = 64 and nothing at n = 16, at worst 2.7x slower.
-int g_tdx_sample_halves = 0;
-int g_tdx_sample_halves_min = 4;
-int g_tdx_sample_tables = 1;    // knob "sample_tables": tdx_unet_prepare_sampling builds the tables (0: leaves eval steps on the direct path)
-int g_tdx_bnbwd_fused = 6;     // knob "bnbwd_fused" (internal.h): bit 0 input-gradient convolutions, bit 1 resize adjoints, bit 2 max-pool backward.
-                               // Measured at B = 256 (tools/gpu_ab.py, ms/step): 0: 15.54, 1: 15.73, 2: 15.52, 4: 15.55, 6: 15.53, 7: 15.66 - the
-                               // heavier convolution epilogue costs the GEMMs more than the reduction pass it saves (that pass is HBM-bound and
-                               // runs beside the weight-gradient GEMMs of the other stream for nothing); the two spatial producers are neutral in
-                               // time and save 8 B/element of HBM traffic and a launch on seven layers: on. The convolution form stays an experiment.
-// knob "wino": fp32 training forwards / input gradients of raw-input units run on Winograd F(2x2,3x3) (conv3x3_wino.hip)
-// where the launch fills the chip (>= "wino_min_wgs" workgroups of 64 tiles x 64 channels) and the map geometry allows
-int g_tdx_wino = 1;
-int g_tdx_wino_min_wgs = 100;
-int g_tdx_wino_wgrad = 1;               // knob "wino_wgrad": weight gradients by F(3x3,2x2) (conv3x3_wgrad_wino_kernel)
-int g_tdx_wino_wgrad_min_tiles = 1024;  // knob "wino_wgrad_min_tiles"
-int g_tdx_wino_infer_min_units = 700;   // knob "wino_infer_min_units" (n = 16: 784 for the first 64->128 layer, 512 for the 4x4 / 64-channel ones)
-int g_tdx_streams = -1;  // tuning knob "streams": -1 = per-network default (NetSpec::overlap), 0 / 1 = force
-
 struct PlanHandles {
   hipStream_t side, side2, half;
   hipEvent_t ev[81];
@@ -388,8 +352,8 @@ extern "C" int tdx_unet_create_full(tdx_unet** out, int max_batch, int kind, int
   u->g_x = nullptr;
   u->bw_unit = -1;
   u->bw_nblk = 0;
-  u->materialize = g_tdx_materialize != 0;
-  u->use_streams = g_tdx_streams < 0 ? (u->spec ? u->spec->overlap : 0) : g_tdx_streams;
+  u->materialize = g_knobs.materialize != 0;
+  u->use_streams = g_knobs.streams < 0 ? (u->spec ? u->spec->overlap : 0) : g_knobs.streams;
   if (!make_handles(&u->handles)) {
     (void)hipFree(u->wpack); if (u->upack) (void)hipFree(u->upack); (void)hipFree(u->infer_ss);
     delete u;
@@ -436,7 +400,7 @@ extern "C" int tdx_unet_set_precision(tdx_unet* u, int precision) {
   if (precision != u->precision) u->packed = false;                 // INFER packs are per precision
   u->precision = precision;
   // bf16 mode = bf16 MFMA operands AND bf16 activation tensors in HBM (round 3; knob "bf16_storage" = 0 keeps fp32 tensors)
-  u->io16 = precision == TDX_PREC_BF16 && g_tdx_bf16_storage ? 1 : 0;
+  u->io16 = precision == TDX_PREC_BF16 && g_knobs.bf16_storage ? 1 : 0;
   return 0;
 }
 
@@ -523,13 +487,13 @@ extern "C" int tdx_unet_tensor(const tdx_unet* u, int batch, const char* name, s
 // 1 when the training step at batch B runs this layer's forward (role 0) / input gradient (role 1) on the Winograd kernel:
 // the geometry must be served in both directions and the launch must fill the chip (one workgroup per CU)
 extern "C" int tdx_conv3x3_train_algo(int B, int H, int W, int cin, int cout, int role) {
-  if (!g_tdx_wino || B <= 0 || role < 0 || role > 2) return 0;
+  if (!g_knobs.wino || B <= 0 || role < 0 || role > 2) return 0;
   if (role == 2)   // weight gradient, F(3x3,2x2): any geometry; enough tiles that its workgroups (>= 4 stages of 8 tiles) fill the chip
-    return g_tdx_wino_wgrad && cin % 64 == 0 && cout % 64 == 0 &&
-           (int64_t)B * ((H + 1) / 2) * ((W + 1) / 2) >= g_tdx_wino_wgrad_min_tiles ? 1 : 0;
+    return g_knobs.wino_wgrad && cin % 64 == 0 && cout % 64 == 0 &&
+           (int64_t)B * ((H + 1) / 2) * ((W + 1) / 2) >= g_knobs.wino_wgrad_min_tiles ? 1 : 0;
   if (!tdx_conv3x3_wino_ok(B, H, W, cin, cout) || !tdx_conv3x3_wino_ok(B, H, W, cout, cin)) return 0;
   const int blocks = tdx_conv3x3_wino_stat_tiles(B, H, W);
-  return blocks * ((role == 0 ? cout : cin) / 64) >= g_tdx_wino_min_wgs ? 1 : 0;
+  return blocks * ((role == 0 ? cout : cin) / 64) >= g_knobs.wino_min_wgs ? 1 : 0;
 }
 
 // 1 when an INFER-mode (sampling) forward of n = B samples runs this layer on the Winograd kernel with split K
@@ -538,8 +502,8 @@ extern "C" int tdx_conv3x3_train_algo(int B, int H, int W, int cin, int cout, in
 // (profiles/r04_infer_layers_wino.txt) it wins wherever workgroups x stages >= ~800 and loses up to 6 us per layer
 // below (the 64-channel and 4x4 layers at n = 16).  The plan must also hold the Winograd pack (decide_wino).
 extern "C" int tdx_conv3x3_infer_algo(int B, int H, int W, int cin, int cout) {
-  if (!g_tdx_wino_infer || g_tdx_infer_ring || !tdx_conv3x3_wino_ok(B, H, W, cin, cout)) return 0;
-  return (int64_t)tdx_conv3x3_wino_stat_tiles(B, H, W) * (cout / 64) * (cin / 8) >= g_tdx_wino_infer_min_units ? 1 : 0;
+  if (!g_knobs.wino_infer || g_knobs.infer_ring || !tdx_conv3x3_wino_ok(B, H, W, cin, cout)) return 0;
+  return (int64_t)tdx_conv3x3_wino_stat_tiles(B, H, W) * (cout / 64) * (cin / 8) >= g_knobs.wino_infer_min_units ? 1 : 0;
 }
 
 static void decide_wino(tdx_unet* u, int B, bool training_modes) {
@@ -549,7 +513,7 @@ static void decide_wino(tdx_unet* u, int B, bool training_modes) {
     if (!training_modes) {
       // INFER pack (fp32): every unit whose geometry the kernel serves (at any batch: the map size decides) gets a Winograd
       // pack; whether a forward uses it is decided from its batch (run_unit).  Post-activation tensors are raw inputs.
-      u->wino_f[i] = g_tdx_wino_infer && u->precision != TDX_PREC_BF16 && !g_tdx_infer_ring &&
+      u->wino_f[i] = g_knobs.wino_infer && u->precision != TDX_PREC_BF16 && !g_knobs.infer_ring &&
                      tdx_conv3x3_wino_ok(1, d.hw, d.hw, d.cin, d.cout);
       continue;
     }
@@ -605,7 +569,7 @@ static int pack_impl(tdx_unet* u, const void* const* params, void* const* buffer
     return 0;
   }
   // INFER pack of the fp32 mode: tile-major, forward only (knob "infer_ring")
-  const bool tiled = buffers && !overlap && u->precision != TDX_PREC_BF16 && g_tdx_infer_ring;
+  const bool tiled = buffers && !overlap && u->precision != TDX_PREC_BF16 && g_knobs.infer_ring;
   u->wf_tiled = tiled;
   decide_wino(u, train_batch, train_batch > 0);
   // overlap: head now; the tail is launched by pack_tail() once the main stream has MFMA work in flight
@@ -664,7 +628,7 @@ static int pack_tail(tdx_unet* u, const void* const* params, tdx_stream_t stream
 // convolutions.  Results equal the whole-batch forward up to the summation order of the split-K plans (which
 // depend on M); in-kernel noise keeps the whole batch's Philox indexing (PStep::elem0).
 static bool infer_halves(const tdx_unet* u, int batch, size_t workspace_bytes, int* b0) {
-  if (!u->spec || !u->half_own || u->whole_batch || !g_tdx_sample_halves || batch < 2 || batch < g_tdx_sample_halves_min) return false;
+  if (!u->spec || !u->half_own || u->whole_batch || !g_knobs.sample_halves || batch < 2 || batch < g_knobs.sample_halves_min) return false;
   const int h0 = (batch + 1) / 2;
   if (workspace_bytes < (make_layout(*u->spec, h0).total + make_layout(*u->spec, batch - h0).total) * sizeof(float)) return false;
   *b0 = h0;
@@ -815,7 +779,7 @@ static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const
       // consumer's staging path - at the bf16 matrix rate the transform's ~128 VALU instructions per K-tile were as long
       // as the K-tile's MFMAs (forward launches with BN on load: +50 % over the same shapes with a raw input)
       const int64_t M = (int64_t)B * d.hw * d.hw;
-      const bool mat16 = io16 && u->materialize && g_tdx_bf16_materialize;
+      const bool mat16 = io16 && u->materialize && g_knobs.bf16_materialize;
       if (infer) {
         const float* iss = u->infer_ss + u->iss_off[i];
         return tdx_conv3x3_fwd_bf16_io(in, wf, bias, Y, B, d.hw, d.hw, d.cin, d.cout, TDX_CONV_OUT_BNRELU, nullptr,
@@ -878,7 +842,7 @@ static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const
     const int ua = 2 * k, ub = 2 * k + 1;
     if (k == 1 && !infer) TDX_HIP(hipStreamWaitEvent(st, u->ev_pack, 0));  // packs of units 2..12
     if (k > 0) RC(run_unit(ua, ws + L.ep[k - 1]));
-    TdxPoolFuse pf{infer && !bf16 && (g_tdx_sample_fuse & 2) ? ws + L.ep[k] : nullptr};
+    TdxPoolFuse pf{infer && !bf16 && (g_knobs.sample_fuse & 2) ? ws + L.ep[k] : nullptr};
     RC(run_unit(ub, ws + L.Y[ua], nullptr, pf.pooled ? &pf : nullptr));
     if (!infer) {
       // the skip branch resize(e_k + t_k) -> second half of the decoder's concat buffer only needs
@@ -897,7 +861,7 @@ static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const
       RC(tdx_maxpool2_ceil_fwd_t(ws + L.Y[ub], sc(ub), sh(ub), ws + L.ep[k], B, S.enc_hw[k], S.enc_hw[k],
                                  S.skip_ch[k], io16, stream));
   }
-  const bool defer_ok = infer && !bf16 && (g_tdx_sample_fuse & 1);
+  const bool defer_ok = infer && !bf16 && (g_knobs.sample_fuse & 1);
   TdxSplitDefer dfr{};   // the deferred result of the unit about to be resized (6, 8, 10, then 12)
   RC(run_unit(6, ws + L.ep[2], defer_ok ? &dfr : nullptr));
   // decoder level k (0: dec3 .. 2: dec1): cat = [up(previous) | resize(e + t)], diffusion.py:135-154
@@ -1065,7 +1029,7 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
     u->bw_unit = -1;
     // Weight gradient: forked to the side stream (which IS the main stream for networks whose
     // NetSpec says overlap = 0).
-    const bool mat = u->materialize && (!bf16 || (io16 && g_tdx_bf16_materialize));
+    const bool mat = u->materialize && (!bf16 || (io16 && g_knobs.bf16_materialize));
     const bool bn_on_load = d.in_bn && !mat;
     if (d.in_bn && mat) in = ws + L.A[i - 1];  // materialised relu(bn(Y[i-1]))
     const float* isc = bn_on_load ? ws + L.ss[i - 1] : nullptr;
@@ -1341,7 +1305,7 @@ static int eval_step_impl(tdx_unet* u, const void* const* params, void* const* b
   u->skip_time_path = tab;
   u->whole_batch = guided;   // (set here, cleared below: no early return in between)
   // the UNets apply the update in final_conv's epilogue (one launch less); the latent MLP keeps the separate kernel
-  const bool fuse_ps = u->spec && (g_tdx_sample_fuse & 4) && !ps.thr &&
+  const bool fuse_ps = u->spec && (g_knobs.sample_fuse & 4) && !ps.thr &&
                        (guided ? 2 : 1) * n_elems == (int64_t)batch * u->spec->in_ch * u->spec->out_hw * u->spec->out_hw;
   ps.counter_dec = tab ? counter : nullptr;
   if (fuse_ps) { u->ps = ps; u->ps.x = x; }
@@ -1421,7 +1385,7 @@ static int prepare_sampling_impl(tdx_unet* u, const void* const* params, const v
   const bool needs_cond = u->kind == 1 || u->num_classes > 0;
   if (needs_cond != (cond != nullptr)) return TDX_E_BADARG;
   if (!u->packed) return TDX_E_STATE;
-  if (!g_tdx_sample_tables) { u->tab_gen = -1; return 0; }   // knob "sample_tables" = 0: A/B against the direct path
+  if (!g_knobs.sample_tables) { u->tab_gen = -1; return 0; }   // knob "sample_tables" = 0: A/B against the direct path
   const NetSpec& S = *u->spec;
   const size_t wsum = (size_t)S.skip_ch[0] + S.skip_ch[1] + S.skip_ch[2], td = S.time_dim;
   // scratch = int64 step indices [T] | sin, pre, emb [T][td] (read as float4 rows: the index block is rounded up to

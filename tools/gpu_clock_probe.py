@@ -8,7 +8,7 @@ import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from tiny_diffusion_amd._lib import lib, check
+from tiny_diffusion_amd._lib import lib, check, tuned
 
 dev = torch.device("cuda")
 st = torch.cuda.current_stream().cuda_stream
@@ -49,10 +49,9 @@ def run(name, fn, nwg, flop, secs=2.0):
     e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / 20
     stamps.zero_()
-    lib.tdx_tune_set(b"conv_stamp", 1)
-    fn()
-    torch.cuda.synchronize()
-    lib.tdx_tune_set(b"conv_stamp", 0)
+    with tuned(conv_stamp=1):
+        fn()
+        torch.cuda.synchronize()
     med, lo, hi, cyc, tl = clock_of(nwg)
     tf = flop / ms / 1e9
     peak_at_clock = 157.3 * med / 2400.0

@@ -5,15 +5,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 import bench
-from tiny_diffusion_amd._lib import lib
+from tiny_diffusion_amd._lib import lib, tuned
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 res = {}
 for tile, name in ((0, "auto"), (1, "128x128"), (2, "128x64"), (3, "64x64")):
-    lib.tdx_tune_set(b"conv_tile", tile)
-    rows, flop, ms, nl = bench.conv_roofline(B, reps=5)
+    with tuned(conv_tile=tile):
+        rows, flop, ms, nl = bench.conv_roofline(B, reps=5)
     res[name] = rows
     print(f"tile {name}: total {ms:.3f} ms  {flop / ms / 1e9:.1f} TF")
-lib.tdx_tune_set(b"conv_tile", 0)
 print(f"{'layer':28s}" + "".join(f"{n:>10s}" for n in res))
 for i, r in enumerate(res["auto"]):
     if r["role"] == "wgrad":

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
-from tiny_diffusion_amd._lib import lib, check  # noqa: E402
+from tiny_diffusion_amd._lib import lib, check, tuned  # noqa: E402
 
 LAYERS = [("enc1.0", 64, 128, 28), ("enc1.3", 128, 128, 28), ("enc2.0", 128, 256, 14), ("enc2.3", 256, 256, 14),
           ("enc3.0", 256, 512, 7), ("enc3.3", 512, 512, 7), ("bottleneck", 512, 512, 4), ("dec3.0", 1024, 256, 8),
@@ -87,24 +87,22 @@ for n in ns:
             res = []
             for bits, label in ((1, "no barrier"), (4, "no DMA"), (16, "no MFMA"), (32, "no LDS reads"), (20, "no DMA+MFMA"),
                                 (52, "barrier only"), (53, "nothing")):
-                check(lib.tdx_tune_set(b"conv_dbg", bits))
-                res.append((label, timed(new)))
-            check(lib.tdx_tune_set(b"conv_dbg", 0))
+                with tuned(conv_dbg=bits):
+                    res.append((label, timed(new)))
             line += "   ablate " + ", ".join(f"{lb} {t:.1f}" for lb, t in res)
         if sweep:
             res = []
             for sp in [1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 24]:
                 if sp > max(nk // 6, 1):
                     break
-                check(lib.tdx_tune_set(b"infer_splits", sp))
-                if sp == 1:
-                    def f1():
-                        check(lib.tdx_conv3x3_fwd_infer(x.data_ptr(), wt.data_ptr(), b.data_ptr(), out.data_ptr(), n, hw, hw,
-                                                        cin, cout, sc.data_ptr(), sh.data_ptr(), None, 0, st()))
-                    res.append((sp, timed(f1)))
-                else:
-                    res.append((sp, timed(new)))
-            check(lib.tdx_tune_set(b"infer_splits", 0))
+                with tuned(infer_splits=sp):
+                    if sp == 1:
+                        def f1():
+                            check(lib.tdx_conv3x3_fwd_infer(x.data_ptr(), wt.data_ptr(), b.data_ptr(), out.data_ptr(), n, hw,
+                                                            hw, cin, cout, sc.data_ptr(), sh.data_ptr(), None, 0, st()))
+                        res.append((sp, timed(f1)))
+                    else:
+                        res.append((sp, timed(new)))
             line += "   sweep " + " ".join(f"{sp}:{t:.1f}" for sp, t in res)
         print(line, flush=True)
         tot_old += t_old; tot_new += t_new; tot_peak += t_peak

@@ -5,7 +5,7 @@ import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from tiny_diffusion_amd._lib import lib
+from tiny_diffusion_amd._lib import lib, tuned
 from tiny_diffusion_amd.diffusion import ForwardProcess, NoiseModel
 from tiny_diffusion_amd.train import TrainStep
 
@@ -19,10 +19,9 @@ lib.tdx_diag_set_buffer(stamps.data_ptr(), stamps.numel() * stamps.element_size(
 for _ in range(30):
     ts.step(x0)
 torch.cuda.synchronize()
-lib.tdx_tune_set(b"conv_stamp", sel)
-ts.step(x0)
-torch.cuda.synchronize()
-lib.tdx_tune_set(b"conv_stamp", 0)
+with tuned(conv_stamp=sel):
+    ts.step(x0)
+    torch.cuda.synchronize()
 if sel == 2:   # every training-forward conv of one step, absolute 100 MHz times
     allr = stamps.cpu().view(16, 8192, 8).double()
     base = None

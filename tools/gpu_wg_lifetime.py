@@ -7,7 +7,7 @@ import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from tiny_diffusion_amd._lib import lib, check
+from tiny_diffusion_amd._lib import lib, check, tuned
 
 dev = torch.device("cuda")
 st = torch.cuda.current_stream().cuda_stream
@@ -31,10 +31,9 @@ for cin, cout, H in ((128, 128, 28), (64, 128, 28), (256, 256, 14), (512, 512, 7
         fn()
     torch.cuda.synchronize()
     stamps.zero_()
-    lib.tdx_tune_set(b"conv_stamp", 1)
-    fn()
-    torch.cuda.synchronize()
-    lib.tdx_tune_set(b"conv_stamp", 0)
+    with tuned(conv_stamp=1):
+        fn()
+        torch.cuda.synchronize()
     s = stamps.cpu()[: 8 * nwg].view(-1, 8)
     s = s[s[:, 1] > 0].double()
     entry, l0, l1, end = s[:, 6], s[:, 2], s[:, 3], s[:, 4]

@@ -7,7 +7,7 @@ import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from tiny_diffusion_amd._lib import lib, check
+from tiny_diffusion_amd._lib import lib, check, tuned
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 dev = torch.device("cuda")
@@ -39,10 +39,9 @@ for cin, cout, H in UNITS:
     torch.cuda.synchronize()
     ev_us = e0.elapsed_time(e1) / 20 * 1e3
     stamps.zero_()
-    lib.tdx_tune_set(b"conv_stamp", 1)
-    fn()
-    torch.cuda.synchronize()
-    lib.tdx_tune_set(b"conv_stamp", 0)
+    with tuned(conv_stamp=1):
+        fn()
+        torch.cuda.synchronize()
     s = stamps.cpu().view(-1, 8)
     s = s[s[:, 1] > 0].double()
     entry, l0, l1, end = s[:, 6], s[:, 2], s[:, 3], s[:, 4]

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
-from tiny_diffusion_amd._lib import lib, check  # noqa: E402
+from tiny_diffusion_amd._lib import lib, check, tuned  # noqa: E402
 
 LAYERS = [("enc1.0", 64, 128, 28), ("enc1.3", 128, 128, 28), ("enc2.0", 128, 256, 14), ("enc2.3", 256, 256, 14),
           ("enc3.0", 256, 512, 7), ("enc3.3", 512, 512, 7), ("bottleneck", 512, 512, 4), ("dec3.0", 1024, 256, 8),
@@ -43,10 +43,9 @@ def probe(fn, nst):
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) / 20 * 1e3
     stamps.zero_()
-    check(lib.tdx_tune_set(b"conv_stamp", 3))
-    fn()
-    torch.cuda.synchronize()
-    check(lib.tdx_tune_set(b"conv_stamp", 0))
+    with tuned(conv_stamp=3):
+        fn()
+        torch.cuda.synchronize()
     s = stamps.cpu().view(-1, 8)
     s = s[s[:, 4] > 0]
     t00 = int(s[:, 0].min())
