@@ -229,6 +229,32 @@ int tdx_p_sample_update_dyn(float* x_out, const float* x, const float* out, int6
                             const float* known, const float* mask, int64_t* counter_dec, float* thr, int per,
                             tdx_stream_t stream);
 
+/* The per-sample sums of the variational bound on the negative log-likelihood (Ho et al. 2020 eq. 5; Nichol & Dhariwal
+ * 2021, calc_bpd_loop): what tiny_diffusion_amd.likelihood turns into bits per dimension.
+ * rows: device table (T,5) fp32 of (p, q, ex, eo, dec).  Sample b uses row t[b].  Per element, fp32, every
+ * operation rounded separately, in this order (x = x_t, o = out):
+ *   u = p*x + q*o;  x0c = min(max(u, clip_lo), clip_hi);  d = x0 - x0c;  e = noise - (ex*x + eo*o)
+ * terms[b*sample_stride + 0] = sum_j e^2      (0 when noise == NULL)
+ * terms[b*sample_stride + 1] = sum_j d^2
+ * terms[b*sample_stride + 2] = dec > 0 && bins ? sum_j -log P_j : 0
+ * P_j, with s = dec (1/sigma of the decoder), half = (data_hi - data_lo) / (2 (bins - 1)), a = (d + half) s,
+ * b = (d - half) s, Phi the standard normal CDF:
+ *   x0 < data_lo + half: Phi(a)      x0 > data_hi - half: 1 - Phi(b)      else: Phi(a) - Phi(b)
+ * floored at 1e-12 before the log.  Every CDF is evaluated as a tail, Phi(z) = erfc(-z / sqrt 2) / 2, the interior
+ * difference on the side where both tails are small (d > 0: Phi(-b) - Phi(-a)), subtracted before the floor; half and
+ * the two edges are fp32 expressions of the host.
+ * One workgroup per sample, 16-byte loads, one pass over the four inputs (16 B/element); the three sums are reduced
+ * inside the wave, then across the waves through LDS in a fixed order (no global atomics): a sample's three numbers are
+ * bit-reproducible and do not depend on batch or on the other samples.  sample_stride (floats, >= 3) lets a caller
+ * write column t of a (B, T, 3) buffer directly.  t is not range-checked, as in tdx_q_sample.  A row (0, 0, 0, 0, 0) with
+ * infinite clip bounds gives d = x0: slot 1 is then sum_j x0^2 (the prior term).
+ * TDX_E_BADARG, before any GPU call and with nothing written: a null pointer other than noise, batch <= 0,
+ * per_sample <= 0, per_sample % 4, sample_stride < 3, not clip_lo < clip_hi (infinite bounds are allowed, NaN is not),
+ * bins == 1 or bins < 0, and with bins >= 2 a data range that is not finite with data_lo < data_hi. */
+int tdx_vlb_terms(const float* x0, const float* x_t, const float* out, const float* noise, const int64_t* t,
+                  const float* rows, int batch, int per_sample, float clip_lo, float clip_hi, float data_lo,
+                  float data_hi, int bins, float* terms, int64_t sample_stride, tdx_stream_t stream);
+
 /* Condition dropout for training the unconditional branch: sample b is dropped iff a Philox uniform in [0,1) keyed by
  * (seed, offset, b) is < p (p == 0: exact copy, p == 1: every sample).  A dropped sample gets label -1 / a zeroed row.
  * The two entries draw the same mask for the same key.  In place (y_out == y, c_out == c) is allowed. */

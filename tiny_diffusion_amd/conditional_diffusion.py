@@ -8,10 +8,11 @@ from typing import Optional
 
 import torch
 
+from .likelihood import bits_per_dim_loop
 from .schedule import ForwardProcess, ddim_sample_loop, dpm_sample_loop, sample_loop
 from .unet import NoiseModelBase, TIME_DIM
 
-__all__ = ["NoiseModel", "ForwardProcess", "sample", "ddim_sample", "dpm_sample"]
+__all__ = ["NoiseModel", "ForwardProcess", "sample", "ddim_sample", "dpm_sample", "bits_per_dim"]
 
 
 class NoiseModel(NoiseModelBase):
@@ -66,6 +67,17 @@ def dpm_sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_sam
     _check_labels(y, n_samples)
     return dpm_sample_loop(noise_model, diffusion, device, n_samples, y, steps=steps, order=order, spacing=spacing,
                            timesteps=timesteps, guidance_scale=guidance_scale, **kw)
+
+
+def bits_per_dim(noise_model: NoiseModel, diffusion: ForwardProcess, x_0, y=None, bins=256, clip_denoised=True, **kw):
+    """The variational bound on the negative log-likelihood of ``x_0`` in bits per dimension (Ho et al. 2020 eq. 5;
+    likelihood.bits_per_dim_loop): ``BitsPerDim(total_bpd, prior_bpd, vb, mse, xstart_mse)`` over all T timesteps,
+    under the labels ``y``.  The defaults are Ho et al.'s and improved-DDPM's settings for pixels: the discretised decoder over 256 levels of
+    [-1, 1] and the clamped x0 prediction.  ``noises`` / ``philox_seed``, ``prediction``, ``variance`` and
+    ``data_range`` pass through."""
+    if y is None:
+        raise ValueError("Class labels 'y' must be provided for conditional generation.")
+    return bits_per_dim_loop(noise_model, diffusion, x_0, y, bins=bins, clip_denoised=clip_denoised, **kw)
 
 
 def _check_labels(y, n_samples):

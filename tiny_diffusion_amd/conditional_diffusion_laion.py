@@ -14,10 +14,12 @@ from typing import Optional
 import torch
 
 from . import _lib
+from .likelihood import bits_per_dim_loop
 from .schedule import ForwardProcess as _ForwardProcess, ddim_sample_loop, dpm_sample_loop, sample_loop
 from .unet import ARCH_LAION, NoiseModelBase
 
-__all__ = ["NoiseModel", "ForwardProcess", "get_timestep_embedding", "sample", "ddim_sample", "dpm_sample", "postprocess_images"]
+__all__ = ["NoiseModel", "ForwardProcess", "get_timestep_embedding", "sample", "ddim_sample", "dpm_sample", "bits_per_dim",
+           "postprocess_images"]
 
 TIME_DIM = ARCH_LAION.time_dim
 
@@ -118,6 +120,18 @@ def dpm_sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, text_
     x = dpm_sample_loop(noise_model, diffusion, device, n_samples, text_embeds, steps=steps, order=order,
                         spacing=spacing, timesteps=timesteps, guidance_scale=guidance_scale, **kw)
     return _decode(x, vae, scaling_factor)
+
+
+def bits_per_dim(noise_model: NoiseModel, diffusion: ForwardProcess, x_0, text_embeds=None, bins=None,
+                 clip_denoised=None, **kw):
+    """The variational bound on the negative log-density of the latents ``x_0`` in bits per dimension (Ho et al. 2020
+    eq. 5; likelihood.bits_per_dim_loop): ``BitsPerDim(total_bpd, prior_bpd, vb, mse, xstart_mse)`` over all T timesteps
+    under the condition ``text_embeds``.  The defaults suit latents: a continuous Gaussian decoder at t = 0 and no
+    clamp, so the result is a density and can be negative.  ``noises`` / ``philox_seed``, ``prediction``, ``variance``, ``bins``
+    and ``data_range`` pass through."""
+    if text_embeds is None:
+        raise ValueError("Text embeddings must be provided for conditional generation.")
+    return bits_per_dim_loop(noise_model, diffusion, x_0, text_embeds, bins=bins, clip_denoised=clip_denoised, **kw)
 
 
 def _decode(x, vae, scaling_factor):

@@ -5,10 +5,11 @@ from __future__ import annotations
 
 import torch
 
+from .likelihood import bits_per_dim_loop
 from .schedule import ForwardProcess, ddim_sample_loop, dpm_sample_loop, sample_loop
 from .unet import NoiseModelBase, TIME_DIM
 
-__all__ = ["NoiseModel", "ForwardProcess", "sample", "ddim_sample", "dpm_sample"]
+__all__ = ["NoiseModel", "ForwardProcess", "sample", "ddim_sample", "dpm_sample", "bits_per_dim"]
 
 
 class NoiseModel(NoiseModelBase):
@@ -56,3 +57,12 @@ def dpm_sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_sam
     prediction); ``philox_seed`` only selects the graph mode."""
     return dpm_sample_loop(noise_model, diffusion, device, n_samples, None, steps=steps, order=order, spacing=spacing,
                            timesteps=timesteps, **kw)
+
+
+def bits_per_dim(noise_model: NoiseModel, diffusion: ForwardProcess, x_0, bins=256, clip_denoised=True, **kw):
+    """The variational bound on the negative log-likelihood of ``x_0`` in bits per dimension (Ho et al. 2020 eq. 5;
+    likelihood.bits_per_dim_loop): ``BitsPerDim(total_bpd, prior_bpd, vb, mse, xstart_mse)`` over all T timesteps.
+    The defaults are Ho et al.'s and improved-DDPM's settings for pixels: the discretised decoder over 256 levels of
+    [-1, 1] and the clamped x0 prediction.  ``noises`` / ``philox_seed``, ``prediction``, ``variance`` and
+    ``data_range`` pass through."""
+    return bits_per_dim_loop(noise_model, diffusion, x_0, None, bins=bins, clip_denoised=clip_denoised, **kw)

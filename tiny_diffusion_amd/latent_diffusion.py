@@ -7,11 +7,12 @@ from __future__ import annotations
 
 import torch
 
+from .likelihood import bits_per_dim_loop
 from .schedule import ForwardProcess, ddim_sample_loop, dpm_sample_loop, sample_loop
 from .unet import ARCH_LATENT, NoiseModelBase
 from .vae import VAE, VAEConfig, VAETrainStep
 
-__all__ = ["NoiseModel", "ForwardProcess", "sample", "ddim_sample", "dpm_sample", "VAE", "VAEConfig",
+__all__ = ["NoiseModel", "ForwardProcess", "sample", "ddim_sample", "dpm_sample", "bits_per_dim", "VAE", "VAEConfig",
            "VAETrainStep"]
 
 
@@ -70,6 +71,17 @@ def dpm_sample(vae: VAE, noise_model: NoiseModel, diffusion: ForwardProcess, dev
     z = dpm_sample_loop(noise_model, diffusion, device, n_samples, y, steps=steps, order=order, spacing=spacing,
                         timesteps=timesteps, **kw)
     return vae.decode(z).view(-1, 1, 28, 28)
+
+
+def bits_per_dim(noise_model: NoiseModel, diffusion: ForwardProcess, x_0, y=None, bins=None, clip_denoised=None, **kw):
+    """The variational bound on the negative log-density of the latents ``x_0`` in bits per dimension (Ho et al. 2020
+    eq. 5; likelihood.bits_per_dim_loop): ``BitsPerDim(total_bpd, prior_bpd, vb, mse, xstart_mse)`` over all T timesteps
+    under the condition ``y``.  The defaults suit latents: a continuous Gaussian decoder at t = 0 and no clamp, so
+    the result is a density and can be negative.  ``noises`` / ``philox_seed``, ``prediction``, ``variance``, ``bins``
+    and ``data_range`` pass through."""
+    if y is None:
+        raise ValueError("Class labels 'y' must be provided for conditional generation.")
+    return bits_per_dim_loop(noise_model, diffusion, x_0, y, bins=bins, clip_denoised=clip_denoised, **kw)
 
 
 def _check_labels(y, n_samples):
