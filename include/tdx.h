@@ -290,6 +290,47 @@ int tdx_mse_loss_grad_weighted(const float* a, const float* b, const int64_t* t,
                                float* loss_out, float* d_a, float gscale, int batch, int per_sample, void* scratch,
                                tdx_stream_t stream);
 
+/* Training timestep sampling (additions within ABI 400; csrc/timestep.hip): which timestep each sample
+ * of a training step sees, from a fixed (T,) probability table or from the loss-second-moment resampler of Nichol &
+ * Dhariwal 2021 (3.3).  Every entry: one stream, no allocation, no atomics on global memory, no host synchronisation
+ * (capturable), bit-reproducible.  TDX_E_BADARG, nothing launched: a null pointer that is not marked optional, a size
+ * <= 0, H < 1, a uniform_prob outside [0, 1].
+ *
+ * tdx_timestep_cdf: probs (T,) >= 0 and not all zero (negative and NaN entries count as 0; an all-zero table gives the
+ * uniform one), one workgroup.  p = probs / sum(probs) and its inclusive prefix sum in double, in a fixed order,
+ * rounded once: cdf[k] = fl(sum_{j<=k} p_j) - non-decreasing - and EXACTLY 1.0f from the last k with p_k > 0 on, so that
+ * a trailing zero-probability timestep cannot be drawn when the running sum rounds below 1 (leading and interior zeros
+ * are skipped by the strict comparison of the draw).  w_eff[k] = fl(w_obj[k] / (T p_k)) with importance != 0 (the
+ * weight that keeps E_p[w_eff L] = mean_t w_obj L_t), else w_obj[k]; 0 where p_k == 0.  w_obj == NULL: ones. */
+int tdx_timestep_cdf(const float* probs, const float* w_obj, int importance, float* cdf, float* w_eff, int T,
+                     tdx_stream_t stream);
+/* t_out[b] = #{k : cdf[k] <= u_b} (np.searchsorted(cdf, u, side="right"), by binary search; clamped to T - 1) with
+ * u_b = (v[1] >> 8) * 2^-24 in [0, 1), v the Philox4x32-10 block of counter (b, offset) under key seed - word 1, while
+ * tdx_cond_drop_* compares word 0 of the same block with its p.  u_out (B,): NULL, or receives u (tests).  rng_dev: NULL,
+ * or two device uint64 {seed, offset} read INSTEAD of the by-value pair, as in tdx_transformer_loss_grads (a captured
+ * step draws fresh timesteps at every replay). */
+int tdx_timestep_draw(const float* cdf, int T, int64_t* t_out, float* u_out, int B, uint64_t seed, uint64_t offset,
+                      const uint64_t* rng_dev, tdx_stream_t stream);
+/* loss_b[s] = fl(w_obj[t[s]] * sum_j (a[s,j] - b[s,j])^2 / per_sample): the loss of every sample on its own, a pass
+ * beside tdx_mse_loss_grad* (whose element -> block mapping stays as it is).  One workgroup of 256 per sample, 16-byte
+ * loads when a and b are 16-byte aligned and per_sample % 4 == 0, differences, squares and sums in double in a fixed
+ * order, one rounding.  w_obj == NULL: weight 1, and t may then be NULL too.  t is not range-checked. */
+int tdx_mse_per_sample(const float* a, const float* b, const int64_t* t, const float* w_obj, float* loss_b, int batch,
+                       int per_sample, tdx_stream_t stream);
+/* The resampler's state and table, one workgroup.  history (T,H) holds the last H losses of every timestep, oldest
+ * first, counts (T,) int32 how many are valid (both zero at the start).  1. The state after the call is that of
+ * applying samples b = 0 .. B-1 IN BATCH ORDER - counts[t_b] < H appends, a full row drops its oldest entry and appends:
+ * improved-DDPM's sequential update, duplicates of a timestep inside the batch included (each sample's place follows
+ * from how many samples of its timestep come before it; no atomics); a t_b outside [0, T) is skipped.  T <= 4096
+ * (TDX_E_SHAPE otherwise: the per-timestep moments of phase 3 live in LDS).  2. Warmed up iff every counts[k] == H.  3. Not warmed up: cdf[k] = fl((k + 1) / T), w_eff =
+ * w_obj, exactly.  Warmed up: w_k = sqrt(mean_h history[k,h]^2), p = w / sum(w), p = p (1 - uniform_prob) +
+ * uniform_prob / T in double, then cdf and w_eff as tdx_timestep_cdf writes them with importance = 1 (all-zero
+ * losses: the uniform p).  B == 0 (t and loss_b may be NULL) only rebuilds cdf / w_eff from the state: after loading
+ * one, or when w_obj changed. */
+int tdx_timestep_history_update(const int64_t* t, const float* loss_b, int B, float* history, int32_t* counts, int H,
+                                float uniform_prob, const float* w_obj, float* cdf, float* w_eff, int T,
+                                tdx_stream_t stream);
+
 /* Adam, torch defaults (diffusion.py:211/236): one fused pass over a flat
  * parameter buffer, 28 B/param.  step is the 1-based step count. */
 int tdx_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,

@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import lib, check
-from .schedule import _prediction, _snr_gamma, loss_weights
+from .schedule import _prediction, _snr_gamma, loss_weights, timestep_probs
 
 
 # ---------------------------------------------------------------- arguments
@@ -33,6 +33,11 @@ def _seed_arg(v, what):
     if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 64):
         raise ValueError(f"{what} must be None or an integer in [0, 2**64)")
     return v
+
+
+def _i64(v: int) -> int:
+    """A uint64 as the int64 with the same bits (torch has no uint64 arithmetic; the kernels read the words as uint64)."""
+    return v - 2 ** 64 if v >= 2 ** 63 else v
 
 
 def _betas_arg(betas):
@@ -93,6 +98,10 @@ class FlatStep:
     """Base of the fused training steps.  A subclass's constructor checks its arguments, calls ``_init_optimizer`` and
     then ``_flatten`` (the first device work).  For ``use_graph`` it provides ``_alloc_static`` and ``_static_step`` and
     drives ``_graph_ready`` / ``_replay``; for the workspace cache ``_workspace_floats``."""
+
+    # a step without timesteps (the VAE's) never calls _check_timestep_sampler
+    timestep_sampler = sample_losses = last_t = None
+    importance_weights = False
 
     def _init_optimizer(self, lr, betas, eps, max_grad_norm, ema_decay=None, ema_warmup=False, use_graph=False):
         self.lr, self.betas, self.eps, self.max_grad_norm = lr, betas, eps, max_grad_norm
@@ -221,10 +230,156 @@ class FlatStep:
         """Change the training objective of an existing step (the constructor's three keywords, same errors): the
         parameters, optimizer state and plans stay; a captured step is dropped and captured again on the next calls,
         because the graph holds the launches of the objective it was captured with.  The defaults give back exactly the
-        default step's launches (``tools/gpu_objective_cost.py`` alternates the two on one step)."""
+        default step's launches (``tools/gpu_objective_cost.py`` alternates the two on one step).  Under a
+        ``timestep_sampler`` the step's own weights are rebuilt from the new table; the loss history stays."""
         self._check_objective(prediction, loss_weighting, snr_gamma)
         self._upload_weights()
+        self._rebuild_timestep_table()
         self._drop_graph()
+
+    # ------------------------------------------------------- timestep sampler
+    # Which timestep each sample sees when step() is not given one (DESIGN.md 3.19).  The sampler's state is device
+    # memory of the step: the CDF the draw inverts (_ts_cdf), the weights the loss entries read in place of _w_table
+    # (_w_eff = objective weight / (T p_t) under importance weights), and for "loss_second_moment" the loss history.
+    def _check_timestep_sampler(self, timestep_sampler, importance_weights, timestep_seed, history_per_term, uniform_prob):
+        """Validate and record the five keywords (``ValueError`` before any device work).  Without a sampler nothing
+        else of this section ever runs: the step draws ``torch.randint`` and allocates nothing."""
+        T = int(self.diffusion.num_timesteps)
+        if importance_weights is not None and not isinstance(importance_weights, bool):
+            raise ValueError("importance_weights must be None, True or False")
+        if isinstance(timestep_seed, bool) or not isinstance(timestep_seed, int) or not 0 <= timestep_seed < 2 ** 64:
+            raise ValueError("timestep_seed must be an integer in [0, 2**64)")
+        if isinstance(history_per_term, bool) or not isinstance(history_per_term, int) or history_per_term < 1:
+            raise ValueError("history_per_term must be an integer >= 1")
+        if not 0.0 <= _number(uniform_prob, "uniform_prob") <= 1.0:
+            raise ValueError("uniform_prob must lie in [0, 1]")
+        self._ts_probs_cpu = None
+        if timestep_sampler is None:
+            self.timestep_sampler = None
+        elif isinstance(timestep_sampler, str):
+            if timestep_sampler != "loss_second_moment":
+                raise ValueError(f"timestep_sampler must be None, 'loss_second_moment' or a ({T},) table of "
+                                 f"probabilities, got {timestep_sampler!r}")
+            if T > 4096:
+                raise ValueError(f"timestep_sampler='loss_second_moment' covers T <= 4096 (tdx_timestep_history_update), "
+                                 f"the diffusion has T = {T}")
+            self.timestep_sampler = "loss_second_moment"
+        else:
+            self._ts_probs_cpu = timestep_probs(T, timestep_sampler)
+            self.timestep_sampler = "table"
+        adaptive = self.timestep_sampler == "loss_second_moment"
+        self.importance_weights = (adaptive if importance_weights is None else importance_weights) \
+            and self.timestep_sampler is not None
+        self.timestep_seed, self.history_per_term, self.uniform_prob = timestep_seed, history_per_term, float(uniform_prob)
+        self.sample_losses = None   # (B,) device tensor: every sample's objective-weighted loss of the last step
+        self.last_t = None          # (B,) the timesteps of the last step under a sampler
+        self._ts_cdf = self._w_eff = self._ts_probs = self._ts_history = self._ts_counts = self._ts_rng = None
+        self._sl = {}               # batch size -> its sample_losses buffer (a captured step holds its address)
+
+    def _init_timestep_sampler(self):
+        """The sampler's device buffers and first table; after ``_upload_weights``."""
+        if self.timestep_sampler is None:
+            return
+        T, dev = int(self.diffusion.num_timesteps), self.device
+        self._ts_cdf = torch.empty(T, dtype=torch.float32, device=dev)
+        self._w_eff = torch.empty(T, dtype=torch.float32, device=dev)
+        if self.timestep_sampler == "table":
+            self._ts_probs = self._ts_probs_cpu.to(dev)
+        else:
+            self._ts_history = torch.zeros(T, self.history_per_term, dtype=torch.float32, device=dev)
+            self._ts_counts = torch.zeros(T, dtype=torch.int32, device=dev)
+        self._rebuild_timestep_table()
+
+    def _rebuild_timestep_table(self):
+        """``_ts_cdf`` and ``_w_eff`` from the probabilities (the fixed table, or the loss history as it stands) and
+        the objective's weights, through the device entries."""
+        if self.timestep_sampler is None:
+            return
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        T = int(self.diffusion.num_timesteps)
+        w_obj = None if self._w_table is None else self._w_table.data_ptr()
+        if self.timestep_sampler == "table":
+            check(lib.tdx_timestep_cdf(self._ts_probs.data_ptr(), w_obj, 1 if self.importance_weights else 0,
+                                       self._ts_cdf.data_ptr(), self._w_eff.data_ptr(), T, st), "tdx_timestep_cdf")
+        else:
+            self._history_update(None, None, 0, st)
+
+    def _history_update(self, t, loss_b, B, st):
+        check(lib.tdx_timestep_history_update(None if t is None else t.data_ptr(),
+                                              None if loss_b is None else loss_b.data_ptr(), B,
+                                              self._ts_history.data_ptr(), self._ts_counts.data_ptr(),
+                                              self.history_per_term, self.uniform_prob,
+                                              None if self._w_table is None else self._w_table.data_ptr(),
+                                              self._ts_cdf.data_ptr(), self._w_eff.data_ptr(),
+                                              int(self.diffusion.num_timesteps), st), "tdx_timestep_history_update")
+
+    def _loss_table(self):
+        """The (T,) device weights the loss entry of this step reads; None: the unweighted entry.  Without a sampler
+        the objective's table as it always was; with one the step's own ``_w_eff`` whenever it can differ from ones."""
+        if self.timestep_sampler is None:
+            return self._w_table
+        if not self.importance_weights and (self._w_table is None or self.timestep_sampler == "loss_second_moment"):
+            return self._w_table    # (the history entry always writes the importance weights of its table into _w_eff)
+        return self._w_eff
+
+    def _draw_t(self, B, offset, st=None, rng_dev=None, out=None):
+        """``t`` (B,) int64 from the sampler's CDF, keyed by ``(timestep_seed, offset, b)`` - or by the two device
+        words ``rng_dev`` that a captured step refreshes before each replay."""
+        t = torch.empty(B, dtype=torch.int64, device=self.device) if out is None else out
+        if st is None:
+            st = torch.cuda.current_stream(self.device).cuda_stream
+        check(lib.tdx_timestep_draw(self._ts_cdf.data_ptr(), int(self.diffusion.num_timesteps), t.data_ptr(), None, B,
+                                    self.timestep_seed, offset, None if rng_dev is None else rng_dev.data_ptr(), st),
+              "tdx_timestep_draw")
+        return t
+
+    def _sample_losses_buf(self, B):
+        buf = self._sl.get(B)
+        if buf is None:
+            buf = self._sl[B] = torch.zeros(B, dtype=torch.float32, device=self.device)
+        return buf
+
+    def _after_loss(self, pred, target, t, B, st=None):
+        """After the loss launch of a step under a sampler: every sample's loss (``sample_losses``: the objective's
+        weight times its mean squared error - not the importance weight, which would feed the sampler its own output)
+        and, for the adaptive sampler, the history update that also writes the next step's ``_ts_cdf`` / ``_w_eff``."""
+        if st is None:
+            st = torch.cuda.current_stream(self.device).cuda_stream
+        self.last_t = t
+        self.sample_losses = out = self._sample_losses_buf(B)
+        check(lib.tdx_mse_per_sample(pred.data_ptr(), target.data_ptr(), t.data_ptr(),
+                                     None if self._w_table is None else self._w_table.data_ptr(), out.data_ptr(), B,
+                                     pred.numel() // B, st), "tdx_mse_per_sample")
+        if self.timestep_sampler == "loss_second_moment":
+            self._history_update(t, out, B, st)
+
+    def timestep_sampler_state(self):
+        """``{"history": (T, H) fp32, oldest first, "counts": (T,) int32}`` of the adaptive sampler, on the CPU (a
+        checkpoint entry; it synchronises)."""
+        if self.timestep_sampler != "loss_second_moment":
+            raise RuntimeError("timestep_sampler_state() needs timestep_sampler='loss_second_moment'")
+        return {"history": self._ts_history.cpu(), "counts": self._ts_counts.cpu()}
+
+    def load_timestep_sampler_state(self, state):
+        """Inverse of ``timestep_sampler_state()``: shapes and the range of the counts are checked (``ValueError``),
+        then the table the next step draws from is rebuilt on the device."""
+        if self.timestep_sampler != "loss_second_moment":
+            raise RuntimeError("load_timestep_sampler_state() needs timestep_sampler='loss_second_moment'")
+        T, H = int(self.diffusion.num_timesteps), self.history_per_term
+        try:
+            hist, counts = state["history"], state["counts"]
+        except (TypeError, KeyError, IndexError):
+            raise ValueError("the sampler state is a dict with 'history' and 'counts'") from None
+        hist, counts = torch.as_tensor(hist), torch.as_tensor(counts)
+        if tuple(hist.shape) != (T, H) or not hist.dtype.is_floating_point:
+            raise ValueError(f"history must be a floating-point ({T},{H}) tensor, got {tuple(hist.shape)}")
+        if tuple(counts.shape) != (T,) or counts.dtype.is_floating_point or counts.dtype == torch.bool:
+            raise ValueError(f"counts must be an integer ({T},) tensor, got {tuple(counts.shape)}")
+        if not torch.isfinite(hist).all() or (counts < 0).any() or (counts > H).any():
+            raise ValueError(f"history must be finite and counts in [0, {H}]")
+        self._ts_history.copy_(hist.to(torch.float32))
+        self._ts_counts.copy_(counts.to(torch.int32))
+        self._rebuild_timestep_table()
 
     def _q_sample(self, x_0, t, noise, offset):
         """``(x_t, target)`` from the forward process's entries: the target is the noise, or v (written by the same

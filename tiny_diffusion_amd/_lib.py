@@ -67,6 +67,11 @@ _SIGS = {
     "tdx_mse_scratch_bytes": (C.c_size_t, []),
     "tdx_mse_loss_grad": (C.c_int, [_ptr, _ptr, _ptr, _ptr, C.c_float, C.c_int64, _ptr, _ptr]),
     "tdx_mse_loss_grad_weighted": (C.c_int, [_ptr] * 6 + [C.c_float, C.c_int, C.c_int, _ptr, _ptr]),
+    "tdx_timestep_cdf": (C.c_int, [_ptr, _ptr, C.c_int, _ptr, _ptr, C.c_int, _ptr]),
+    "tdx_timestep_draw": (C.c_int, [_ptr, C.c_int, _ptr, _ptr, C.c_int, C.c_uint64, C.c_uint64, _ptr, _ptr]),
+    "tdx_mse_per_sample": (C.c_int, [_ptr] * 5 + [C.c_int, C.c_int, _ptr]),
+    "tdx_timestep_history_update": (C.c_int, [_ptr, _ptr, C.c_int, _ptr, _ptr, C.c_int, C.c_float, _ptr, _ptr, _ptr,
+                                              C.c_int, _ptr]),
     "tdx_adam_step": (C.c_int, [_ptr, _ptr, _ptr, _ptr, C.c_int64, C.c_float, C.c_float, C.c_float,
                                 C.c_float, C.c_int, C.c_float, _ptr]),
     "tdx_adam_clip_scratch_bytes": (C.c_size_t, []),

@@ -20,8 +20,8 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import check, lib
-from ._flat_step import (FlatStep, _betas_arg, _ema_args, _max_grad_norm_arg, _number, _seed_arg, cosine_annealing_lr,
-                         ema_decay_at)
+from ._flat_step import (FlatStep, _betas_arg, _ema_args, _i64, _max_grad_norm_arg, _number, _seed_arg,
+                         cosine_annealing_lr, ema_decay_at)
 from .likelihood import bits_per_dim_loop
 from .schedule import ForwardProcess, ddim_sample_loop, dpm_sample_loop, sample_loop
 from .vae import VAE, VAEConfig
@@ -189,11 +189,6 @@ class _TShape(C.Structure):
                 ("num_layers", C.c_int), ("num_classes", C.c_int), ("dropout_p", C.c_float), ("ln_eps", C.c_float)]
 
 
-def _i64(v: int) -> int:
-    """A uint64 as the int64 with the same bits (torch has no uint64 arithmetic; the kernels read the words as uint64)."""
-    return v - 2 ** 64 if v >= 2 ** 63 else v
-
-
 class TransformerTrainStep(FlatStep):
     """The optimisation step of the transformer's training loop (diffusion_transformer.py:193-202: ``randint``,
     ``q_sample``, forward, ``F.mse_loss``, ``zero_grad``, ``backward``, ``optimizer.step``) as one short chain of libtdx
@@ -223,6 +218,12 @@ class TransformerTrainStep(FlatStep):
     the very masks of ``model(z_t, t, y)`` under the same seed.  ``dropout_seed=int``: that key with offset
     ``step_count * 4 * num_layers``.  ``last_dropout_seed`` / ``last_dropout_offset`` hold what the last step used.
 
+    ``timestep_sampler`` / ``importance_weights`` / ``timestep_seed`` / ``history_per_term`` / ``uniform_prob``: as in
+    ``train.TrainStep`` - a ``(T,)`` probability table or ``"loss_second_moment"`` replaces ``torch.randint`` by a
+    Philox draw on the device keyed by ``(timestep_seed, step_count, sample)``; ``sample_losses``, ``last_t`` and
+    ``timestep_sampler_state()`` come with it.  A captured step draws into its static ``t`` right before the replay and
+    runs the sampler's other launches inside the graph, so it sees the timesteps and leaves the state of an eager one.
+
     ``use_graph=True``: the first step with a batch size runs eagerly, the second is captured into a HIP graph, later
     ones replay it; inputs, Adam's step-dependent scalars and the dropout ``{seed, offset}`` live in static device
     buffers refreshed before each replay.  With ``philox_seed`` the step stays eager.
@@ -234,7 +235,9 @@ class TransformerTrainStep(FlatStep):
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, max_grad_norm: Optional[float] = None,
                  prediction: str = "eps", loss_weighting=None, snr_gamma: float = 5.0,
                  ema_decay: Optional[float] = None, ema_warmup: bool = False, philox_seed: Optional[int] = None,
-                 dropout_seed: Optional[int] = None, use_graph: bool = False):
+                 dropout_seed: Optional[int] = None, use_graph: bool = False, timestep_sampler=None,
+                 importance_weights=None, timestep_seed: int = 0, history_per_term: int = 10,
+                 uniform_prob: float = 0.001):
         if not isinstance(model, NoiseModel):
             raise ValueError("TransformerTrainStep needs a diffusion_transformer.NoiseModel")
         if not isinstance(diffusion, ForwardProcess):
@@ -243,6 +246,7 @@ class TransformerTrainStep(FlatStep):
         max_grad_norm = _max_grad_norm_arg(max_grad_norm)
         self.model, self.diffusion = model, diffusion
         self._check_objective(prediction, loss_weighting, snr_gamma)
+        self._check_timestep_sampler(timestep_sampler, importance_weights, timestep_seed, history_per_term, uniform_prob)
         self._init_optimizer(lr, betas, eps, max_grad_norm, *_ema_args(ema_decay, ema_warmup), use_graph=bool(use_graph))
         self.philox_seed = _seed_arg(philox_seed, "philox_seed")
         self.dropout_seed = _seed_arg(dropout_seed, "dropout_seed")
@@ -270,6 +274,7 @@ class TransformerTrainStep(FlatStep):
         self._upload_weights()
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._gz = self._gy = self._gt = self._gnoise = self._grng = None
+        self._init_timestep_sampler()
 
     # ------------------------------------------------------------------ setup
     def _params(self):
@@ -319,20 +324,29 @@ class TransformerTrainStep(FlatStep):
         return seed, 0
 
     def _loss_grads(self, z_t, t, y, target, B, loss, grads: bool, train: bool, rng, rng_dev=None, eps_hat=None):
+        """``grads``: the training step - its loss weights are the sampler's where there is one (``_loss_table``);
+        ``evaluate()`` reads the objective's own."""
         st = torch.cuda.current_stream(self.device).cuda_stream
+        w_table = self._loss_table() if grads else self._w_table
         check(lib.tdx_transformer_loss_grads(C.byref(self._shape(B)), self._p_ptrs, self._g_ptrs if grads else None,
                                              z_t.data_ptr(), t.data_ptr(), y.data_ptr(), target.data_ptr(),
-                                             None if self._w_table is None else self._w_table.data_ptr(),
+                                             None if w_table is None else w_table.data_ptr(),
                                              1 if train else 0, rng[0], rng[1],
                                              None if rng_dev is None else rng_dev.data_ptr(), 1.0, loss.data_ptr(),
                                              None if eps_hat is None else eps_hat.data_ptr(),
                                              self._workspace(B).data_ptr(), st), "tdx_transformer_loss_grads")
 
     def _eager_step(self, z_0, y, t, noise, B, rng, hyper=None, rng_dev=None):
-        if t is None:
+        sampler = self.timestep_sampler is not None
+        if t is None and sampler:
+            t = self._draw_t(B, self.step_count)
+        elif t is None:
             t = torch.randint(0, self.diffusion.num_timesteps, (B,), device=self.device)   # line 193
         z_t, target = self._q_sample(z_0, t, noise, self.step_count)                         # line 196
-        self._loss_grads(z_t, t, y, target, B, self.loss, True, self.model.training, rng, rng_dev)   # lines 197-201
+        eps_hat = torch.empty_like(target) if sampler else None
+        self._loss_grads(z_t, t, y, target, B, self.loss, True, self.model.training, rng, rng_dev, eps_hat)   # lines 197-201
+        if sampler:
+            self._after_loss(eps_hat, target, t, B)
         self.last_dropout_seed, self.last_dropout_offset = rng
         self.step_count += 1
         self._adam(hyper)                                                                    # line 202
@@ -356,7 +370,10 @@ class TransformerTrainStep(FlatStep):
         rng = self._next_rng()
         self._gz.copy_(z_0)
         self._gy.copy_(y)
-        if t is None:
+        sampler = self.timestep_sampler is not None
+        if t is None and sampler:
+            self._draw_t(B, self.step_count, out=self._gt)      # from the table the replay before this one left
+        elif t is None:
             self._gt.random_(0, self.diffusion.num_timesteps)   # outside the graph: torch's generator advances as in
         else:                                                    # the eager step (randint, then randn_like)
             self._gt.copy_(t)
@@ -366,6 +383,8 @@ class TransformerTrainStep(FlatStep):
             self._gnoise.copy_(noise)
         self._grng.copy_(torch.tensor([_i64(rng[0]), _i64(rng[1])], dtype=torch.int64))
         self.last_dropout_seed, self.last_dropout_offset = rng
+        if sampler:   # what the replay writes
+            self.last_t, self.sample_losses = self._gt, self._sample_losses_buf(B)
         return self._replay()
 
     def _alloc_static(self, B):

@@ -253,6 +253,46 @@ def loss_weights(diffusion: ForwardProcess, prediction: str = "eps", weighting="
     return w.to(torch.float32).contiguous()
 
 
+def logit_normal_timestep_probs(T: int, mean: float = 0.0, std: float = 1.0):
+    """A ``(T,)`` fp64 probability table for ``TrainStep(timestep_sampler=...)``: the logit-normal density (Esser et
+    al. 2024; Karras et al. 2022 train on a normal in log-sigma) at the bin centres ``s = (t + 0.5) / T``,
+    ``exp(-(logit(s) - mean)^2 / (2 std^2)) / (s (1 - s))``, normalised to sum 1 - the batch is spent in the middle of
+    the noise range; ``mean`` shifts it (positive: towards large t), ``std`` widens it."""
+    if isinstance(T, bool) or not isinstance(T, numbers.Integral) or T < 1:
+        raise ValueError("T must be an integer >= 1")
+    for name, v in (("mean", mean), ("std", std)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite number")
+    if not std > 0:
+        raise ValueError("std must be > 0")
+    s = (torch.arange(int(T), dtype=torch.float64) + 0.5) / int(T)
+    z = (torch.log(s) - torch.log1p(-s) - float(mean)) / float(std)
+    p = torch.exp(-0.5 * z * z) / (s * (1.0 - s))
+    return p / p.sum()
+
+
+def timestep_probs(T: int, table):
+    """A user's ``(T,)`` timestep probability table, checked: fp32 on the CPU (what the device entry reads; it
+    normalises in double itself).  ``ValueError`` unless it is a real tensor / array of exactly T finite entries >= 0,
+    not all zero (after the rounding to fp32)."""
+    if isinstance(table, np.ndarray):
+        table = torch.from_numpy(table)
+    if not isinstance(table, torch.Tensor):
+        raise ValueError(f"timestep_sampler must be None, 'loss_second_moment' or a ({T},) table of probabilities, got "
+                         f"{table!r}")
+    if table.dtype == torch.bool or table.is_complex():
+        raise ValueError("a timestep probability table must hold real numbers")
+    if tuple(table.shape) != (T,):
+        raise ValueError(f"the timestep probability table has shape {tuple(table.shape)}, the diffusion has T = {T}")
+    p = table.detach().to("cpu", torch.float64)
+    if not torch.isfinite(p).all() or (p < 0).any():
+        raise ValueError("timestep probabilities must be finite and >= 0")
+    p = p.to(torch.float32).contiguous()
+    if not torch.isfinite(p).all() or not (p > 0).any():
+        raise ValueError("timestep probabilities must not all be zero (in fp32)")
+    return p
+
+
 class TimestepSchedule:
     """A reverse chain over a subset of the T timesteps: step k = S-1 .. 0 runs the network at
     ``timesteps[k]`` and applies ``x' = c1 (x - c2 eps) + sigma z`` with row k of ``coef``

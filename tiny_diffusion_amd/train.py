@@ -27,7 +27,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from ._flat_step import FlatStep, _ema_args, cosine_annealing_lr, ema_decay_at  # noqa: F401  (re-exported)
+from ._flat_step import FlatStep, _ema_args, _i64, cosine_annealing_lr, ema_decay_at  # noqa: F401  (re-exported)
 from ._lib import lib, check
 from .schedule import ForwardProcess
 from .unet import KIND_LAION, KIND_MNIST, MODE_TRAIN, MODE_EVAL_GRAD, NoiseModelBase, _cond_tensor, backward_stage_params
@@ -103,8 +103,25 @@ class TrainStep(FlatStep):
                  cosine_eta_min: float = 0.0, use_graph: bool = False, data_parallel: bool = True,
                  sync_bn: bool = False, cond_drop_prob: float = 0.0, cond_drop_seed: int = 0,
                  ema_decay: Optional[float] = None, ema_warmup: bool = False, prediction: str = "eps",
-                 loss_weighting=None, snr_gamma: float = 5.0):
-        """``prediction`` / ``loss_weighting`` / ``snr_gamma`` (the training objective; the defaults are the
+                 loss_weighting=None, snr_gamma: float = 5.0, timestep_sampler=None, importance_weights=None,
+                 timestep_seed: int = 0, history_per_term: int = 10, uniform_prob: float = 0.001):
+        """``timestep_sampler`` (which timestep each sample sees when ``step()`` is not given ``t``; ``None``: the
+        reference's ``torch.randint``, and nothing below is allocated or launched).  A ``(T,)`` table of probabilities
+        (``schedule.logit_normal_timestep_probs``, or any finite, non-negative, not all-zero table): ``t`` is a Philox
+        draw keyed by ``(timestep_seed, step * world + rank, sample)`` inverted through the table's CDF on the device
+        (``tdx_timestep_draw``); torch's generator is not consumed for ``t``.  ``"loss_second_moment"`` (Nichol &
+        Dhariwal 2021, 3.3): the step keeps the last ``history_per_term`` per-sample losses of every timestep on the
+        device and, once every timestep has that many, draws ``t`` with probability proportional to ``sqrt(E[L_t^2])``
+        mixed with ``uniform_prob`` of the uniform distribution (``tdx_mse_per_sample`` and
+        ``tdx_timestep_history_update`` after the loss launch; until then uniformly).  ``importance_weights``
+        (``None``: on for the adaptive sampler, off for a table): each sample's loss is multiplied by ``1 / (T p_t)``, so
+        the objective stays the uniform one while its gradient noise drops; the product with the objective's weights is
+        the step's own device table ``_w_eff``.  An explicit ``t=`` is used as given: no draw, its losses still enter
+        the history.  ``sample_losses`` (B,): every sample's objective-weighted loss of the last step; ``last_t`` its
+        timesteps; ``timestep_sampler_state()`` / ``load_timestep_sampler_state()`` for checkpoints.  The adaptive
+        sampler is single-rank (``ValueError`` inside a process group of more than one rank).
+
+        ``prediction`` / ``loss_weighting`` / ``snr_gamma`` (the training objective; the defaults are the
         reference's: predict eps, unweighted MSE, and then the step calls the entries it always called and allocates
         nothing new).  ``prediction="v"`` (Salimans & Ho 2022): the network's target is ``v = sqrt(acp[t]) eps -
         sqrt(1 - acp[t]) x_0``, written by the q_sample launch in place of the noise (``tdx_q_sample_target[_philox]``);
@@ -139,6 +156,11 @@ class TrainStep(FlatStep):
         self.model = model
         self.diffusion = diffusion
         self._check_objective(prediction, loss_weighting, snr_gamma)   # the table is uploaded after _flatten
+        self._check_timestep_sampler(timestep_sampler, importance_weights, timestep_seed, history_per_term, uniform_prob)
+        if (self.timestep_sampler == "loss_second_moment" and data_parallel and torch.distributed.is_available()
+                and torch.distributed.is_initialized() and torch.distributed.get_world_size(process_group) > 1):
+            raise ValueError("timestep_sampler='loss_second_moment' is single-rank: the ranks' loss histories are not "
+                             "gathered (use a fixed table under data parallelism)")
         # max_grad_norm: torch.nn.utils.clip_grad_norm_(parameters, max_norm) between backward and the
         # optimizer step (conditional_diffusion_laion.py:469); None = no clipping (MNIST scripts)
         self._init_optimizer(lr, betas, eps, max_grad_norm, *_ema_args(ema_decay, ema_warmup), use_graph=use_graph)
@@ -193,6 +215,7 @@ class TrainStep(FlatStep):
         self._last_plan = None
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._mse_scratch = None
+        self._init_timestep_sampler()
 
     def _params(self):
         named = dict(self.model.named_parameters())
@@ -254,7 +277,11 @@ class TrainStep(FlatStep):
         if y is not None:
             self._gy.copy_(y)
             self._drop_cond(self._gy, out=self._gy)   # before the replay: the captured graph reads _gy as it always did
+        if self.timestep_sampler is not None:   # the captured draw reads its key from the device
+            self._ts_rng.copy_(torch.tensor([_i64(self.timestep_seed), _i64(self._philox_offset())], dtype=torch.int64))
         self._replay()
+        if self.timestep_sampler is not None:
+            self.last_t, self.sample_losses = self._g_last
         m._buf_epoch += 1  # BN running statistics changed on the device (invalidates inference packs)
         if self.cosine_T_max is not None:
             self.lr = cosine_annealing_lr(self.step_count, self.base_lr, self.cosine_T_max, self.cosine_eta_min)
@@ -263,6 +290,8 @@ class TrainStep(FlatStep):
     def _alloc_static(self, x_0, y):
         self._gx0 = x_0.detach().clone().contiguous().float()
         self._gy = None if y is None else y.detach().clone().contiguous()
+        if self.timestep_sampler is not None:
+            self._ts_rng = torch.zeros(2, dtype=torch.int64, device=self.device)
 
     def _static_step(self, hyper):
         # (a plan whose finalizer runs inside the capture is parked, not destroyed: unet._Plan.__del__)
@@ -272,13 +301,17 @@ class TrainStep(FlatStep):
         # destroy it under the graph: the graph's owner keeps it alive (an evicted plan is only destroyed
         # when its last reference goes).
         self._graph_plan = self._last_plan
+        self._g_last = (self.last_t, self.sample_losses)   # what a replay writes
 
     def _eager_step(self, x_0, y, t, noise, hyper=None):
         m, fp = self.model, self.diffusion
         B = x_0.shape[0]
         dev = x_0.device
         st = torch.cuda.current_stream(dev).cuda_stream
-        if t is None:
+        sampler = self.timestep_sampler is not None
+        if t is None and sampler:
+            t = self._draw_t(B, self._philox_offset(), st, self._ts_rng if hyper is not None else None)
+        elif t is None:
             t = torch.randint(0, fp.num_timesteps, (B,), device=dev)          # diffusion.py:220-222
         # `noise` is the loss target from here on: the noise itself, or v (written by the same launch)
         x_t, noise = self._q_sample(x_0, t, noise, self._philox_offset())     # diffusion.py:225
@@ -288,16 +321,20 @@ class TrainStep(FlatStep):
         d_out = torch.empty_like(eps_hat)
         if self._mse_scratch is None:
             self._mse_scratch = torch.empty(lib.tdx_mse_scratch_bytes(), dtype=torch.uint8, device=dev)
-        if self._w_table is not None:
+        w_loss = self._loss_table()
+        if w_loss is not None or sampler:
             t_w = t.to(dev).contiguous().to(torch.int64)
+        if w_loss is not None:
             check(lib.tdx_mse_loss_grad_weighted(eps_hat.data_ptr(), noise.data_ptr(), t_w.data_ptr(),
-                                                 self._w_table.data_ptr(), self.loss.data_ptr(), d_out.data_ptr(), 1.0,
+                                                 w_loss.data_ptr(), self.loss.data_ptr(), d_out.data_ptr(), 1.0,
                                                  B, eps_hat.numel() // B, self._mse_scratch.data_ptr(), st),
                   "tdx_mse_loss_grad_weighted")
         else:
             check(lib.tdx_mse_loss_grad(eps_hat.data_ptr(), noise.data_ptr(), self.loss.data_ptr(), d_out.data_ptr(),
                                         1.0, eps_hat.numel(), self._mse_scratch.data_ptr(), st),
                   "tdx_mse_loss_grad")                                         # diffusion.py:231
+        if sampler:
+            self._after_loss(eps_hat, noise, t_w, B, st)
         if self.world == 1 and not self.reducer.force:
             m._run_backward(plan, d_out, self.grad_views)                      # diffusion.py:235
         else:
