@@ -228,7 +228,40 @@ struct tdx_unet {
   hipStream_t side2;
   hipEvent_t ev_s2_fork[3], ev_s2_done[3], ev_join2, ev_red[13];
   hipEvent_t ev_mark[N_STAGES][2];   // tdx_unet_backward_mark: where side / side2 were when slot i was marked
+  // Waits the caller's stream does not need (helper_record / caller_wait below): the events the caller's stream waits
+  // for (ev_w, ev_pack on `side`; ev_s2_done on `side2`) are numbered per helper stream as they are recorded, and
+  // `seen` is the highest number of each helper the caller's stream `st` has waited for since caller_begin.
+  struct Joined { hipStream_t st; bool capturing; uint64_t rec[2], seen[2]; } jn;
+  uint64_t seq_w[13], seq_s2[3], seq_pack;
 };
+
+// An event wait costs the waiting stream 4-6 us on MI355X whether or not the event has completed long ago
+// (tools/micro/event_boundary_probe.hip, profiles/r12_event_boundary_probe.txt): the barrier packet is processed in
+// queue order in front of the next kernel.  A helper stream completes its events in the order it records them, so a
+// wait for event n of helper h (0: side, 1: side2) orders the caller's stream behind every earlier event of h too, and
+// a later wait for one of those is not enqueued.  The same holds inside a stream capture (a helper's captured nodes
+// form a chain).  The bookkeeping starts afresh with every training forward, and whenever the caller's stream or its
+// capture status is another one than at the last wait.
+static void caller_begin(tdx_unet* u, hipStream_t st, bool fresh) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(st, &cs);
+  const bool capturing = cs == hipStreamCaptureStatusActive;
+  if (fresh || st != u->jn.st || capturing != u->jn.capturing) u->jn.seen[0] = u->jn.seen[1] = 0;
+  u->jn.st = st;
+  u->jn.capturing = capturing;
+}
+
+static hipError_t helper_record(tdx_unet* u, int h, hipEvent_t ev, uint64_t* seq) {
+  *seq = ++u->jn.rec[h];
+  return hipEventRecord(ev, h ? u->side2 : u->side);
+}
+
+static hipError_t caller_wait(tdx_unet* u, hipStream_t st, int h, hipEvent_t ev, uint64_t seq) {
+  if ((h ? u->side2 : u->side) == st) return hipSuccess;   // the helper is the caller's stream itself
+  if (seq <= u->jn.seen[h]) return hipSuccess;              // an earlier wait covers it
+  u->jn.seen[h] = seq;
+  return hipStreamWaitEvent(st, ev, 0);
+}
 
 // Streams and events of destroyed plans are RECYCLED, never destroyed (round 4).  A module keeps its six most recently
 // used plans and destroys the rest, so a long process creates and destroys plans by the hundred; with a captured
@@ -257,8 +290,15 @@ static bool make_handles(PlanHandles* h) {
   if (hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, lo) != hipSuccess) return false;
   if (hipStreamCreateWithPriority(&h->side2, hipStreamNonBlocking, lo) != hipSuccess) return false;
   if (hipStreamCreateWithFlags(&h->half, hipStreamNonBlocking) != hipSuccess) return false;
-  for (auto& e : h->ev)
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return false;
+  // ev[0..50] order work among the plan's own streams and the caller's on ONE device, inside a step: no system-scope
+  // release (a record costs its stream 3-4 us instead of 5.6, profiles/r12_event_boundary_probe.txt; what the host or
+  // another device reads is released by the caller's stream, whose kernels follow the join).  ev[51..80] are ev_mark:
+  // the host synchronises on them and a communication stream consumes behind them, so they keep the system fence.
+  // The flags go with the position in `ev`, so every pooled PlanHandles has the same ones.
+  for (int i = 0; i < 81; ++i) {
+    const unsigned flags = hipEventDisableTiming | (i < 51 ? hipEventDisableSystemFence : 0);
+    if (hipEventCreateWithFlags(&h->ev[i], flags) != hipSuccess) return false;
+  }
   return true;
 }
 
@@ -371,6 +411,7 @@ extern "C" int tdx_unet_create_full(tdx_unet** out, int max_batch, int kind, int
   }
   u->side = u->side_own;
   u->side2 = u->side2_own;
+  u->jn = {};
   *out = u;
   return 0;
 }
@@ -601,14 +642,17 @@ extern "C" int tdx_unet_pack(tdx_unet* u, const void* const* params, void* const
   return pack_impl(u, params, buffers, stream);
 }
 
-// packs of units 2..12 on the side stream, ordered after what the main stream has enqueued so far
+// packs of units 2..12 on the side stream, ordered after what the main stream has enqueued so far.  (Forking the side
+// stream with the head's record instead - the packs read nothing of the forward - saves this record and was measured:
+// 9.308 against the parent's 9.295 ms per B = 256 step, profiles/r12_event_chain_ab.txt: the packs then start beside
+// the step's small head kernels and unit 0.  Not kept.)
 static int pack_tail(tdx_unet* u, const void* const* params, tdx_stream_t stream) {
   const float* const* P = reinterpret_cast<const float* const*>(params);
   TDX_HIP(hipEventRecord(u->ev_fork, to_stream(stream)));
   TDX_HIP(hipStreamWaitEvent(u->side, u->ev_fork, 0));
   int rc = pack_units(u, P, 2, 13, reinterpret_cast<tdx_stream_t>(u->side), false, false);
   if (rc) return rc;
-  TDX_HIP(hipEventRecord(u->ev_pack, u->side));
+  TDX_HIP(helper_record(u, 0, u->ev_pack, &u->seq_pack));
   return 0;
 }
 
@@ -731,6 +775,7 @@ static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const
   // runs there too, beside initial_conv and the first encoder level (LAION, 768 wide: 90 us off the head
   // of the step).  Sampling is one stream.
   hipStream_t tst = st;
+  if (!infer) caller_begin(u, st, true);
   if (!infer && u->side2 != st) {
     TDX_HIP(hipEventRecord(u->ev_fork, st));   // t / labels / cond are in place
     TDX_HIP(hipStreamWaitEvent(u->side2, u->ev_fork, 0));
@@ -840,7 +885,7 @@ static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const
   if (!infer) RC(pack_tail(u, params, stream));  // beside unit 1's convolution
   for (int k = 0; k < 3; ++k) {
     const int ua = 2 * k, ub = 2 * k + 1;
-    if (k == 1 && !infer) TDX_HIP(hipStreamWaitEvent(st, u->ev_pack, 0));  // packs of units 2..12
+    if (k == 1 && !infer) TDX_HIP(caller_wait(u, st, 0, u->ev_pack, u->seq_pack));  // packs of units 2..12
     if (k > 0) RC(run_unit(ua, ws + L.ep[k - 1]));
     TdxPoolFuse pf{infer && !bf16 && (g_knobs.sample_fuse & 2) ? ws + L.ep[k] : nullptr};
     RC(run_unit(ub, ws + L.Y[ua], nullptr, pf.pooled ? &pf : nullptr));
@@ -855,7 +900,7 @@ static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const
       RC(tdx_bilinear_ac_fwd_t(ws + L.Y[ub], sc(ub), sh(ub), ws + L.tp[k], ws + L.cat[kd], B, S.enc_hw[k],
                                S.enc_hw[k], dd.hw, dd.hw, S.skip_ch[k], dd.cin, c_up, io16,
                                reinterpret_cast<tdx_stream_t>(u->side2)));
-      TDX_HIP(hipEventRecord(u->ev_s2_done[k], u->side2));
+      TDX_HIP(helper_record(u, 1, u->ev_s2_done[k], &u->seq_s2[k]));
     }
     if (!pf.pooled)   // (null also when the convolution was not split: its reduction could not do the pooling)
       RC(tdx_maxpool2_ceil_fwd_t(ws + L.Y[ub], sc(ub), sh(ub), ws + L.ep[k], B, S.enc_hw[k], S.enc_hw[k],
@@ -880,7 +925,8 @@ static int unet_forward_impl(tdx_unet* u, const void* const* params, void* const
     } else {
       RC(tdx_bilinear_ac_fwd_t(ws + L.Y[prev], sc(prev), sh(prev), nullptr, ws + L.cat[k], B, dp.hw, dp.hw, hw, hw,
                                c_up, da.cin, 0, io16, stream));
-      TDX_HIP(hipStreamWaitEvent(st, u->ev_s2_done[skip_k], 0));  // skip half: written during the encoder
+      // skip half: written during the encoder (the first level's wait, for the last resize, covers the other two)
+      TDX_HIP(caller_wait(u, st, 1, u->ev_s2_done[skip_k], u->seq_s2[skip_k]));
     }
     RC(run_unit(ua, ws + L.cat[k]));
     RC(run_unit(ub, ws + L.Y[ua], defer_ok ? &dfr : nullptr));
@@ -978,8 +1024,8 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
       GBuf& c = gb[i];
       if (c.p != a && c.p != b && (!best || c.age < best->age)) best = &c;
     }
-    if (best->w_unit >= 0) TDX_HIP(hipStreamWaitEvent(st, u->ev_w[best->w_unit], 0));
-    if (best->s2 >= 0) TDX_HIP(hipStreamWaitEvent(st, u->ev_s2_done[best->s2], 0));
+    if (best->w_unit >= 0) TDX_HIP(caller_wait(u, st, 0, u->ev_w[best->w_unit], u->seq_w[best->w_unit]));
+    if (best->s2 >= 0) TDX_HIP(caller_wait(u, st, 1, u->ev_s2_done[best->s2], u->seq_s2[best->s2]));
     best->w_unit = -1;
     best->s2 = -1;
     best->age = ++clock;
@@ -1005,9 +1051,33 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
   hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(st, &cap_status);
   const bool capturing = cap_status == hipStreamCaptureStatusActive;
+  caller_begin(u, st, false);
+  // The slab reduction of unit i's weight gradient: third stream - or, while the step is being CAPTURED, right
+  // behind the GEMM on its own stream (see above), which needs neither of the two cross-helper waits.
+  auto slab_reduce = [&](int i) -> int {
+    const UnitDef& d = S.units[i];
+    const bool mat = u->materialize && (!bf16 || (io16 && g_knobs.bf16_materialize));
+    const bool wino = u->wino_w[i] && !(d.in_bn && !mat);
+    float* slab = ws + ((i & 1) ? L.slabs2 : L.slabs);
+    hipStream_t wst = u->side;
+    hipStream_t red_st = capturing ? wst : u->side2;
+    if (red_st != wst) TDX_HIP(hipStreamWaitEvent(red_st, u->ev_w[i], 0));
+    RC(tdx_conv3x3_wgrad_reduce_pad(slab, G[TDX_P_UNIT0 + 4 * i],
+                                    bf16 ? tdx_conv3x3_wgrad_splits_bf16(B, d.hw, d.hw, d.cin, d.cout)
+                                    : wino ? tdx_conv3x3_wgrad_wino_splits(B, d.hw, d.hw, d.cin, d.cout)
+                                           : tdx_conv3x3_wgrad_splits(B, d.hw, d.hw, d.cin, d.cout),
+                                    d.cout, d.cin, d.cin_real, reinterpret_cast<tdx_stream_t>(red_st)));
+    if (red_st != wst) {
+      TDX_HIP(hipEventRecord(u->ev_red[i], red_st));
+      u->red_pending[i] = true;
+    }
+    return 0;
+  };
   // unit_bwd: g_next holds dL/d(activation of unit i); afterwards that buffer holds
-  // dL/d(conv output) (read by the wgrad on the side stream) and *g_in_out the input gradient
-  auto unit_bwd = [&](int i, const float* in, float** g_in_out) -> int {
+  // dL/d(conv output) (read by the wgrad on the side stream) and *g_in_out the input gradient.
+  // reduce_later: the caller enqueues slab_reduce(i) itself, behind work the third stream must not keep waiting
+  // for this unit's weight gradient (dec_level_bwd)
+  auto unit_bwd = [&](int i, const float* in, float** g_in_out, bool reduce_later = false) -> int {
     const UnitDef& d = S.units[i];
     float* g = g_next;
     const float* ss = ws + L.ss[i];
@@ -1039,7 +1109,6 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
     // The split-K slabs alternate between two buffers; the (HBM-bound) slab reduction runs on the
     // third stream.  Unit i's slab buffer was last read by the reduction of unit i+2.
     hipStream_t wst = fork ? u->side : st;
-    hipStream_t red_st = capturing ? wst : u->side2;
     if (fork) {
       TDX_HIP(hipEventRecord(u->ev_dy[i], st));
       TDX_HIP(hipStreamWaitEvent(u->side, u->ev_dy[i], 0));
@@ -1057,19 +1126,8 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
       RC(tdx_conv3x3_wgrad(in, g, slab, B, d.hw, d.hw, d.cin, d.cout, bn_on_load ? TDX_CONV_IN_BNRELU : 0, isc, ish,
                            reinterpret_cast<tdx_stream_t>(wst)));
     // dy is free again once the wgrad GEMM has read it
-    TDX_HIP(hipEventRecord(u->ev_w[i], wst));
-    // the slab reduction: third stream - or, while the step is being CAPTURED, right behind the GEMM on its
-    // own stream (red_st, see the top of this function), which needs neither of the two cross-helper waits
-    if (red_st != wst) TDX_HIP(hipStreamWaitEvent(red_st, u->ev_w[i], 0));
-    RC(tdx_conv3x3_wgrad_reduce_pad(slab, G[TDX_P_UNIT0 + 4 * i],
-                                    bf16 ? tdx_conv3x3_wgrad_splits_bf16(B, d.hw, d.hw, d.cin, d.cout)
-                                    : u->wino_w[i] && !bn_on_load ? tdx_conv3x3_wgrad_wino_splits(B, d.hw, d.hw, d.cin, d.cout)
-                                                                  : tdx_conv3x3_wgrad_splits(B, d.hw, d.hw, d.cin, d.cout),
-                                    d.cout, d.cin, d.cin_real, reinterpret_cast<tdx_stream_t>(red_st)));
-    if (red_st != wst) {
-      TDX_HIP(hipEventRecord(u->ev_red[i], red_st));
-      u->red_pending[i] = true;
-    }
+    TDX_HIP(helper_record(u, 0, u->ev_w[i], &u->seq_w[i]));
+    if (!reduce_later) RC(slab_reduce(i));
     GBuf* gbuf = find(g);
     gbuf->w_unit = i;
     gbuf->age = ++clock;
@@ -1122,8 +1180,14 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
     const UnitDef& da = S.units[ua];
     const UnitDef& dp = S.units[prev];
     const int c_up = dp.cout, c_skip = S.skip_ch[skip_k];
+    // The skip branch's adjoint goes to the third stream BEFORE this unit's slab reduction.  Behind it, it waited for
+    // this unit's weight gradient, which the side stream reaches late: at the innermost level the very next stage
+    // needs GS (max-pool backward), and the main stream stood idle for ~100 us of a B = 256 MNIST step
+    // (profiles/r12_step_timeline_before.txt, 6193.7 .. 6296.0; afterwards 11.6 us).  Not inside a capture, where
+    // the reduction is not on the third stream.
+    const bool reduce_later = !capturing;
     float* gcat;
-    RC(unit_bwd(ua, ws + L.cat[k], &gcat));
+    RC(unit_bwd(ua, ws + L.cat[k], &gcat, reduce_later));
     // skip branch (needed only when the encoder is reached): third stream
     TDX_HIP(hipEventRecord(u->ev_s2_fork[k], st));
     TDX_HIP(hipStreamWaitEvent(u->side2, u->ev_s2_fork[k], 0));
@@ -1135,7 +1199,8 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
     }
     RC(tdx_pixel_sum(ws + L.GS[skip_k], ws + L.gtp[skip_k], B, S.enc_hw[skip_k] * S.enc_hw[skip_k], c_skip,
                      u->side2, io16));
-    TDX_HIP(hipEventRecord(u->ev_s2_done[k], u->side2));
+    TDX_HIP(helper_record(u, 1, u->ev_s2_done[k], &u->seq_s2[k]));
+    if (reduce_later) RC(slab_reduce(ua));
     // this projection's weight gradient and its share of g(emb) as soon as its pixel sum exists (levels
     // arrive in the order time_proj1, 2, 3 = the summation order of tdx_time_embed_bwd): six of the
     // time path's small kernels leave the tail of the step.  The REST of that path stays after the last
@@ -1176,7 +1241,7 @@ static int unet_backward_impl(tdx_unet* u, const void* const* params, void* cons
     float* gnew;
     RC(acquire(gpool, nullptr, &gnew));
     // GS[k] was written on the third stream during the decoder
-    TDX_HIP(hipStreamWaitEvent(st, u->ev_s2_done[2 - k], 0));
+    TDX_HIP(caller_wait(u, st, 1, u->ev_s2_done[2 - k], u->seq_s2[2 - k]));
     {
       const int cu = S.skip_ch[k];
       int nblk = 0;

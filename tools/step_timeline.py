@@ -6,7 +6,8 @@
 One line per kernel: start / end / duration in us relative to the end of the previous step's Adam kernel, the
 hardware queue (1 = main stream, 2 = weight-gradient stream, 3 = helper stream), C for the MFMA convolutions,
 the kernel name and its grid.  The footer sums the convolution kernels by role and lists every interval with no
-convolution in flight (what the step pays on top of its GEMMs)."""
+convolution in flight (what the step pays on top of its GEMMs), then every interval of 3 us or more on the caller's
+stream between a kernel's end and the next kernel's start, and their sum (the fork / join operations of the schedule)."""
 import csv
 import sys
 
@@ -54,3 +55,19 @@ for s, e in sorted(gaps, key=lambda g: g[0] - g[1])[:12]:
     inside = [short(r["Kernel_Name"]) for r in seg
               if int(r["Start_Timestamp"]) - t0 < e and int(r["End_Timestamp"]) - t0 > s and not isconv(r["Kernel_Name"])]
     print(f"    {s / 1e3:9.1f} .. {e / 1e3:9.1f} ({(e - s) / 1e3:6.1f} us): {', '.join(dict.fromkeys(inside))}")
+# The caller's stream (the queue of the step's first kernel) is the step's dependent chain.  Same-stream boundaries
+# with nothing between them show start == previous end; what is left are the event records and stream waits that the
+# fork / join schedule puts there (and, between steps, the host).
+MIN_GAP = 3000  # ns
+main = [(int(r["Start_Timestamp"]) - t0, int(r["End_Timestamp"]) - t0, short(r["Kernel_Name"]))
+        for r in seg if queues[r["Queue_Id"]] == 1]
+holes, cur, last = [], 0, "(previous step's Adam)"
+for s, e, n in main:
+    if s - cur >= MIN_GAP:
+        holes.append((cur, s, last, n))
+    if e > cur:
+        cur, last = e, n
+print(f"\ncaller's stream: {len(main)} kernels, {len(holes)} intervals >= {MIN_GAP / 1e3:.0f} us between a kernel's end "
+      f"and the next kernel's start, {sum(e - s for s, e, _, _ in holes) / 1e3:.1f} us in all:")
+for s, e, a, b in holes:
+    print(f"    {s / 1e3:9.1f} .. {e / 1e3:9.1f} ({(e - s) / 1e3:6.1f} us): {a} -> {b}")
