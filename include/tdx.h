@@ -883,6 +883,34 @@ int tdx_time_mlp_bwd(const int64_t* t, const int64_t* y, const void* const* para
                      const float* g_t2, const float* g_t3, float* scratch, int batch,
                      int num_classes, tdx_stream_t stream);
 
+/* Additions within ABI 400: the same path at either kind and any time_dim (a constructor argument of every reference
+ * model), as the networks run it.  kind 0 is the formula above at width time_dim; kind 1 is the LAION model's
+ * (conditional_diffusion_laion.py:222-243, 297-308): emb = W2 silu(W1 sinusoid(t) + b1) + b2 + cond, projections of
+ * 64 | 128 | 256 outputs.  time_dim: 1 ... 4096 for kind 0, 4 ... 4096 for kind 1 (the sinusoid divides by
+ * time_dim / 2 - 1); TDX_E_SHAPE otherwise, nothing is written.  TDX_E_BADARG, nothing written: another kind, a null
+ * pointer that is not marked optional, batch <= 0, parts that is 0 or holds a bit other than 1 | 2 | 4, k outside
+ * 0 ... 2, labels with num_classes <= 0, or - at the widths 256, 512, 768, 1024, whose kernels read rows as float4 -
+ * a weight matrix, pre, emb, the sinusoid or the text rows off a 16-byte boundary.
+ *   fwd:  cond  kind 0: int64 labels (a negative label is the null condition) or NULL; kind 1: (B, time_dim) text rows.
+ *         aux   written: kind 0 float(t), B floats; kind 1 the sinusoid, (B, time_dim).
+ *         pre, emb (B, time_dim); t1, t2, t3 (B, 128 | 256 | 512) for kind 0, (B, 64 | 128 | 256) for kind 1.
+ *   bwd:  parts 1 = the three projections (dW_k, db_k and g_emb), 2 = the middle (dE, dW2, db2, g_h; for kind 1 dW1 and
+ *         db1 too), 4 = kind 0's first layer (dW1, db1); in one call or, in this order, in several.  y: kind 0's labels
+ *         or NULL (optional; ignored for kind 1), aux / pre / emb as the forward left them.  g_t1..3 are read by part 1
+ *         only.  scratch: 3 * B * time_dim floats, g_emb | h | g_h, which the caller may read afterwards: g_emb is
+ *         d(loss)/d(emb), h = silu(pre), g_h = d(loss)/d(h) (kind 1: already multiplied by silu'(pre)).
+ *   proj_bwd: part 1 of projection k alone: dW_k, db_k, and g_emb = (k > 0 ? g_emb : 0) + g_tk W_k in scratch[0 : B *
+ *         time_dim].  Calling k = 0, 1, 2 and then bwd with parts 2 (| 4) equals bwd with all parts bit for bit. */
+int tdx_time_path_fwd(int kind, int time_dim, const int64_t* t, const void* cond, const void* const* params,
+                      float* aux, float* pre, float* emb, float* t1, float* t2, float* t3, int batch,
+                      tdx_stream_t stream);
+int tdx_time_path_bwd(int kind, int time_dim, int parts, const int64_t* y, const void* const* params,
+                      void* const* grads, const float* aux, const float* pre, const float* emb, const float* g_t1,
+                      const float* g_t2, const float* g_t3, float* scratch, int batch, int num_classes,
+                      tdx_stream_t stream);
+int tdx_time_path_proj_bwd(int kind, int time_dim, int k, const void* const* params, void* const* grads,
+                           const float* emb, const float* g_tk, float* scratch, int batch, tdx_stream_t stream);
+
 /* One reverse step x_t -> x_{t-1} of sample() (diffusion.py:259-274), capturable in a HIP graph:
  *   t = *counter; *counter = t - 1;  eps = eps_theta(x, t[, cond]) in TDX_MODE_INFER;
  *   x = c1[t] (x - c2[t] eps) + sigma[t] z   in place (z = 0 at t == 0).

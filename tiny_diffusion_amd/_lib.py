@@ -236,6 +236,9 @@ _SIGS = {
     "tdx_time_mlp_fwd": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, _ptr]),
     "tdx_time_mlp_bwd": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int, C.c_int,
                                    _ptr]),
+    "tdx_time_path_fwd": (C.c_int, [C.c_int, C.c_int] + [_ptr] * 9 + [C.c_int, _ptr]),
+    "tdx_time_path_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int] + [_ptr] * 10 + [C.c_int, C.c_int, _ptr]),
+    "tdx_time_path_proj_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int] + [_ptr] * 5 + [C.c_int, _ptr]),
     "tdx_conv3x3_dgrad": (C.c_int, [_ptr, _ptr, _ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ptr]),
     "tdx_bn_apply_relu_fwd": (C.c_int, [_ptr, _ptr, C.c_int64, C.c_int, _ptr, _ptr, _ptr]),
     "tdx_unet_pack": (C.c_int, [_ptr, _ptr, _ptr, _ptr]),

@@ -641,6 +641,70 @@ int tdx_sample_head(const int64_t* counter, int32_t* t_idx, int64_t* t_vec, int 
 }
 
 // ------------------------------------------------------------------ C ABI (the path on its own)
+static inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+// the row kernels (and, at kind 0 width 256, time_emb_kernel / time_proj_kernel) read the activations and the
+// weight rows as float4: at the widths that take them these must sit on 16-byte boundaries
+static bool time_path_fwd_misaligned(int td, const float* const* P, const float* aux, const float* pre,
+                                     const float* emb) {
+  if (!td_fast(td)) return false;
+  return misaligned16(aux) || misaligned16(pre) || misaligned16(emb) || misaligned16(P[TDX_P_TE0_W]) ||
+         misaligned16(P[TDX_P_TE2_W]) || misaligned16(P[TDX_P_TP1_W]) || misaligned16(P[TDX_P_TP2_W]) ||
+         misaligned16(P[TDX_P_TP3_W]);
+}
+
+extern "C" int tdx_time_path_fwd(int kind, int time_dim, const int64_t* t, const void* cond,
+                                 const void* const* params, float* aux, float* pre, float* emb, float* t1,
+                                 float* t2, float* t3, int batch, tdx_stream_t stream) {
+  if ((kind != 0 && kind != 1) || !t || !params || !aux || !pre || !emb || !t1 || !t2 || !t3 || batch <= 0)
+    return TDX_E_BADARG;
+  if (kind == 1 && !cond) return TDX_E_BADARG;
+  if (time_dim <= 0 || !td_ok(kind, time_dim)) return TDX_E_SHAPE;
+  const float* const* P = reinterpret_cast<const float* const*>(params);
+  for (int s : {TDX_P_TE0_W, TDX_P_TE0_B, TDX_P_TE2_W, TDX_P_TE2_B, TDX_P_TP1_W, TDX_P_TP1_B, TDX_P_TP2_W,
+                TDX_P_TP2_B, TDX_P_TP3_W, TDX_P_TP3_B})
+    if (!P[s]) return TDX_E_BADARG;
+  if (kind == 0 && cond && !P[TDX_P_CLASS_EMB]) return TDX_E_BADARG;
+  if (time_path_fwd_misaligned(time_dim, P, kind == 1 ? aux : nullptr, pre, emb)) return TDX_E_BADARG;
+  if (kind == 1 && td_fast(time_dim) && misaligned16(cond)) return TDX_E_BADARG;
+  return tdx_time_embed_fwd(kind, t, kind == 0 ? static_cast<const int64_t*>(cond) : nullptr,
+                            kind == 1 ? static_cast<const float*>(cond) : nullptr, P, aux, pre, emb, t1, t2, t3,
+                            batch, to_stream(stream), time_dim);
+}
+
+extern "C" int tdx_time_path_bwd(int kind, int time_dim, int parts, const int64_t* y, const void* const* params,
+                                 void* const* grads, const float* aux, const float* pre, const float* emb,
+                                 const float* g_t1, const float* g_t2, const float* g_t3, float* scratch, int batch,
+                                 int num_classes, tdx_stream_t stream) {
+  if ((kind != 0 && kind != 1) || !params || !grads || !aux || !pre || !emb || !scratch || batch <= 0)
+    return TDX_E_BADARG;
+  if (parts <= 0 || (parts & ~(TDX_TIME_PROJ | TDX_TIME_MID | TDX_TIME_L1))) return TDX_E_BADARG;
+  if ((parts & TDX_TIME_PROJ) && (!g_t1 || !g_t2 || !g_t3)) return TDX_E_BADARG;
+  if (kind == 0 && y && num_classes <= 0) return TDX_E_BADARG;
+  if (time_dim <= 0 || !td_ok(kind, time_dim)) return TDX_E_SHAPE;
+  const float* const* P = reinterpret_cast<const float* const*>(params);
+  float* const* G = reinterpret_cast<float* const*>(grads);
+  for (int s : {TDX_P_TE0_W, TDX_P_TE0_B, TDX_P_TE2_W, TDX_P_TE2_B, TDX_P_TP1_W, TDX_P_TP1_B, TDX_P_TP2_W,
+                TDX_P_TP2_B, TDX_P_TP3_W, TDX_P_TP3_B})
+    if (!P[s] || !G[s]) return TDX_E_BADARG;
+  if (kind == 0 && y && !G[TDX_P_CLASS_EMB]) return TDX_E_BADARG;
+  return tdx_time_embed_bwd(kind, kind == 0 ? y : nullptr, P, G, aux, pre, emb, g_t1, g_t2, g_t3, scratch, batch,
+                            kind == 0 && y ? num_classes : 0, to_stream(stream), time_dim, parts);
+}
+
+extern "C" int tdx_time_path_proj_bwd(int kind, int time_dim, int k, const void* const* params, void* const* grads,
+                                      const float* emb, const float* g_tk, float* scratch, int batch,
+                                      tdx_stream_t stream) {
+  if ((kind != 0 && kind != 1) || k < 0 || k > 2 || !params || !grads || !emb || !g_tk || !scratch || batch <= 0)
+    return TDX_E_BADARG;
+  if (time_dim <= 0 || !td_ok(kind, time_dim)) return TDX_E_SHAPE;
+  const float* const* P = reinterpret_cast<const float* const*>(params);
+  float* const* G = reinterpret_cast<float* const*>(grads);
+  const int pw = k == 0 ? TDX_P_TP1_W : k == 1 ? TDX_P_TP2_W : TDX_P_TP3_W;
+  if (!P[pw] || !G[pw] || !G[pw + 1]) return TDX_E_BADARG;
+  return tdx_time_proj_bwd(kind, k, P, G, emb, g_tk, scratch, batch, to_stream(stream), time_dim);
+}
+
 extern "C" int tdx_time_mlp_fwd(const int64_t* t, const int64_t* y, const void* const* params, float* pre,
                                 float* emb, float* t1, float* t2, float* t3, int batch, tdx_stream_t stream) {
   if (!t || !params || !pre || !emb || !t1 || !t2 || !t3 || batch <= 0) return TDX_E_BADARG;
