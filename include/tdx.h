@@ -331,6 +331,29 @@ int tdx_timestep_history_update(const int64_t* t, const float* loss_b, int B, fl
                                 float uniform_prob, const float* w_obj, float* cdf, float* w_eff, int T,
                                 tdx_stream_t stream);
 
+/* Progressive distillation (additions within ABI 400; csrc/distill.hip; Salimans & Ho 2022, Algorithm
+ * 2): two deterministic DDIM steps of a frozen teacher at PER-SAMPLE timesteps and the target with which ONE DDIM step
+ * of the student lands where they did.  Sample b reads row t[b] of rows, a (T, 12) fp32 table
+ *   (p1, q1, A1, B1,  p2, q2, A2, B2,  W2, W1, G, H)          (schedule.distill_tables; 16-byte aligned)
+ * - two rows (p, q, A, Bx) of the x0 form (TDX_STEP_X0) of the teacher's grid, the convex weights of the student's
+ * x0 and the map from it to the student's target - and with clamp(v) = min(max(v, lo), hi):
+ *   tdx_distill_teacher_step:  x1c = clamp(p1 z_t + q1 out1),   z_mid = A1 x1c + B1 z_t,   t_mid[b] = t_mid_table[t[b]]
+ *   tdx_distill_target:        x2c = clamp(p2 z_mid + q2 out2), x~ = W2 x2c + W1 x1c,      target = G x~ + H z_t
+ * out1 = teacher(z_t, t), out2 = teacher(z_mid, t_mid).  Every product and sum is rounded separately in the order
+ * written: the arithmetic of tdx_p_sample_update(form = TDX_STEP_X0) without its noise term, so z_mid is that entry's
+ * result bit for bit when every sample sits on one row.  Infinite bounds never bind.  x_tilde may be NULL (not
+ * written; target is the same bits).  t is not range-checked, as in tdx_q_sample: rows and t_mid_table must hold
+ * max(t) + 1 entries.  Elementwise, float4 accesses, grid-strided, no LDS, no atomics, one stream, capturable: 16 B per
+ * element and 20 B (24 B with x_tilde).  TDX_E_BADARG, before any GPU call and with nothing written: a null pointer
+ * other than x_tilde, batch <= 0, per_sample <= 0, per_sample % 4 (a float4 must not straddle two samples), not lo < hi
+ * (a NaN bound included). */
+int tdx_distill_teacher_step(const float* z_t, const float* out1, const int64_t* t, const float* rows,
+                             const int64_t* t_mid_table, float* z_mid, float* x1c, int64_t* t_mid, int batch,
+                             int per_sample, float lo, float hi, tdx_stream_t stream);
+int tdx_distill_target(const float* z_t, const float* z_mid, const float* out2, const float* x1c, const int64_t* t,
+                       const float* rows, float* target, float* x_tilde, int batch, int per_sample, float lo, float hi,
+                       tdx_stream_t stream);
+
 /* Adam, torch defaults (diffusion.py:211/236): one fused pass over a flat
  * parameter buffer, 28 B/param.  step is the 1-based step count. */
 int tdx_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,

@@ -381,9 +381,11 @@ class FlatStep:
         self._ts_counts.copy_(counts.to(torch.int32))
         self._rebuild_timestep_table()
 
-    def _q_sample(self, x_0, t, noise, offset):
+    def _q_sample(self, x_0, t, noise, offset, y=None):
         """``(x_t, target)`` from the forward process's entries: the target is the noise, or v (written by the same
-        launch); without ``noise`` and with ``philox_seed`` the noise is drawn in the kernel, keyed by ``offset``."""
+        launch); without ``noise`` and with ``philox_seed`` the noise is drawn in the kernel, keyed by ``offset``.
+        ``y``: the step's condition, unused here - for a step whose target is itself a network's work
+        (``train.DistillStep``)."""
         fp, dev = self.diffusion, x_0.device
         philox = noise is None and self.philox_seed is not None
         if self.prediction != "eps":

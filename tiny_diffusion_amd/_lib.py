@@ -72,6 +72,8 @@ _SIGS = {
     "tdx_mse_per_sample": (C.c_int, [_ptr] * 5 + [C.c_int, C.c_int, _ptr]),
     "tdx_timestep_history_update": (C.c_int, [_ptr, _ptr, C.c_int, _ptr, _ptr, C.c_int, C.c_float, _ptr, _ptr, _ptr,
                                               C.c_int, _ptr]),
+    "tdx_distill_teacher_step": (C.c_int, [_ptr] * 8 + [C.c_int, C.c_int, C.c_float, C.c_float, _ptr]),
+    "tdx_distill_target": (C.c_int, [_ptr] * 8 + [C.c_int, C.c_int, C.c_float, C.c_float, _ptr]),
     "tdx_adam_step": (C.c_int, [_ptr, _ptr, _ptr, _ptr, C.c_int64, C.c_float, C.c_float, C.c_float,
                                 C.c_float, C.c_int, C.c_float, _ptr]),
     "tdx_adam_clip_scratch_bytes": (C.c_size_t, []),
