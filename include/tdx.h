@@ -354,6 +354,40 @@ int tdx_distill_target(const float* z_t, const float* z_mid, const float* out2, 
                        const float* rows, float* target, float* x_tilde, int batch, int per_sample, float lo, float hi,
                        tdx_stream_t stream);
 
+/* Guided distillation (additions within ABI 400; csrc/distill.hip; Meng et al. 2023): the teacher is
+ * sampled under classifier-free guidance and the student's ONE conditional evaluation learns the combination.  Guided
+ * layout as in tdx_p_sample_step_guided: with n = batch * per_sample, out1 / out2 hold 2n floats - the rows under the
+ * caller's condition, then the rows under the null condition - and for j < n
+ *   e[j] = out[j + n] + w (out[j] - out[j + n])                 (each operation rounded separately: common.h cfg_eps)
+ * takes the place of the teacher's output; out[j] == out[j + n] gives out[j + n] bit for bit, whatever w.  The
+ * arithmetic that follows is the unguided entries', operation for operation:
+ *   tdx_distill_teacher_step_guided:  x1c = clamp(p1 z_t + q1 e1),   z_mid = A1 x1c + B1 z_t
+ *       z_mid (2n floats) is written to both halves and t_mid (2 batch entries) to both halves: with them and the
+ *       doubled condition the teacher's second forward runs as is.  z_t, x1c: n floats (z_t may be the first half of
+ *       the 2n-float input of the first forward).
+ *   tdx_distill_target_guided:        x2c = clamp(p2 z_mid + q2 e2), x~ = W2 x2c + W1 x1c,   target = G x~ + H z_t
+ *       z_mid: its first n floats are read; target, x_tilde (nullable): n floats.
+ *   tdx_distill_guidance_target:      x0c = clamp(p z_t + q e),      target = G x0c + H z_t
+ *       the same-timestep step (stage one of Meng et al.): sample b reads row t[b] of rows, a (T, 4) fp32 table
+ *       (p, q, G, H) (schedule.guidance_distill_table; 16-byte aligned) - (p, q) of the x0 form at timestep t, (G, H) the
+ *       map from x0 to the student's target.  guided != 0: out holds 2n floats and e is the combination; guided == 0:
+ *       out holds n floats, e = out and w is not read - a change of parameterisation (an eps teacher, a v student).
+ *       x0c may be NULL (not written; target is the same bits).
+ * t is not range-checked.  Elementwise, float4 accesses, grid-strided, no LDS, no atomics, one stream, capturable.  Per
+ * element of the n: 24 B (reads z_t and two of out1, writes two of z_mid and x1c); 24 B (28 B with x_tilde); 12 B
+ * unguided and 16 B guided (4 B more with x0c).  TDX_E_BADARG, before any GPU call and with nothing written: a null
+ * pointer other than x_tilde / x0c, batch <= 0, per_sample <= 0, per_sample % 4, not lo < hi (a NaN bound included), a w
+ * that is not finite (tdx_distill_guidance_target: when guided != 0). */
+int tdx_distill_teacher_step_guided(const float* z_t, const float* out1, const int64_t* t, const float* rows,
+                                    const int64_t* t_mid_table, float* z_mid, float* x1c, int64_t* t_mid, int batch,
+                                    int per_sample, float w, float lo, float hi, tdx_stream_t stream);
+int tdx_distill_target_guided(const float* z_t, const float* z_mid, const float* out2, const float* x1c,
+                              const int64_t* t, const float* rows, float* target, float* x_tilde, int batch,
+                              int per_sample, float w, float lo, float hi, tdx_stream_t stream);
+int tdx_distill_guidance_target(const float* z_t, const float* out, const int64_t* t, const float* rows, float* target,
+                                float* x0c, int batch, int per_sample, int guided, float w, float lo, float hi,
+                                tdx_stream_t stream);
+
 /* Adam, torch defaults (diffusion.py:211/236): one fused pass over a flat
  * parameter buffer, 28 B/param.  step is the 1-based step count. */
 int tdx_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,

@@ -74,6 +74,9 @@ _SIGS = {
                                               C.c_int, _ptr]),
     "tdx_distill_teacher_step": (C.c_int, [_ptr] * 8 + [C.c_int, C.c_int, C.c_float, C.c_float, _ptr]),
     "tdx_distill_target": (C.c_int, [_ptr] * 8 + [C.c_int, C.c_int, C.c_float, C.c_float, _ptr]),
+    "tdx_distill_teacher_step_guided": (C.c_int, [_ptr] * 8 + [C.c_int, C.c_int] + [C.c_float] * 3 + [_ptr]),
+    "tdx_distill_target_guided": (C.c_int, [_ptr] * 8 + [C.c_int, C.c_int] + [C.c_float] * 3 + [_ptr]),
+    "tdx_distill_guidance_target": (C.c_int, [_ptr] * 6 + [C.c_int, C.c_int, C.c_int] + [C.c_float] * 3 + [_ptr]),
     "tdx_adam_step": (C.c_int, [_ptr, _ptr, _ptr, _ptr, C.c_int64, C.c_float, C.c_float, C.c_float,
                                 C.c_float, C.c_int, C.c_float, _ptr]),
     "tdx_adam_clip_scratch_bytes": (C.c_size_t, []),
