@@ -472,6 +472,20 @@ int tdx_final_conv_forward(const float* in, const float* w, const float* bias, f
                            int cout, tdx_stream_t stream);
 int tdx_final_conv_backward(const float* in, const float* g_out, const float* w, float* g_in, float* dw, float* db,
                             float* scratch, int B, int H, int W, int cout, tdx_stream_t stream);
+/* The same five with the storage flag of the bf16 mode: io16 != 0 -> the FAT channels-last tensor of 64 stored channels
+ * (`out` of initial_conv; `g_out` of its two backward entries; `in` and `g_in` of final_conv) holds bf16, widened on load
+ * and rounded to nearest-even once on store; the thin NCHW tensor, the weights, bias, dw, db and scratch stay fp32.
+ * io16 == 0: exactly the entries above, refusals (W < 4, channel counts) included. */
+int tdx_initial_conv_forward_io(const float* x, const float* w, const float* bias, void* out, int B, int H, int W,
+                                int cin, int cout, int io16, tdx_stream_t stream);
+int tdx_initial_conv_backward_io(const float* x, const void* g_out, float* dw, float* db, float* scratch, int B,
+                                 int H, int W, int cin, int cout, int io16, tdx_stream_t stream);
+int tdx_initial_conv_input_grad_io(const void* g_out, const float* w, float* g_x, int B, int H, int W, int cin,
+                                   int cout, int io16, tdx_stream_t stream);
+int tdx_final_conv_forward_io(const void* in, const float* w, const float* bias, float* out, int B, int H, int W,
+                              int cout, int io16, tdx_stream_t stream);
+int tdx_final_conv_backward_io(const void* in, const float* g_out, const float* w, void* g_in, float* dw, float* db,
+                               float* scratch, int B, int H, int W, int cout, int io16, tdx_stream_t stream);
 
 /* 3x3, pad 1, stride 1 convolution as an implicit GEMM on fp32 MFMA
  * (nn.Conv2d(cin,cout,3,padding=1), diffusion.py:28-98), NHWC.
@@ -677,6 +691,78 @@ int tdx_bilinear_ac_fwd(const float* in, const float* scale, const float* shift,
 int tdx_bilinear_ac_bwd(const float* g_out, float* g_in,
                         int B, int Hi, int Wi, int Ho, int Wo, int C,
                         int g_cstride, int g_coff, tdx_stream_t stream);
+
+/* ---- the storage-flag (_io) forms of the HBM-bound kernels, and the sum-emitting producers -----------------
+ * What a plan in bf16 mode (tdx_unet_set_precision(TDX_PREC_BF16)) and the default training step launch, one kernel
+ * at a time, so each can be held against a reference on its own (tests/test_gpu_io16_dispatch.py).  io16 != 0: every
+ * `void*` ACTIVATION tensor (channels-last activations and activation gradients) holds bf16 - widened exactly on load,
+ * arithmetic in fp32, ONE round-to-nearest-even on store; io16 == 0: they hold fp32 and the call is exactly the fp32
+ * entry of the same name without the suffix.  Per-channel operands (scale, shift, mean, rstd, gamma, addend, bias),
+ * partial sums, dgamma / dbeta / dbias and every thin (NCHW) tensor, weight and weight gradient are fp32 either way.
+ * Layouts, channel rules and refusals are those of the fp32 entry unless stated.  Every refusal (TDX_E_BADARG: a NULL
+ * or non-positive argument; TDX_E_SHAPE: a width the kernel does not have) comes before the first launch and writes
+ * nothing.  No new kernel, no new arithmetic: additions within ABI 400. */
+
+/* tdx_bn_apply_relu_fwd.  io16 != 0 needs C % 8 == 0 (the bf16 kernel handles eight channels per thread):
+ * TDX_E_SHAPE otherwise, like every other width refusal of this header.  io16 == 0 answers C % 4 != 0 as
+ * tdx_bn_apply_relu_fwd always has (TDX_E_BADARG); C = 12 is therefore computed in fp32 and refused in bf16. */
+int tdx_bn_apply_relu_fwd_io(const void* y, void* out, int64_t rows, int C, const float* scale, const float* shift,
+                             int io16, tdx_stream_t stream);
+/* tdx_bn_relu_bwd: reduction pass over (g, y), finalize, in-place apply pass; g and y (rows, C) in the storage type.
+ * In bf16 the reduction reads the STORED (rounded) gradient.  scratch: tdx_bn_relu_bwd_scratch_floats(rows, C). */
+int tdx_bn_relu_bwd_io(void* g, const void* y, int64_t rows, int C, const float* scale, const float* shift,
+                       const float* save_mean, const float* save_rstd, const float* gamma, float* dgamma,
+                       float* dbeta, float* dbias, float* scratch, int training, int io16, tdx_stream_t stream);
+/* The same WITHOUT the reduction pass: partial [nblk][2][C] (per block and channel: sum gz, then sum gz * xhat) is
+ * already in memory - written by a producer below, or by the caller.  The blocks are added in double in a fixed order;
+ * dgamma / dbeta / dbias (each may be NULL), then g <- the input gradient in place.  coef: 3 * C floats of scratch.
+ * nblk >= 1; C % 4 == 0 and C <= 1024 (TDX_E_SHAPE otherwise).  A buffer of tdx_bn_relu_bwd_scratch_floats(rows, C)
+ * floats holds the largest `partial` any producer writes (2048 blocks) plus coef. */
+int tdx_bn_relu_bwd_from_partials(void* g, const void* y, int64_t rows, int C, const float* scale, const float* shift,
+                                  const float* save_mean, const float* save_rstd, const float* gamma, float* dgamma,
+                                  float* dbeta, float* dbias, const float* partial, int nblk, float* coef,
+                                  int training, int io16, tdx_stream_t stream);
+
+/* tdx_maxpool2_ceil_fwd / _bwd.  The maximum of bf16 values is a bf16 value and skip + g is rounded once.
+ * Backward, partial == NULL: the plain kernel (bn_mean, bn_rstd ignored; *nblk = 0 when nblk is given).
+ * partial != NULL: the PRODUCER form - besides g_in it writes, per workgroup, the BatchNorm-backward sums of the unit
+ * whose pre-BN output is y (scale / shift its BN, bn_mean / bn_rstd its saved statistics) over the elements the
+ * workgroup wrote: partial [*nblk][2][C], *nblk <= 2048 workgroups, formed from the fp32 gradient BEFORE it is rounded
+ * for the store.  nblk, bn_mean, bn_rstd must then be given (TDX_E_BADARG).  It falls back to the plain kernel, and
+ * says so with *nblk == 0 (partial untouched), when scale == NULL, when C is not a width of tdx_bn_relu_bwd, or when
+ * bit 2 of the knob bnbwd_fused is off.  nblk points to HOST memory. */
+int tdx_maxpool2_ceil_fwd_io(const void* y, const float* scale, const float* shift, void* out, int B, int H, int W,
+                             int C, int io16, tdx_stream_t stream);
+int tdx_maxpool2_ceil_bwd_io(const void* y, const float* scale, const float* shift, const void* g_out,
+                             const void* skip_grad, void* g_in, int B, int H, int W, int C, const float* bn_mean,
+                             const float* bn_rstd, float* partial, int* nblk, int io16, tdx_stream_t stream);
+
+/* tdx_bilinear_ac_fwd / _bwd (addend stays fp32 (B, C)).  Backward, partial == NULL: the plain adjoint.
+ * partial != NULL: the PRODUCER form of the row kernel: bn_y (B, Hi, Wi, C, storage type) is the pre-BN output of the
+ * unit whose activation gradient g_in is, bn_scale .. bn_rstd its BN; partial [*nblk][2][C], *nblk = min(B Hi, 2048);
+ * all of nblk, bn_y, bn_scale, bn_shift, bn_mean, bn_rstd must be given (TDX_E_BADARG).  Falls back to the plain
+ * adjoint with *nblk == 0 when Hi or Wi > 64, when C is not a width of tdx_bn_relu_bwd, or when bit 1 of bnbwd_fused
+ * is off.  The contributor limit and the slice rules of tdx_bilinear_ac_bwd hold in every form. */
+int tdx_bilinear_ac_fwd_io(const void* in, const float* scale, const float* shift, const float* addend, void* out,
+                           int B, int Hi, int Wi, int Ho, int Wo, int C, int out_cstride, int out_coff, int io16,
+                           tdx_stream_t stream);
+int tdx_bilinear_ac_bwd_io(const void* g_out, void* g_in, int B, int Hi, int Wi, int Ho, int Wo, int C, int g_cstride,
+                           int g_coff, const void* bn_y, const float* bn_scale, const float* bn_shift,
+                           const float* bn_mean, const float* bn_rstd, float* partial, int* nblk, int io16,
+                           tdx_stream_t stream);
+/* Both halves of a decoder input in one launch (inference): out (B, Ho, Wo, Ca + Cb) = resize(A) | resize(b + b_addend).
+ * a (B, Ha, Wa, Ca), b (B, Hb, Wb, Cb) and out in the storage type; b_addend (B, Cb) fp32 or NULL; Cb == 0: no second
+ * source (b ignored).  a_splits > 0: source A is a DEFERRED split-K convolution - a is ignored and every element of A is
+ * relu((a_bias + partial_0 + ... + partial_{a_splits-1}) * a_scale + a_shift), summed in that order, from a_splits
+ * fp32 slabs (B, Ha, Wa, Ca) that lie a_slab >= B Ha Wa Ca floats apart at a_partial (fp32 in both storage types);
+ * a_bias may be NULL, a_scale and a_shift may not.  Ca % 4, Cb % 4: TDX_E_SHAPE. */
+int tdx_bilinear_pair_fwd_io(const void* a, const float* a_partial, int a_splits, size_t a_slab, const float* a_bias,
+                             const float* a_scale, const float* a_shift, int Ha, int Wa, int Ca, const void* b,
+                             const float* b_addend, int Hb, int Wb, int Cb, void* out, int B, int Ho, int Wo, int io16,
+                             tdx_stream_t stream);
+/* out[b][c] = sum over the HW pixels of g (B, HW, C), fp32 (B, C): the gradient of a broadcast per-sample addend.
+ * Widths as tdx_bn_relu_bwd (TDX_E_SHAPE otherwise); NULL or non-positive arguments: TDX_E_BADARG. */
+int tdx_pixel_sum_io(const void* g, float* out, int B, int HW, int C, int io16, tdx_stream_t stream);
 
 /* ---- whole network ------------------------------------------------------ */
 

@@ -151,18 +151,28 @@ def relu_margin(y, scale, shift):
     return ys + shift.double(), 8.0 * U * (ys.abs() + shift.double().abs())
 
 
-def nudge_relu(y, scale, shift):
+def nudge_relu(y, scale, shift, bf16=False):
     """y with every element whose pre-activation is inside the threshold moved away from it (by 64 u of the
-    magnitude, in the direction it already points): afterwards every element is decidable, none is left out."""
+    magnitude, in the direction it already points): afterwards every element is decidable, none is left out.
+    bf16: y is rounded to bf16 first and an offender moves to ANOTHER bf16 value - by the step above or by `trip`
+    spacings of bf16 at |y| (2^-7 relative, 2^-133 at zero), whichever is larger - and is checked again after the
+    rounding; the result is bf16-representable (returned as fp32)."""
     y = y.clone()
-    for _ in range(4):
+    if bf16:
+        y = y.bfloat16().float()
+    for trip in range(16 if bf16 else 4):
         pre, thr = relu_margin(y, scale, shift)
         bad = ~(pre.abs() > thr)
         if not bool(bad.any()):
             break
         sc = scale.double().expand_as(pre)
         step = (8.0 * thr + 1e-20) / sc.abs() * torch.where(pre >= 0, 1.0, -1.0) * torch.sign(sc)
-        y = torch.where(bad, (y.double() + step).float(), y)
+        if bf16:
+            spacing = torch.exp2(torch.floor(torch.log2(y.double().abs().clamp_min(2.0 ** -126))) - 7.0)
+            step = torch.sign(step) * torch.maximum(step.abs(), (trip + 1) * spacing)
+            y = torch.where(bad, (y.double() + step).float().bfloat16().float(), y)
+        else:
+            y = torch.where(bad, (y.double() + step).float(), y)
     assert relu_decidable(y, scale, shift)
     return y
 

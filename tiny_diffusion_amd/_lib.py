@@ -143,6 +143,25 @@ _SIGS = {
                                       C.c_int, C.c_int, C.c_int, C.c_int, _ptr]),
     "tdx_bilinear_ac_bwd": (C.c_int, [_ptr, _ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_int, _ptr]),
+    # the storage-flag (_io) forms and the sum-emitting producers (io16 last before the stream)
+    "tdx_bn_apply_relu_fwd_io": (C.c_int, [_ptr, _ptr, C.c_int64, C.c_int, _ptr, _ptr, C.c_int, _ptr]),
+    "tdx_bn_relu_bwd_io": (C.c_int, [_ptr, _ptr, C.c_int64, C.c_int] + [_ptr] * 9 + [C.c_int, C.c_int, _ptr]),
+    "tdx_bn_relu_bwd_from_partials": (C.c_int, [_ptr, _ptr, C.c_int64, C.c_int] + [_ptr] * 9
+                                      + [C.c_int, _ptr, C.c_int, C.c_int, _ptr]),
+    "tdx_maxpool2_ceil_fwd_io": (C.c_int, [_ptr] * 4 + [C.c_int] * 5 + [_ptr]),
+    "tdx_maxpool2_ceil_bwd_io": (C.c_int, [_ptr] * 6 + [C.c_int] * 4 + [_ptr, _ptr, _ptr, C.POINTER(C.c_int), C.c_int,
+                                                                        _ptr]),
+    "tdx_bilinear_ac_fwd_io": (C.c_int, [_ptr] * 5 + [C.c_int] * 9 + [_ptr]),
+    "tdx_bilinear_ac_bwd_io": (C.c_int, [_ptr, _ptr] + [C.c_int] * 8 + [_ptr] * 6 + [C.POINTER(C.c_int), C.c_int, _ptr]),
+    "tdx_bilinear_pair_fwd_io": (C.c_int, [_ptr, _ptr, C.c_int, C.c_size_t, _ptr, _ptr, _ptr, C.c_int, C.c_int, C.c_int,
+                                           _ptr, _ptr, C.c_int, C.c_int, C.c_int, _ptr, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, _ptr]),
+    "tdx_pixel_sum_io": (C.c_int, [_ptr, _ptr, C.c_int, C.c_int, C.c_int, C.c_int, _ptr]),
+    "tdx_initial_conv_forward_io": (C.c_int, [_ptr] * 4 + [C.c_int] * 6 + [_ptr]),
+    "tdx_initial_conv_backward_io": (C.c_int, [_ptr] * 5 + [C.c_int] * 6 + [_ptr]),
+    "tdx_initial_conv_input_grad_io": (C.c_int, [_ptr] * 3 + [C.c_int] * 6 + [_ptr]),
+    "tdx_final_conv_forward_io": (C.c_int, [_ptr] * 4 + [C.c_int] * 5 + [_ptr]),
+    "tdx_final_conv_backward_io": (C.c_int, [_ptr] * 7 + [C.c_int] * 5 + [_ptr]),
     "tdx_adam_step_dev": (C.c_int, [_ptr, _ptr, _ptr, _ptr, C.c_int64, _ptr, C.c_float, C.c_float, C.c_float, _ptr]),
     "tdx_step_begin": (C.c_int, [_ptr, _ptr, _ptr, C.c_int, _ptr]),
     "tdx_step_begin_sched": (C.c_int, [_ptr, _ptr, _ptr, _ptr, C.c_int, _ptr]),

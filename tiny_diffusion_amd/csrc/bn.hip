@@ -523,3 +523,37 @@ int tdx_bn_relu_bwd_tail(float* g, const float* y, int64_t rows, int C, const fl
   TDX_CHECK_LAUNCH();
   return 0;
 }
+
+// ---- the C-ABI forms with the storage flag (include/tdx.h): io16 != 0 -> the activation tensors hold bf16.  No kernel
+// and no launch of their own; every refusal comes before the first launch.
+extern "C" int tdx_bn_apply_relu_fwd_io(const void* y, void* out, int64_t rows, int C, const float* scale,
+                                        const float* shift, int io16, tdx_stream_t stream) {
+  if (!y || !out || !scale || !shift || rows <= 0 || C <= 0) return TDX_E_BADARG;
+  if (io16 && C % 8) return TDX_E_SHAPE;   // eight channels per thread in bf16 (C % 4 in fp32: the fp32 entry's answer)
+  return tdx_bn_relu_apply(static_cast<const float*>(y), static_cast<float*>(out), rows, C, scale, shift,
+                           to_stream(stream), io16 ? 1 : 0);
+}
+
+extern "C" int tdx_bn_relu_bwd_io(void* g, const void* y, int64_t rows, int C, const float* scale, const float* shift,
+                                  const float* save_mean, const float* save_rstd, const float* gamma, float* dgamma,
+                                  float* dbeta, float* dbias, float* scratch, int training, int io16,
+                                  tdx_stream_t stream) {
+  if (C <= 0) return TDX_E_BADARG;
+  return tdx_bn_relu_bwd_sync(static_cast<float*>(g), static_cast<const float*>(y), rows, C, scale, shift, save_mean,
+                              save_rstd, gamma, dgamma, dbeta, dbias, scratch, training, nullptr, nullptr, nullptr,
+                              stream, io16 ? 1 : 0);
+}
+
+extern "C" int tdx_bn_relu_bwd_from_partials(void* g, const void* y, int64_t rows, int C, const float* scale,
+                                             const float* shift, const float* save_mean, const float* save_rstd,
+                                             const float* gamma, float* dgamma, float* dbeta, float* dbias,
+                                             const float* partial, int nblk, float* coef, int training, int io16,
+                                             tdx_stream_t stream) {
+  if (!g || !y || !scale || !shift || !save_mean || !save_rstd || !gamma || !partial || !coef || nblk <= 0 ||
+      rows <= 0 || C <= 0)
+    return TDX_E_BADARG;
+  if (C % 4 || C > 1024) return TDX_E_SHAPE;
+  return tdx_bn_relu_bwd_tail(static_cast<float*>(g), static_cast<const float*>(y), rows, C, scale, shift, save_mean,
+                              save_rstd, gamma, dgamma, dbeta, dbias, partial, nblk, coef, training, nullptr, nullptr,
+                              nullptr, stream, io16 ? 1 : 0);
+}

@@ -602,32 +602,55 @@ extern "C" size_t tdx_edge_conv_wgrad_scratch_floats(int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return 0;
   return (size_t)tdx_small_conv_wgrad_blocks(B, H, W) * SMALLP_W;
 }
+// The _io forms: io16 != 0 -> the fat channels-last tensor (64 stored channels) holds bf16; the thin NCHW tensor, the
+// weights and the weight gradients are fp32 either way.  The fp32 entries are the _io forms at io16 == 0.
+extern "C" int tdx_initial_conv_forward_io(const float* x, const float* w, const float* bias, void* out, int B, int H,
+                                           int W, int cin, int cout, int io16, tdx_stream_t stream) {
+  if (!x || !w || !out || B <= 0 || H <= 0 || W <= 0) return TDX_E_BADARG;
+  return tdx_initial_conv_fwd(x, w, bias, out, B, H, W, cin, cout, to_stream(stream), io16 ? 1 : 0);
+}
+extern "C" int tdx_initial_conv_backward_io(const float* x, const void* g_out, float* dw, float* db, float* scratch,
+                                            int B, int H, int W, int cin, int cout, int io16, tdx_stream_t stream) {
+  if (!x || !g_out || !dw || !db || !scratch || B <= 0 || H <= 0 || W <= 0) return TDX_E_BADARG;
+  return tdx_initial_conv_wgrad(x, g_out, scratch, dw, db, B, H, W, cin, cout, to_stream(stream), io16 ? 1 : 0);
+}
+extern "C" int tdx_initial_conv_input_grad_io(const void* g_out, const float* w, float* g_x, int B, int H, int W,
+                                              int cin, int cout, int io16, tdx_stream_t stream) {
+  if (!g_out || !w || !g_x || B <= 0 || H <= 0 || W <= 0) return TDX_E_BADARG;
+  return tdx_initial_conv_dgrad(g_out, w, g_x, B, H, W, cin, cout, to_stream(stream), io16 ? 1 : 0);
+}
+extern "C" int tdx_final_conv_forward_io(const void* in, const float* w, const float* bias, float* out, int B, int H,
+                                         int W, int cout, int io16, tdx_stream_t stream) {
+  if (!in || !w || !bias || !out || B <= 0 || H <= 0 || W <= 0) return TDX_E_BADARG;
+  return tdx_final_conv_fwd(in, w, bias, out, B, H, W, cout, to_stream(stream), io16 ? 1 : 0);
+}
+extern "C" int tdx_final_conv_backward_io(const void* in, const float* g_out, const float* w, void* g_in, float* dw,
+                                          float* db, float* scratch, int B, int H, int W, int cout, int io16,
+                                          tdx_stream_t stream) {
+  if (!in || !g_out || !w || !g_in || !dw || !db || !scratch || B <= 0 || H <= 0 || W <= 0) return TDX_E_BADARG;
+  if (W < 4 || (cout != 1 && cout != 4)) return TDX_E_SHAPE;   // (before the input gradient: a refused call writes nothing)
+  const int rc = tdx_final_conv_dgrad(g_out, w, g_in, B, H, W, cout, to_stream(stream), io16 ? 1 : 0);
+  if (rc) return rc;
+  return tdx_final_conv_wgrad(in, g_out, scratch, dw, db, B, H, W, cout, to_stream(stream), io16 ? 1 : 0);
+}
 extern "C" int tdx_initial_conv_forward(const float* x, const float* w, const float* bias, float* out, int B, int H,
                                         int W, int cin, int cout, tdx_stream_t stream) {
-  if (!x || !w || !out || B <= 0 || H <= 0 || W <= 0) return TDX_E_BADARG;
-  return tdx_initial_conv_fwd(x, w, bias, out, B, H, W, cin, cout, to_stream(stream));
+  return tdx_initial_conv_forward_io(x, w, bias, out, B, H, W, cin, cout, 0, stream);
 }
 extern "C" int tdx_initial_conv_backward(const float* x, const float* g_out, float* dw, float* db, float* scratch,
                                          int B, int H, int W, int cin, int cout, tdx_stream_t stream) {
-  if (!x || !g_out || !dw || !db || !scratch || B <= 0 || H <= 0 || W <= 0) return TDX_E_BADARG;
-  return tdx_initial_conv_wgrad(x, g_out, scratch, dw, db, B, H, W, cin, cout, to_stream(stream));
+  return tdx_initial_conv_backward_io(x, g_out, dw, db, scratch, B, H, W, cin, cout, 0, stream);
 }
 extern "C" int tdx_initial_conv_input_grad(const float* g_out, const float* w, float* g_x, int B, int H, int W,
                                            int cin, int cout, tdx_stream_t stream) {
-  if (!g_out || !w || !g_x || B <= 0 || H <= 0 || W <= 0) return TDX_E_BADARG;
-  return tdx_initial_conv_dgrad(g_out, w, g_x, B, H, W, cin, cout, to_stream(stream));
+  return tdx_initial_conv_input_grad_io(g_out, w, g_x, B, H, W, cin, cout, 0, stream);
 }
 extern "C" int tdx_final_conv_forward(const float* in, const float* w, const float* bias, float* out, int B, int H,
                                       int W, int cout, tdx_stream_t stream) {
-  if (!in || !w || !bias || !out || B <= 0 || H <= 0 || W <= 0) return TDX_E_BADARG;
-  return tdx_final_conv_fwd(in, w, bias, out, B, H, W, cout, to_stream(stream));
+  return tdx_final_conv_forward_io(in, w, bias, out, B, H, W, cout, 0, stream);
 }
 extern "C" int tdx_final_conv_backward(const float* in, const float* g_out, const float* w, float* g_in, float* dw,
                                        float* db, float* scratch, int B, int H, int W, int cout,
                                        tdx_stream_t stream) {
-  if (!in || !g_out || !w || !g_in || !dw || !db || !scratch || B <= 0 || H <= 0 || W <= 0) return TDX_E_BADARG;
-  if (W < 4 || (cout != 1 && cout != 4)) return TDX_E_SHAPE;   // (before the input gradient: a refused call writes nothing)
-  const int rc = tdx_final_conv_dgrad(g_out, w, g_in, B, H, W, cout, to_stream(stream));
-  if (rc) return rc;
-  return tdx_final_conv_wgrad(in, g_out, scratch, dw, db, B, H, W, cout, to_stream(stream));
+  return tdx_final_conv_backward_io(in, g_out, w, g_in, dw, db, scratch, B, H, W, cout, 0, stream);
 }

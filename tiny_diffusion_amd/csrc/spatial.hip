@@ -649,4 +649,74 @@ int tdx_pixel_sum(const void* g, float* out, int B, int HW, int C, hipStream_t s
   return 0;
 }
 
+// ---- the C-ABI forms with the storage flag (include/tdx.h): io16 != 0 -> the activation tensors hold bf16, io16 == 0 ->
+// exactly the fp32 entries above.  No kernel and no launch of their own; every refusal comes before the first launch.
+extern "C" int tdx_maxpool2_ceil_fwd_io(const void* y, const float* scale, const float* shift, void* out, int B, int H,
+                                        int W, int C, int io16, tdx_stream_t stream) {
+  if (scale && !shift) return TDX_E_BADARG;
+  return tdx_maxpool2_ceil_fwd_t(y, scale, shift, out, B, H, W, C, io16 ? 1 : 0, stream);
+}
+
+// partial != NULL: the sum-emitting form (tdx_maxpool2_ceil_bwd_bn), which falls back to the plain kernel by itself and
+// says so with *nblk == 0
+extern "C" int tdx_maxpool2_ceil_bwd_io(const void* y, const float* scale, const float* shift, const void* g_out,
+                                        const void* skip_grad, void* g_in, int B, int H, int W, int C,
+                                        const float* bn_mean, const float* bn_rstd, float* partial, int* nblk, int io16,
+                                        tdx_stream_t stream) {
+  if (!y || !g_out || !g_in || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (scale && !shift)) return TDX_E_BADARG;
+  if (C % 4) return TDX_E_SHAPE;
+  if (!partial) {
+    if (nblk) *nblk = 0;
+    return maxpool_bwd_t(y, scale, shift, g_out, skip_grad, g_in, B, H, W, C, io16 ? 1 : 0, stream);
+  }
+  if (!nblk || !bn_mean || !bn_rstd) return TDX_E_BADARG;
+  return tdx_maxpool2_ceil_bwd_bn(y, scale, shift, g_out, skip_grad, g_in, B, H, W, C, bn_mean, bn_rstd, partial, nblk,
+                                  stream, io16 ? 1 : 0);
+}
+
+extern "C" int tdx_bilinear_ac_fwd_io(const void* in, const float* scale, const float* shift, const float* addend,
+                                      void* out, int B, int Hi, int Wi, int Ho, int Wo, int C, int out_cstride,
+                                      int out_coff, int io16, tdx_stream_t stream) {
+  if (scale && !shift) return TDX_E_BADARG;
+  return tdx_bilinear_ac_fwd_t(in, scale, shift, addend, out, B, Hi, Wi, Ho, Wo, C, out_cstride, out_coff, io16 ? 1 : 0,
+                               stream);
+}
+
+// partial != NULL: the sum-emitting form (tdx_bilinear_ac_bwd_bn); *nblk == 0 on return: it ran the plain kernel
+extern "C" int tdx_bilinear_ac_bwd_io(const void* g_out, void* g_in, int B, int Hi, int Wi, int Ho, int Wo, int C,
+                                      int g_cstride, int g_coff, const void* bn_y, const float* bn_scale,
+                                      const float* bn_shift, const float* bn_mean, const float* bn_rstd, float* partial,
+                                      int* nblk, int io16, tdx_stream_t stream) {
+  if (!g_out || !g_in || B <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || C <= 0) return TDX_E_BADARG;
+  if (C % 4 || g_cstride % 4 || g_coff % 4 || g_coff < 0 || g_coff + C > g_cstride) return TDX_E_SHAPE;
+  if (!partial) {
+    if (nblk) *nblk = 0;
+    return bilinear_ac_bwd_t(g_out, g_in, B, Hi, Wi, Ho, Wo, C, g_cstride, g_coff, io16 ? 1 : 0, stream);
+  }
+  if (!nblk || !bn_y || !bn_scale || !bn_shift || !bn_mean || !bn_rstd) return TDX_E_BADARG;
+  return tdx_bilinear_ac_bwd_bn(g_out, g_in, B, Hi, Wi, Ho, Wo, C, g_cstride, g_coff, bn_y, bn_scale, bn_shift, bn_mean,
+                                bn_rstd, partial, nblk, stream, io16 ? 1 : 0);
+}
+
+// a_splits > 0: source A is `a_splits` fp32 partial slabs of `a_slab` floats at a_partial (TdxSplitDefer, internal.h)
+extern "C" int tdx_bilinear_pair_fwd_io(const void* a, const float* a_partial, int a_splits, size_t a_slab,
+                                        const float* a_bias, const float* a_scale, const float* a_shift, int Ha, int Wa,
+                                        int Ca, const void* b, const float* b_addend, int Hb, int Wb, int Cb, void* out,
+                                        int B, int Ho, int Wo, int io16, tdx_stream_t stream) {
+  if (!out || B <= 0 || Ho <= 0 || Wo <= 0 || Ha <= 0 || Wa <= 0 || Ca <= 0 || Cb < 0 || a_splits < 0)
+    return TDX_E_BADARG;
+  if (a_splits ? (!a_partial || !a_scale || !a_shift || a_slab < (size_t)B * Ha * Wa * Ca) : !a) return TDX_E_BADARG;
+  if (Cb && (!b || Hb <= 0 || Wb <= 0)) return TDX_E_BADARG;
+  if (Ca % 4 || Cb % 4) return TDX_E_SHAPE;
+  const TdxSplitDefer defer{a_partial, a_splits, a_slab, a_bias, a_scale, a_shift};
+  return tdx_bilinear_pair_fwd_ex(a, a_splits ? &defer : nullptr, Ha, Wa, Ca, b, b_addend, Hb, Wb, Cb, out, B, Ho, Wo,
+                                  to_stream(stream), io16 ? 1 : 0);
+}
+
+extern "C" int tdx_pixel_sum_io(const void* g, float* out, int B, int HW, int C, int io16, tdx_stream_t stream) {
+  if (!g || !out || B <= 0 || HW <= 0 || C <= 0) return TDX_E_BADARG;
+  if (C % 4 || C > 1024 || 256 % (C / 4)) return TDX_E_SHAPE;
+  return tdx_pixel_sum(g, out, B, HW, C, to_stream(stream), io16 ? 1 : 0);
+}
+
 // initial_conv / final_conv and their backward passes: edge_conv.hip
