@@ -56,6 +56,8 @@ struct WinoArgs {
 constexpr int OLD = 68;            // floats per pixel of the epilogue's output image in LDS (64 channels + 4: rows stay 16-byte aligned)
 constexpr int TAB_OFF = 2 * STAGE; // floats: behind the two stages, the workgroup's tile table - per tile {byte offset of its first
                                    // output pixel in the NHWC output, validity bits of its four pixels} (built once at kernel start)
+constexpr int XREG = 2 * STAGE / 4; // floats of one wave's region of the row split's epilogue exchange (32 KB)
+constexpr int XQ = XREG / 4;        // floats of one register quad's part of it: 8 accumulators x 64 lanes x 4
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Shared epilogue: A^T . A on the sixteen accumulators of every (tile, channel) this lane holds, bias, the epilogue's
@@ -66,10 +68,22 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // division per accumulator row - measured with the workgroup stamps (tools/gpu_wino_phases.py), the scalar form cost
 // 8-9 us of a 31-50 us workgroup.
 // XH >= 0 (the row split): this wave holds channel half wn = XH of positions 8 XH .. 8 XH + 7 in acc; the other eight
-// positions' registers 4 j .. 4 j + 3 are at xin[(p * 4 + j) * 64] (p = position - 8 (1 - XH)) in LDS, read four
-// registers at a time when the row loop needs them - held in registers all at once, they spill - and the output image,
-// which overlaps them, is written once every wave has read its own.
-template <int EPI, int XH = -1>
+// positions' registers 4 j .. 4 j + 3 are at xin[(j * 8 + p) * 64] (p = position - 8 (1 - XH)) in LDS - quarter j of
+// the wave's own region of the exchange.  They are read four registers at a time (held all at once, they spill), one
+// row group ahead: the eight reads of rows 4 j + 4 .. 4 j + 7 fly while rows 4 j .. 4 j + 3 are transformed.  The output
+// image does not overlap anybody else's quads: a wave writes its 128 pixels x 32 channels into ITS OWN region -
+// rows 4 j .. 4 j + 3 (32 pixels x 32 floats, 4 KB) into the first half of quarter j, which only this wave reads and has
+// read by then - so no barrier stands between the row loop and the image; the one barrier in front of the stores
+// also publishes the statistics' sums (in the second half of quarter 0).  A store instruction's source - 16 lanes x
+// 16 bytes of one pixel - is 128 bytes in each of the two channel halves' regions, an odd and an even pixel row
+// together covering the 64 banks once.
+// Statistics: sums and counts before the stores' barrier, one barrier behind the means, one behind the M2 partials
+// (which have a slot of their own) - two barriers, where the first form had four.
+// FULL (statistics only): every tile of the workgroup lies inside the tensor with all four outputs valid (even H and
+// W, not the ragged last block).  The validity tests, selections and the count then select the value itself and
+// multiply by 1.0f: this copy of the epilogue leaves them out - the same bits from a third fewer instructions, and with
+// one wave per SIMD every instruction costs its issue slot.  The kernel picks the copy per workgroup.
+template <int EPI, int XH = -1, bool FULL = false>
 __device__ __forceinline__ void wino_epilogue(const WinoArgs& a, float* out, const float* bias, f32x16 (&acc)[16], float* smem,
                                               int tblk, int n0, int wm, int wn, int l31, int half, int tid,
                                               const f32x4* xin = nullptr) {
@@ -80,50 +94,80 @@ __device__ __forceinline__ void wino_epilogue(const WinoArgs& a, float* out, con
   float osc = 1.f, osh = 0.f;
   if (EPI == EPI_BNRELU) { osc = a.out_scale[col]; osh = a.out_shift[col]; }
   float csum = 0.f, cnt = 0.f;
-  float* ot = smem;   // [256 pixels = 64 tiles x 4][OLD]
+  constexpr bool RX = XH >= 0;
+  float* ot = smem;   // channel split: [256 pixels = 64 tiles x 4][OLD]
+  float* own = smem + (RX ? (2 * XH + wm) * XREG : 0);   // row split: this wave's region of the exchange
+  // the statistics' scratch, per (tile group, channel): slot 0 the sums, 1 the counts, 2 the M2 - and the 64 means
+  auto red = [&](int slot, int g, int c) -> float* {
+    return RX ? smem + (2 * (c >> 5) + g) * XREG + XQ / 2 + slot * 32 + (c & 31) : smem + 256 * OLD + (2 * slot + g) * 64 + c;
+  };
+  float* means = RX ? smem + XQ / 2 + 128 : smem + 256 * OLD + 384;
   // the transformed outputs replace the accumulators of positions 0, 1, 4, 5 (Y00, Y01, Y10, Y11), so that the centred
   // second pass of the statistics can read them again
-  f32x4 pv[8];
+  f32x4 pv[2][8];
+  if (RX) {
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    if (XH >= 0 && (r & 3) == 0) {
+    for (int p = 0; p < 8; ++p) pv[0][p] = xin[p * 64];
+  }
+  // Two rows (registers r, r + 1 = tiles tl, tl + 1) at a time, as float pairs: with one wave per SIMD every vector
+  // instruction costs its issue slot whatever it computes, and no MFMA runs beside these, so the 24 additions of
+  // A^T . A and the bias are packed (v_pk_add_f32: the same IEEE additions in the same order, half the instructions).
+  // (The inference epilogue keeps one row at a time, as it was.)
+  constexpr int RW = EPI == EPI_BNRELU ? 1 : 2;
+  typedef float rowv __attribute__((ext_vector_type(RW)));
 #pragma unroll
-      for (int p = 0; p < 8; ++p) pv[p] = xin[(p * 4 + (r >> 2)) * 64];
+  for (int r = 0; r < 16; r += RW) {
+    if (RX && (r & 3) == 0 && r < 12) {   // the quads of the next four rows fly while these four are transformed
+#pragma unroll
+      for (int p = 0; p < 8; ++p) pv[((r >> 2) + 1) & 1][p] = xin[(((r >> 2) + 1) * 8 + p) * 64];
     }
-    auto M = [&](int p) { return XH >= 0 && (p >> 3) != XH ? pv[p & 7][r & 3] : acc[p][r]; };
-    float s0[4], s1[4];
+    auto M = [&](int p) {
+      rowv v;
+#pragma unroll
+      for (int e = 0; e < RW; ++e) v[e] = RX && (p >> 3) != XH ? pv[(r >> 2) & 1][p & 7][(r & 3) + e] : acc[p][r + e];
+      return v;
+    };
+    rowv s0[4], s1[4], bv2;
+#pragma unroll
+    for (int e = 0; e < RW; ++e) bv2[e] = bv;
 #pragma unroll
     for (int nu = 0; nu < 4; ++nu) {
       s0[nu] = M(0 + nu) + M(4 + nu) + M(8 + nu);
       s1[nu] = M(4 + nu) - M(8 + nu) - M(12 + nu);
     }
-    float y[4] = {s0[0] + s0[1] + s0[2], s0[1] - s0[2] - s0[3], s1[0] + s1[1] + s1[2], s1[1] - s1[2] - s1[3]};
-    const int tl = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-    const unsigned m = tab[2 * tl + 1];
+    const rowv y2[4] = {s0[0] + s0[1] + s0[2] + bv2, s0[1] - s0[2] - s0[3] + bv2, s1[0] + s1[1] + s1[2] + bv2,
+                         s1[1] - s1[2] - s1[3] + bv2};
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float val = y[q] + bv;
-      if (EPI == EPI_BNRELU) val = fmaxf(fmaf(val, osc, osh), 0.f);
-      const bool ok = (m >> q) & 1u;
-      if (XH < 0) ot[(tl * 4 + q) * OLD + cl] = val;
-      csum += ok ? val : 0.f;
-      cnt += ok ? 1.f : 0.f;
-      y[q] = ok ? val : 0.f;
+    for (int e = 0; e < RW; ++e) {
+      const int re = r + e;
+      const int tl = wm * 32 + (re & 3) + 8 * (re >> 2) + 4 * half;
+      const unsigned m = FULL ? 15u : tab[2 * tl + 1];
+      float y[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float val = y2[q][e];
+        if (EPI == EPI_BNRELU) val = fmaxf(fmaf(val, osc, osh), 0.f);
+        const bool ok = (m >> q) & 1u;
+        // the image serves the stores only, and a pixel that is not valid is never stored: no masking for it
+        if (RX) own[(re >> 2) * XQ + (((re & 3) + 4 * half) * 4 + q) * 32 + l31] = val;
+        else ot[(tl * 4 + q) * OLD + cl] = val;
+        csum += ok ? val : 0.f;
+        cnt += ok ? 1.f : 0.f;
+        y[q] = ok ? val : 0.f;
+      }
+      acc[0][re] = y[0]; acc[1][re] = y[1]; acc[4][re] = y[2]; acc[5][re] = y[3];
+      if (!FULL) {
+        acc[2][re] = (m & 1u) ? 1.f : 0.f;          // validity of the four outputs, for pass two
+        acc[3][re] = (m & 2u) ? 1.f : 0.f;
+        acc[6][re] = (m & 4u) ? 1.f : 0.f;
+        acc[7][re] = (m & 8u) ? 1.f : 0.f;
+      }
     }
-    acc[0][r] = y[0]; acc[1][r] = y[1]; acc[4][r] = y[2]; acc[5][r] = y[3];
-    acc[2][r] = (m & 1u) ? 1.f : 0.f;          // validity of the four outputs, for pass two
-    acc[3][r] = (m & 2u) ? 1.f : 0.f;
-    acc[6][r] = (m & 4u) ? 1.f : 0.f;
-    acc[7][r] = (m & 8u) ? 1.f : 0.f;
   }
-  if (XH >= 0) {   // (the image of the stores only: a pixel that is not valid - y = 0 here - is never stored)
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int tl = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-      ot[(tl * 4 + 0) * OLD + cl] = acc[0][r]; ot[(tl * 4 + 1) * OLD + cl] = acc[1][r];
-      ot[(tl * 4 + 2) * OLD + cl] = acc[4][r]; ot[(tl * 4 + 3) * OLD + cl] = acc[5][r];
-    }
+  if (EPI == EPI_STATS) {   // the wave's sums and counts ride on the barrier the image needs anyway
+    const float s = csum + __shfl_xor(csum, 32, 64);
+    const float n = cnt + __shfl_xor(cnt, 32, 64);
+    if (half == 0) { *red(0, wm, cl) = s; *red(1, wm, cl) = n; }
   }
   __syncthreads();
   {
@@ -131,42 +175,41 @@ __device__ __forceinline__ void wino_epilogue(const WinoArgs& a, float* out, con
     const int c4 = (tid & 15) * 4, q = (tid >> 4) & 3;   // a wave instruction = the four pixels of one tile: tile 4 i + wave, pixel q
     const unsigned qoff = (unsigned)((((q >> 1) * a.W + (q & 1)) * a.Cout + n0 + c4) * 4);
     const uint2* tab2 = reinterpret_cast<const uint2*>(tab);
-    const float* src = ot + (tid >> 4) * OLD + c4;
+    // pixel P = (tid >> 4) + 16 i.  Row split: region 2 (c4 >> 5) + (P >> 7), chunk (P & 127) >> 5, row P & 31
+    const float* src = RX ? smem + 2 * (c4 >> 5) * XREG + (tid >> 4) * 32 + (c4 & 31) : ot + (tid >> 4) * OLD + c4;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const uint2 e = tab2[4 * i + (tid >> 6)];
       const unsigned off = ((e.y >> q) & 1u) ? e.x + qoff : 0x80000000u;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(src + i * 16 * OLD);
+      const f32x4 v = *reinterpret_cast<const f32x4*>(src + (RX ? (i >> 3) * XREG + ((i & 7) >> 1) * XQ + (i & 1) * 512 : i * 16 * OLD));
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc_out, off, 0, 0);
     }
   }
   if (EPI == EPI_STATS) {
     // per workgroup and channel: (sum, M2 about the workgroup mean) - the partials bn_finalize merges with Chan's formula
-    float* red = smem + 256 * OLD;   // [2 wm][64] sums | [2 wm][64] counts | [64] means   (behind the output image)
-    const float s = csum + __shfl_xor(csum, 32, 64);
-    const float n = cnt + __shfl_xor(cnt, 32, 64);
-    if (half == 0) { red[wm * 64 + cl] = s; red[128 + wm * 64 + cl] = n; }
-    __syncthreads();
     if (tid < 64) {
-      const float ts = red[tid] + red[64 + tid];
-      const float tn = red[128 + tid] + red[192 + tid];
-      red[256 + tid] = tn > 0.f ? ts / tn : 0.f;
+      const float ts = *red(0, 0, tid) + *red(0, 1, tid);
+      const float tn = *red(1, 0, tid) + *red(1, 1, tid);
+      means[tid] = tn > 0.f ? ts / tn : 0.f;
       a.stats[((size_t)tblk * 2 + 0) * a.Cout + n0 + tid] = ts;
     }
     __syncthreads();
-    const float mean = red[256 + cl];
+    const float mean = means[cl];
     float q = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const float d0 = acc[0][r] - mean, d1 = acc[1][r] - mean, d2 = acc[4][r] - mean, d3 = acc[5][r] - mean;
-      q = fmaf(d0 * acc[2][r], d0, q); q = fmaf(d1 * acc[3][r], d1, q);
-      q = fmaf(d2 * acc[6][r], d2, q); q = fmaf(d3 * acc[7][r], d3, q);
+      if (FULL) {   // (d * 1.0f is d)
+        q = fmaf(d0, d0, q); q = fmaf(d1, d1, q); q = fmaf(d2, d2, q); q = fmaf(d3, d3, q);
+      } else {
+        q = fmaf(d0 * acc[2][r], d0, q); q = fmaf(d1 * acc[3][r], d1, q);
+        q = fmaf(d2 * acc[6][r], d2, q); q = fmaf(d3 * acc[7][r], d3, q);
+      }
     }
     q += __shfl_xor(q, 32, 64);
-    __syncthreads();   // everyone has read the means
-    if (half == 0) red[wm * 64 + cl] = q;
+    if (half == 0) *red(2, wm, cl) = q;   // (a slot of its own: no barrier between the means' readers and this)
     __syncthreads();
-    if (tid < 64) a.stats[((size_t)tblk * 2 + 1) * a.Cout + n0 + tid] = red[tid] + red[64 + tid];
+    if (tid < 64) a.stats[((size_t)tblk * 2 + 1) * a.Cout + n0 + tid] = *red(2, 0, tid) + *red(2, 1, tid);
   }
 #endif
 }
@@ -228,42 +271,16 @@ conv3x3_wino_kernel(WinoArgs a) {
   const int n0 = nblk * WN;
   const int tpi = a.th * a.tw;   // tiles per image
 
-  // ---- the tile table of the epilogue (visible after the first barrier below)
-  if (tid < WT) {
-    const int T = T0 + tid;
-    const bool tv = T < a.NT;
-    int rem, tx;
-    const int b = div_rcp(T, tpi, a.rcp_tpi, &rem);
-    const int ty = div_rcp(rem, a.tw, a.rcp_tw, &tx);
-    const bool r1 = 2 * ty + 1 < a.H, c1 = 2 * tx + 1 < a.W;
-    unsigned* tab = reinterpret_cast<unsigned*>(smem + TAB_OFF);
-    tab[2 * tid] = tv ? (unsigned)(((b * a.H + 2 * ty) * a.W + 2 * tx) * a.Cout * 4) : 0u;
-    tab[2 * tid + 1] = tv ? (1u | (c1 ? 2u : 0u) | (r1 ? 4u : 0u) | (r1 && c1 ? 8u : 0u)) : 0u;
-  }
-
-  // ---- DMA maps.  A: instruction (px, g) covers pixel px of the 32 tiles of group g: lane L -> tile g*32 + (L >> 1),
-  // k-half L & 1 (4 channels); this wave issues px = 4*wave .. 4*wave+3 for both groups.
+  // ---- Prologue order: the weight pieces of stage 0 depend on nothing but the workgroup's ids, so they are requested
+  // first and fly while the tile table and the patch offsets (four divisions and the border tests per lane) are
+  // computed; then the patches of stage 0, then the weights of stage 1.  Everything of stage 0 is still requested
+  // before anything of stage 1: the counted wait in front of the first barrier keeps its meaning.
+  // DMA maps.  B: a stage is 32 contiguous KiB of the pack; this wave copies KiB 8*wave .. 8*wave+7
   const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, (int)((int64_t)a.M * a.Cin * 4), 0x00020000);
   const auto rsrc_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.u), 0, a.Cout * 16 * a.Cin * 4, 0x00020000);
   constexpr unsigned OOB = 0x80000000u;
-  unsigned a_off[4][2];
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    const int T = T0 + g * 32 + (lane >> 1);
-    const bool tv = T < a.NT;
-    int rem, tx;
-    const int b = div_rcp(T, tpi, a.rcp_tpi, &rem);
-    const int ty = div_rcp(rem, a.tw, a.rcp_tw, &tx);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int px = 4 * wave + j;
-      const int ih = 2 * ty - 1 + (px >> 2), iw = 2 * tx - 1 + (px & 3);
-      const bool ok = tv && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W;
-      a_off[j][g] = ok ? (unsigned)((((b * a.H + ih) * a.W + iw) * a.Cin + (lane & 1) * 4) * 4) : OOB;
-    }
-  }
-  // B: a stage is 32 contiguous KiB of the pack; this wave copies KiB 8*wave .. 8*wave+7
   const unsigned u_base = (unsigned)(nblk * (a.Cin / WK)) * (unsigned)(B_ST * 4) + (unsigned)(wave * 8 * 1024 + lane * 16);
+  unsigned a_off[4][2];
 
   const int s0 = SPLITK ? (int)blockIdx.y * a.per : 0;                        // first stage of this workgroup
   const int ns = SPLITK ? min(a.per, a.Cin / WK - s0) : a.Cin / WK;             // and how many
@@ -280,12 +297,53 @@ conv3x3_wino_kernel(WinoArgs a) {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_in, (lds_ptr_t)(Ab + (4 * wave + ((i - 8) >> 1)) * 512 + ((i - 8) & 1) * 256), 16,
                                                a_off[(i - 8) >> 1][(i - 8) & 1], (unsigned)(sc * WK * 4), 0, 0);
   };
+  // (Training instantiations only, like the peeled first stage below: the inference instantiations keep the requests
+  // behind the arithmetic, as they were.)
+  constexpr bool PEEL = !SPLITK && EPI != EPI_BNRELU;
+  if (PEEL) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) piece(i, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);   // (the requests stay in front of the arithmetic below)
+  }
+
+  // ---- the tile table of the epilogue (visible after the first barrier below)
+  if (tid < WT) {
+    const int T = T0 + tid;
+    const bool tv = T < a.NT;
+    int rem, tx;
+    const int b = div_rcp(T, tpi, a.rcp_tpi, &rem);
+    const int ty = div_rcp(rem, a.tw, a.rcp_tw, &tx);
+    const bool r1 = 2 * ty + 1 < a.H, c1 = 2 * tx + 1 < a.W;
+    unsigned* tab = reinterpret_cast<unsigned*>(smem + TAB_OFF);
+    tab[2 * tid] = tv ? (unsigned)(((b * a.H + 2 * ty) * a.W + 2 * tx) * a.Cout * 4) : 0u;
+    tab[2 * tid + 1] = tv ? (1u | (c1 ? 2u : 0u) | (r1 ? 4u : 0u) | (r1 && c1 ? 8u : 0u)) : 0u;
+  }
+
+  // ---- A: instruction (px, g) covers pixel px of the 32 tiles of group g: lane L -> tile g*32 + (L >> 1), k-half L & 1
+  // (4 channels); this wave issues px = 4*wave .. 4*wave+3 for both groups - one patch row (px >> 2 == wave): the row
+  // test and the row's offset are common to the four.
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    const int T = T0 + g * 32 + (lane >> 1);
+    const bool tv = T < a.NT;
+    int rem, tx;
+    const int b = div_rcp(T, tpi, a.rcp_tpi, &rem);
+    const int ty = div_rcp(rem, a.tw, a.rcp_tw, &tx);
+    const int ih = 2 * ty - 1 + wave;
+    const bool rok = tv && (unsigned)ih < (unsigned)a.H;
+    const int rowpx = (b * a.H + ih) * a.W;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int iw = 2 * tx - 1 + j;
+      const bool ok = rok && (unsigned)iw < (unsigned)a.W;
+      a_off[j][g] = ok ? (unsigned)(((rowpx + iw) * a.Cin + (lane & 1) * 4) * 4) : OOB;
+    }
+  }
 
   // Training launches (statistics epilogue, plain input gradient) never zero the 256 accumulator registers: their first
   // stage is a second copy of the stage's code whose first MFMA of every position takes the constant 0 as C (0.43 us
   // of a 23-40 us workgroup: step 9.98 -> 9.87 ms).  The inference launches keep the zeroing: their workgroups run 4-16
   // stages from a cold instruction cache, and the second copy cost a reverse step 8 us at n = 16 and 17 us at n = 64.
-  constexpr bool PEEL = !SPLITK && EPI != EPI_BNRELU;
   f32x16 acc[16];
   const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (!PEEL) {
@@ -296,7 +354,7 @@ conv3x3_wino_kernel(WinoArgs a) {
   }
 
 #pragma unroll
-  for (int i = 0; i < 16; ++i) piece(i, 0, 0);
+  for (int i = PEEL ? 8 : 0; i < 16; ++i) piece(i, 0, 0);   // (PEEL: the weights of stage 0 went out at the top)
   unsigned long long t_issued = 0, t_landed = 0, t_loop = 0, c_loop = 0;
   if constexpr (ROWS) {
     // ---- the row split.  Wave (h, wm) = wave 2 h + wm owns tiles 32 wm .. 32 wm + 31, the positions xi = 2h, 2h+1 (all
@@ -314,7 +372,9 @@ conv3x3_wino_kernel(WinoArgs a) {
     // Epilogue: A^T . A mixes all four xi rows.  Wave (h, wm) keeps channel half h and hands its 8 accumulators of half
     // 1-h to wave (1-h, wm) through the free ring (32 KB per wave, 128 KB = the two stages: the tile table stays); the
     // shared epilogue then does what wave (wm, wn = h) of the channel split did, with the same arithmetic, reading the
-    // received rows from LDS as it goes (XH).
+    // received rows from LDS one row group ahead and writing its part of the output image into its own region of the
+    // exchange as the quarters empty (XH; the layout and the barriers: above wino_epilogue).  A forward workgroup whose
+    // 256 outputs are all valid takes the epilogue's copy without the validity masks (FULL).
     static_assert(4 * 8 * 16 * 64 == 2 * STAGE, "the exchange fills the ring");
 #pragma unroll
     for (int i = 0; i < 8; ++i) piece(i, 1, 1);
@@ -412,20 +472,26 @@ conv3x3_wino_kernel(WinoArgs a) {
       for (int s = 1; s < ns; ++s) stage(std::false_type{}, s);
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the requests past the end; the ring is free
       if (a.stamps) { t_loop = __builtin_amdgcn_s_memrealtime(); c_loop = __builtin_amdgcn_s_memtime() - c_loop; }
-      // exchange: [receiving wave][accumulator][register quad][lane][4] (16-byte lane runs: conflict-free)
+      // exchange: [receiving wave][register quad][accumulator][lane][4] (16-byte lane runs: conflict-free).  Quad-major:
+      // the eight reads of one row group empty one quarter (XQ floats) of the receiver's region, which then takes that
+      // group's rows of the output image (see wino_epilogue)
       {
-        f32x4* xo = reinterpret_cast<f32x4*>(smem) + (2 * (1 - H) + wm) * 2048 + lane;
+        f32x4* xo = reinterpret_cast<f32x4*>(smem + (2 * (1 - H) + wm) * XREG) + lane;
 #pragma unroll
         for (int pp = 0; pp < 8; ++pp)
 #pragma unroll
           for (int r4 = 0; r4 < 4; ++r4) {
             const f32x16& x = acc[8 * (1 - H) + pp];
-            xo[(pp * 4 + r4) * 64] = f32x4{x[4 * r4], x[4 * r4 + 1], x[4 * r4 + 2], x[4 * r4 + 3]};
+            xo[(r4 * 8 + pp) * 64] = f32x4{x[4 * r4], x[4 * r4 + 1], x[4 * r4 + 2], x[4 * r4 + 3]};
           }
       }
       __syncthreads();
-      wino_epilogue<EPI, H>(a, a.out, a.bias, acc, smem, tblk, n0, wm, H, l31, half, tid,
-                            reinterpret_cast<const f32x4*>(smem) + wave * 2048 + lane);
+      if (EPI == EPI_STATS && !((a.H | a.W) & 1) && T0 + WT <= a.NT)   // all 256 outputs valid: the FULL copy
+        wino_epilogue<EPI, H, true>(a, a.out, a.bias, acc, smem, tblk, n0, wm, H, l31, half, tid,
+                                    reinterpret_cast<const f32x4*>(smem + wave * XREG) + lane);
+      else
+        wino_epilogue<EPI, H>(a, a.out, a.bias, acc, smem, tblk, n0, wm, H, l31, half, tid,
+                              reinterpret_cast<const f32x4*>(smem + wave * XREG) + lane);
     };
     if (wn) body(std::integral_constant<int, 1>{});
     else body(std::integral_constant<int, 0>{});
@@ -535,7 +601,7 @@ conv3x3_wino_kernel(WinoArgs a) {
     if (a.stamps) { t_loop = __builtin_amdgcn_s_memrealtime(); c_loop = __builtin_amdgcn_s_memtime() - c_loop; }
     if (SPLITK)   // raw partials: bias and epilogue are the split-K reduction's
       wino_epilogue<EPI_PLAIN>(a, a.out + (size_t)blockIdx.y * (size_t)a.M * a.Cout, nullptr, acc, smem, tblk, n0, wm, wn, l31, half, tid);
-    else
+    else   // (no FULL copy here: with all sixteen positions in its registers this instantiation spills around the choice)
       wino_epilogue<EPI>(a, a.out, a.bias, acc, smem, tblk, n0, wm, wn, l31, half, tid);
   }
   if (a.stamps && tid == 0) {   // 10-ns ticks: entry, first stage requested, landed, loop end, epilogue end; loop cycles; ids
