@@ -1144,6 +1144,45 @@ const char* tdx_tune_name(int index);
 int tdx_diag_set_buffer(void* device_buffer, size_t bytes);
 int tdx_diag_conv_occupancy(int tile);  /* resident workgroups per CU of the forward kernel of tile bm*1000+bn */
 
+/* Additions within ABI 400: the pairwise kernels of the sample-quality metrics (metrics.hip; metrics.py builds the
+ * Frechet distance, KID and precision / recall on them).  a (na, d) and b (nb, d) are row-major fp32 feature matrices,
+ * every na, nb, d >= 1.  One kernel body computes
+ *     g_ij = fma(a_i[d-1], b_j[d-1], ... fma(a_i[1], b_j[1], fma(a_i[0], b_j[0], 0)))
+ * - the k-ordered fp32 fmaf chain of v_mfma_f32_32x32x2_f32, the same bits for every tiling and chunking - and four
+ * epilogues take what a metric needs from it; only tdx_pair_gram writes the pair matrix.  The three reductions:
+ *   - squared row norms, by the library from the same matrices: n_i = fma(x[d-1], x[d-1], ... fma(x[0], x[0], 0)), so
+ *     the norm of a row equals its g with a bit-identical row;
+ *   - d2_ij = max(0, (|a_i|^2 + |b_j|^2) - 2 g_ij): one fp32 add, the exact doubling, one fp32 subtraction, the floor;
+ *   - the candidates b are cut into col_chunks chunks of whole 128-row tiles (0: the library chooses; more chunks than
+ *     tiles are clipped), grid = ceil(na / 128) x chunks; each chunk writes a partial result per query to `scratch`
+ *     and a second launch folds the chunks in ascending order.  No atomics: every output is bit-reproducible from
+ *     launch to launch, and those of tdx_pair_kth_dist2 and tdx_pair_member are the same bits for every col_chunks
+ *     (d2 does not depend on the chunking, and a k-smallest multiset or an OR does not depend on the order);
+ *   - scratch: tdx_pair_scratch_bytes(na, nb, k, col_chunks) bytes (k: that of tdx_pair_kth_dist2, 0 for the other
+ *     two; 0 is returned for na, nb <= 0, col_chunks < 0 or k > 8), 16-byte aligned.  TDX_E_WORKSPACE when smaller.
+ * TDX_E_BADARG, before any launch and with nothing written: a null pointer, na, nb or d <= 0, col_chunks < 0, and the
+ * cases named at each entry.  All launches go to `stream`; capturable. */
+size_t tdx_pair_scratch_bytes(int na, int nb, int k, int col_chunks);
+/* out (na, nb): out[i * nb + j] = g_ij. */
+int tdx_pair_gram(const float* a, const float* b, int na, int nb, int d, float* out, tdx_stream_t stream);
+/* out (na,): the k-th smallest d2_ij over j (ties count: the k-th element of the sorted row).  exclude_diag != 0
+ * leaves out j == i by INDEX - an exact duplicate of row i elsewhere in b still counts, at distance 0.
+ * 1 <= k <= 8 and nb >= k (nb >= k + 1 with exclude_diag); TDX_E_BADARG otherwise. */
+int tdx_pair_kth_dist2(const float* a, const float* b, int na, int nb, int d, int k, int exclude_diag, int col_chunks,
+                       float* out, void* scratch, size_t scratch_bytes, tdx_stream_t stream);
+/* flag (na,) int32: flag[i] = 1 if d2_ij <= r2[j] for some j, else 0.  r2 (nb,) belongs to the CANDIDATES b: query a_i
+ * is a member when it lies inside the ball of some b_j. */
+int tdx_pair_member(const float* a, const float* b, const float* r2, int na, int nb, int d, int col_chunks,
+                    int32_t* flag, void* scratch, size_t scratch_bytes, tdx_stream_t stream);
+/* out (na,) fp64: out[i] = sum_j v_ij^3 with v_ij = fma((double)gamma, (double)g_ij, (double)coef0) and the cube
+ * (v * v) * v, all in fp64 (exclude_diag != 0: j != i, by index).  Each lane half adds its candidates in ascending j
+ * (of a 128-tile at offset 32 t: rows (r & 3) + 8 (r >> 2) + 4 h, h = 0 | 1 the half), the chunk's value is
+ * half 0 + half 1, and the chunks are added in ascending order: reproducible, but a function of col_chunks in the
+ * last fp64 bits.  gamma and coef0 finite (TDX_E_BADARG otherwise). */
+int tdx_pair_poly_rowsum(const float* a, const float* b, int na, int nb, int d, float gamma, float coef0,
+                         int exclude_diag, int col_chunks, double* out, void* scratch, size_t scratch_bytes,
+                         tdx_stream_t stream);
+
 /* Peak probes used by bench.py for measured roofline denominators. */
 int tdx_probe_mfma_f32(float* out, int iters, int blocks, tdx_stream_t stream);
 int tdx_probe_stream_copy(const float* src, float* dst, int64_t n, tdx_stream_t stream);

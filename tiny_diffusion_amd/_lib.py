@@ -273,6 +273,13 @@ _SIGS = {
     "tdx_diag_set_buffer": (C.c_int, [_ptr, C.c_size_t]),
     "tdx_probe_mfma_f32": (C.c_int, [_ptr, C.c_int, C.c_int, _ptr]),
     "tdx_probe_stream_copy": (C.c_int, [_ptr, _ptr, C.c_int64, _ptr]),
+    # the pairwise kernels of the sample-quality metrics (metrics.hip)
+    "tdx_pair_scratch_bytes": (C.c_size_t, [C.c_int] * 4),
+    "tdx_pair_gram": (C.c_int, [_ptr, _ptr, C.c_int, C.c_int, C.c_int, _ptr, _ptr]),
+    "tdx_pair_kth_dist2": (C.c_int, [_ptr, _ptr] + [C.c_int] * 6 + [_ptr, _ptr, C.c_size_t, _ptr]),
+    "tdx_pair_member": (C.c_int, [_ptr, _ptr, _ptr] + [C.c_int] * 4 + [_ptr, _ptr, C.c_size_t, _ptr]),
+    "tdx_pair_poly_rowsum": (C.c_int, [_ptr, _ptr] + [C.c_int] * 3 + [C.c_float, C.c_float, C.c_int, C.c_int,
+                                                                    _ptr, _ptr, C.c_size_t, _ptr]),
 }
 
 EXPORTS = tuple(_SIGS)
