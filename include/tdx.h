@@ -255,6 +255,20 @@ int tdx_vlb_terms(const float* x0, const float* x_t, const float* out, const flo
                   const float* rows, int batch, int per_sample, float clip_lo, float clip_hi, float data_lo,
                   float data_hi, int bins, float* terms, int64_t sample_stride, tdx_stream_t stream);
 
+/* The per-sample squared norm of the model's noise prediction (csrc/analytic.hip): the statistic of the KL-optimal
+ * reverse variance (Bao et al. 2022, Analytic-DPM; tiny_diffusion_amd/analytic.py).  With (ex, eo) = rows[t[b]] of the
+ * fp32 (T, 2) table - (0, 1) for an eps-model, (sqrt(1 - abar), sqrt(abar)) for a v-model -
+ *   sums[b * sample_stride] = sum_i (ex x_t[b,i] + eo out[b,i])^2,
+ * each product and sum rounded separately.  One workgroup of 256 per sample, 16-byte loads, one pass over the two
+ * inputs (8 B/element); the sum is reduced inside the wave, then across the four waves through LDS in wave order (no
+ * global atomics): a sample's number is bit-reproducible and does not depend on batch or on the other samples.
+ * sample_stride (floats, >= 1) lets a caller write column k of an (N, S) buffer directly.  t is not range-checked, as
+ * in tdx_q_sample.
+ * TDX_E_BADARG, before any GPU call and with nothing written: a null pointer, batch <= 0, per_sample <= 0,
+ * per_sample % 4, sample_stride < 1. */
+int tdx_eps_sqnorm(const float* x_t, const float* out, const int64_t* t, const float* rows, int batch, int per_sample,
+                   float* sums, int64_t sample_stride, tdx_stream_t stream);
+
 /* Condition dropout for training the unconditional branch: sample b is dropped iff a Philox uniform in [0,1) keyed by
  * (seed, offset, b) is < p (p == 0: exact copy, p == 1: every sample).  A dropped sample gets label -1 / a zeroed row.
  * The two entries draw the same mask for the same key.  In place (y_out == y, c_out == c) is allowed. */

@@ -239,6 +239,7 @@ _SIGS = {
                                                 C.c_int, C.c_uint64, C.c_int, C.c_int] + [C.c_float] * 3 + [_ptr] * 3
                                       + [C.c_int, C.c_float, _ptr, _ptr]),
     "tdx_vlb_terms": (C.c_int, [_ptr] * 6 + [C.c_int, C.c_int] + [C.c_float] * 4 + [C.c_int, _ptr, C.c_int64, _ptr]),
+    "tdx_eps_sqnorm": (C.c_int, [_ptr] * 4 + [C.c_int, C.c_int, _ptr, C.c_int64, _ptr]),
     "tdx_p_sample_step_guided": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int64, C.c_float, C.c_int,
                                            C.c_uint64, _ptr, _ptr]),
     "tdx_p_sample_step_x0": (C.c_int, [_ptr] * 7 + [C.c_int64, C.c_float, C.c_float, C.c_int, C.c_uint64, _ptr, _ptr]),

@@ -33,7 +33,9 @@ def sample(noise_model: NoiseModel, diffusion: ForwardProcess, device, n_samples
     existing ``x_T=`` and ``timesteps=`` arguments and is not part of this (schedule.sample_loop).  ``dynamic_threshold=q`` (through ``**kw``; q in (0, 1]): Imagen's dynamic thresholding on the range of
     ``clip_denoised`` ((-1, 1) when that is off) - per sample and step the q-quantile s of ``|x0 - centre|`` bounds the
     implied x_0 and, where it exceeds the half range h, scales it back by h / s (schedule.sample_loop); ``ddim_sample``
-    and ``dpm_sample`` take it too."""
+    and ``dpm_sample`` take it too.  ``variance=m`` (through ``**kw``; an ``EpsMoments`` of ``analytic.estimate_eps_moments``): the chain adds noise of
+    the KL-optimal scale of this model (Bao et al. 2022, Analytic-DPM) instead of the schedule's - sigma is a table column, the mean of
+    every step is unchanged (schedule.sample_loop); ``ddim_sample`` takes it too at ``eta`` > 0, ``dpm_sample`` is deterministic and refuses it."""
     return sample_loop(noise_model, diffusion, device, n_samples, None, **kw)
 
 
@@ -64,5 +66,6 @@ def bits_per_dim(noise_model: NoiseModel, diffusion: ForwardProcess, x_0, bins=2
     likelihood.bits_per_dim_loop): ``BitsPerDim(total_bpd, prior_bpd, vb, mse, xstart_mse)`` over all T timesteps.
     The defaults are Ho et al.'s and improved-DDPM's settings for pixels: the discretised decoder over 256 levels of
     [-1, 1] and the clamped x0 prediction.  ``noises`` / ``philox_seed``, ``prediction``, ``variance`` and
-    ``data_range`` pass through."""
+    ``data_range`` pass through.  ``variance`` may also be an ``EpsMoments`` (the KL-optimal variance of this model,
+    analytic.py) and ``timesteps=[...]`` evaluates the bound of the K-step chain over an ascending sub-list (likelihood.bits_per_dim_loop)."""
     return bits_per_dim_loop(noise_model, diffusion, x_0, None, bins=bins, clip_denoised=clip_denoised, **kw)

@@ -41,7 +41,9 @@ def sample(vae: VAE, noise_model: NoiseModel, diffusion: ForwardProcess, device,
     (schedule.sample_loop).  ``ddim_sample`` and ``dpm_sample`` take the two keywords too.  ``dynamic_threshold=q`` (through ``**kw``; q in (0, 1]): Imagen's dynamic thresholding on the range of
     ``clip_denoised`` ((-1, 1) when that is off) - per sample and step the q-quantile s of ``|x0 - centre|`` bounds the
     implied z_0 and, where it exceeds the half range h, scales it back by h / s (schedule.sample_loop); ``ddim_sample``
-    and ``dpm_sample`` take it too."""
+    and ``dpm_sample`` take it too.  ``variance=m`` (through ``**kw``; an ``EpsMoments`` of ``analytic.estimate_eps_moments``): the chain adds noise of
+    the KL-optimal scale of this model (Bao et al. 2022, Analytic-DPM) instead of the schedule's - sigma is a table column, the mean of
+    every step is unchanged (schedule.sample_loop); ``ddim_sample`` takes it too at ``eta`` > 0, ``dpm_sample`` is deterministic and refuses it."""
     _check_labels(y, n_samples)
     vae.eval()
     z = sample_loop(noise_model, diffusion, device, n_samples, y, **kw)
@@ -78,7 +80,8 @@ def bits_per_dim(noise_model: NoiseModel, diffusion: ForwardProcess, x_0, y=None
     eq. 5; likelihood.bits_per_dim_loop): ``BitsPerDim(total_bpd, prior_bpd, vb, mse, xstart_mse)`` over all T timesteps
     under the condition ``y``.  The defaults suit latents: a continuous Gaussian decoder at t = 0 and no clamp, so
     the result is a density and can be negative.  ``noises`` / ``philox_seed``, ``prediction``, ``variance``, ``bins``
-    and ``data_range`` pass through."""
+    and ``data_range`` pass through.  ``variance`` may also be an ``EpsMoments`` (the KL-optimal variance of this model,
+    analytic.py) and ``timesteps=[...]`` evaluates the bound of the K-step chain over an ascending sub-list (likelihood.bits_per_dim_loop)."""
     if y is None:
         raise ValueError("Class labels 'y' must be provided for conditional generation.")
     return bits_per_dim_loop(noise_model, diffusion, x_0, y, bins=bins, clip_denoised=clip_denoised, **kw)

@@ -341,6 +341,26 @@ class TimestepSchedule:
         coef64 = torch.stack([c1 * den, c2 * sa / den, sigma], dim=1).contiguous()
         return TimestepSchedule(self.num_timesteps, self.timesteps, coef64, eta=self.eta)
 
+    def with_sigma(self, sigma64) -> "TimestepSchedule":
+        """This chain with another noise scale: a new schedule whose ``coef`` keeps the fp32 (c1, c2) columns bit for
+        bit - for ``ddpm_schedule`` they are the reference's own rows, not roundings of ``coef64`` - and holds
+        ``sigma64`` rounded once to fp32 in column 2; ``coef64`` likewise keeps (c1, c2) and takes ``sigma64``.  The mean
+        of every step is unchanged.  ``sigma64``: (S,) finite real numbers >= 0 (``ValueError`` otherwise, and on a
+        ``MultistepSchedule``, which has no noise)."""
+        if isinstance(self, MultistepSchedule):
+            raise ValueError("a multistep chain is deterministic: it has no sigma")
+        sigma64 = torch.as_tensor(sigma64)
+        if sigma64.dtype == torch.bool or sigma64.is_complex() or tuple(sigma64.shape) != (self.steps,):
+            raise ValueError(f"sigma must hold one real number per step ({self.steps}), got {tuple(sigma64.shape)}")
+        sigma64 = sigma64.detach().to("cpu", torch.float64)
+        if not bool(torch.isfinite(sigma64).all()) or bool((sigma64 < 0).any()):
+            raise ValueError("sigma must be finite and >= 0")
+        coef64, coef = self.coef64.clone(), self.coef.clone()
+        coef64[:, 2] = sigma64
+        coef[:, 2] = sigma64.to(torch.float32)
+        return TimestepSchedule(self.num_timesteps, self.timesteps, coef64.contiguous(), coef=coef.contiguous(),
+                                eta=self.eta)
+
     def x0_form(self, diffusion: ForwardProcess, prediction: str = "eps", device=None, dtype=torch.float32):
         """The (S, 5) table ``(p, q, A, Bx, sigma)`` of this chain's update in x0 form (clipped-x0 sampling): with
         a = sqrt(acp[tau_k]), b = sqrt(1 - acp[tau_k]) and this schedule's eps-form row (c1, c2, sigma),
@@ -766,7 +786,8 @@ def ddim_sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: 
                      eta: float = 0.0, timesteps=None, **kw):
     """``sample_loop`` on ``ddim_schedule(diffusion, steps | timesteps, eta)``: ``timesteps``, when given,
     replaces ``steps``.  The drop-in modules' ``ddim_sample`` functions call this (``guidance_scale`` and the other
-    keywords of ``sample_loop`` pass through, ``prediction`` and ``known`` / ``mask`` among them)."""
+    keywords of ``sample_loop`` pass through, ``prediction``, ``known`` / ``mask`` and ``variance`` - an ``EpsMoments``:
+    the KL-optimal sigma of this chain at this ``eta`` > 0 - among them)."""
     _prediction(kw.get("prediction", "eps"))
     _dynamic_threshold(kw.get("dynamic_threshold"), _clip_denoised(kw.get("clip_denoised")))
     if kw.get("guidance_scale") is not None:
@@ -789,6 +810,8 @@ def dpm_sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: i
         _guidance_scale(noise_model, kw["guidance_scale"], y)   # an argument error comes before the schedule's
     if kw.get("noises") is not None:
         raise ValueError("a multistep chain is deterministic: it takes no noises")
+    if kw.get("variance") is not None:
+        raise ValueError("a multistep chain is deterministic: it takes no variance")
     if "schedule" in kw:
         raise ValueError("dpm_sample builds its own schedule: give steps or timesteps")
     _known_mask(kw.get("known"), kw.get("mask"), n_samples, _in_shape(noise_model))
@@ -797,12 +820,36 @@ def dpm_sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: i
     return sample_loop(noise_model, diffusion, device, n_samples, y, schedule=sched, **kw)
 
 
+def _with_optimal_sigma(diffusion: ForwardProcess, schedule, moments, prediction: str, clip):
+    """``schedule`` (``None``: ``ddpm_schedule(diffusion)``, eta = 1) with the sigma column of the KL-optimal reverse
+    variance of ``moments`` (analytic.optimal_sigma2); every argument error of ``sample_loop(variance=...)``."""
+    from .analytic import EpsMoments, optimal_sigma2   # analytic imports this module
+
+    if not isinstance(moments, EpsMoments):
+        raise ValueError(f"variance must be None or an EpsMoments (analytic.estimate_eps_moments), got {moments!r}")
+    if moments.prediction != prediction:
+        raise ValueError(f"the moments were estimated for prediction={moments.prediction!r}, the chain runs with "
+                         f"prediction={prediction!r}")
+    if isinstance(schedule, MultistepSchedule):
+        raise ValueError("a multistep chain is deterministic: it takes no variance")
+    if schedule is None:
+        schedule, eta = ddpm_schedule(diffusion), 1.0
+    else:
+        if schedule.num_timesteps != diffusion.num_timesteps:
+            raise ValueError(f"the schedule was built for T = {schedule.num_timesteps}, the diffusion has "
+                             f"T = {diffusion.num_timesteps}")
+        eta = 1.0 if schedule.eta is None else schedule.eta
+    finite = clip is not None and math.isfinite(clip[0]) and math.isfinite(clip[1])
+    sigma2 = optimal_sigma2(diffusion, moments, schedule.timesteps, eta, clip if finite else None)
+    return schedule.with_sigma(torch.sqrt(sigma2))
+
+
 @torch.no_grad()
 def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, y=None,
                 x_T: Optional[torch.Tensor] = None, noises=None, use_graph: bool = False,
                 philox_seed: Optional[int] = None, schedule: Optional[TimestepSchedule] = None,
                 guidance_scale: Optional[float] = None, prediction: str = "eps", clip_denoised=None,
-                known=None, mask=None, dynamic_threshold=None):
+                known=None, mask=None, dynamic_threshold=None, variance=None):
     """Reverse process, diffusion.py:254-276.
 
     Default (``x_T is None and noises is None``): the reference's RNG consumption -
@@ -864,6 +911,16 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
     cannot run in final_conv's epilogue, since a sample's bound needs the whole output.  The (n, 2) buffer of bounds is
     allocated once per call, outside every capture.  The returned sample lies in [lo, hi] exactly.  ``ValueError``,
     before any GPU work, for a bool, a NaN, a q outside (0, 1] or an infinite bound.
+    ``variance``: ``None`` (the code paths above, unchanged - every launch, table and allocation) or an ``EpsMoments``
+    (``analytic.estimate_eps_moments``) - the chain adds noise of the KL-optimal scale of this model (Bao et al. 2022,
+    Analytic-DPM) instead of the schedule's: it runs on ``(schedule or ddpm_schedule(diffusion)).with_sigma(sqrt(
+    optimal_sigma2(diffusion, variance, schedule.timesteps, eta)))`` with the schedule's own eta (1 for
+    ``ddpm_schedule``), down the scheduled path of all three modes and every combination above - sigma is a table
+    column, no kernel changes and the mean of every step is the schedule's.  The bounded-data cap of
+    ``optimal_sigma2`` uses the range of ``clip_denoised`` / ``dynamic_threshold`` when that is finite and is off
+    otherwise.  Under guidance the g of the conditional model is used (an approximation).  ``ValueError``, before any
+    GPU work, for anything but an ``EpsMoments``, one estimated for another ``prediction`` or T or without the chain's
+    timesteps, a deterministic chain (eta = 0, a ``MultistepSchedule``).
     """
     prediction = _prediction(prediction)
     clip = _clip_denoised(clip_denoised)
@@ -877,6 +934,8 @@ def sample_loop(noise_model, diffusion: ForwardProcess, device, n_samples: int, 
     w = _guidance_scale(noise_model, guidance_scale, y) if guided else None
     shape = _in_shape(noise_model)
     km = _known_mask(known, mask, n_samples, shape)
+    if variance is not None:
+        schedule = _with_optimal_sigma(diffusion, schedule, variance, prediction, clip)
     device = torch.device(device)
     if device.type != "cuda":
         raise _lib.TdxError("sampling runs on the GPU only (no CPU fallback)")
