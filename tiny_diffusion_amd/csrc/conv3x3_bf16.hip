@@ -1617,7 +1617,9 @@ extern "C" int tdx_conv3x3_wgrad_bf16_io(const void* in_, const void* dy_, float
   a.groups = a.tilesCi * a.tilesCo * splits;
   a.adv_q = 0; a.adv_s = 0; a.dbg = g_knobs.conv_dbg;
   hipStream_t st = to_stream(stream);
-  if (io16 && g_knobs.bf16_wgrad9 && W <= 95) return launch_wgrad9_bf16(a, splits, in_bn, st);   // (ring of <= 7 blocks: 96 KB of LDS)
+  // (ring of <= 7 blocks: 96 KB of LDS.  A padded sample of fewer than 8 slots - the 1x1, 1x2 and 2x1 maps - goes to the
+  // per-tap kernel: pos_of shifts a slot by 8 samples, its first block starts >= 64 slots in front of the tensor)
+  if (io16 && g_knobs.bf16_wgrad9 && W <= 95 && (H + 1) * (W + 1) >= 8) return launch_wgrad9_bf16(a, splits, in_bn, st);
 #define TDX_WG(BM_, BN_)                                                                        \
   (io16 ? (g_knobs.bf16_wgrad_swz ? launch_wgrad_bf16s<BM_, BN_>(a, in_bn, st) : launch_wgrad_bf16<BM_, BN_, true>(a, in_bn, st)) \
         : launch_wgrad_bf16<BM_, BN_, false>(a, in_bn, st))
